@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- learned-index seeding throughput of the MI355X backend (BASELINE.json metric).
 
-  python bench.py --gpus 1 --steps 5 --warmup 1
+  python bench.py --gpus 1 --steps 5 --warmup 1 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-         bench.py --gpus N --steps K --warmup W
+         bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up (genome, index on the device, reads), warms up, times the K steps and prints the headline line; --dump-outputs DIR
+then also writes what the last timed step computed (a fixed, seeded sample of its SMEMs and hits) as DIR/*.npy.  --full adds everything
+else below: the parity check against the oracle, the roofline, the CPU baselines, the other legs and the counter passes.
 
 A "step" is one pass of the seeding hot path (P-RMI lookup -> SA last-mile search -> SMEM enumeration,
 all three rounds, hit gather included) over one batch of synthetic 150-bp reads that is already resident
@@ -15,7 +19,7 @@ suffix-array entries in HBM -- and 10 M synthetic 150-bp single-end reads per GP
 -- suffix array, entries, P-RMI -- is built on the GPU in a few seconds (MEME_BENCH_SA=host: our host builders, minutes,
 cached in /dev/shm for the next invocation).
 
-Besides the headline line's `roofline` and `cpu_baseline` objects, rank 0 at N=1 adds `chain` (chaining of 2 M of the batch's reads on the device), `ext` (+ `cigar`), `kswv` (mate-rescue Smith-Waterman jobs), `bsw` (the banded-SW kernel on 2 M
+With --full, besides the headline line's `roofline` and `cpu_baseline` objects, rank 0 at N=1 adds `chain` (chaining of 2 M of the batch's reads on the device), `ext` (+ `cigar`), `kswv` (mate-rescue Smith-Waterman jobs), `bsw` (the banded-SW kernel on 2 M
 distinct extension jobs) and `e2e` (BASELINE.json's second metric: paired-end `mem -7` through the reference aligner
 with the HIP backend bound in, next to the unmodified reference on the same host cores, SAM md5 compared).
 
@@ -24,9 +28,11 @@ per step, default 10,000,000), MEME_BENCH_BITS (P-RMI leaves = 2^bits, default: 
 MEME_BENCH_LANES (lanes per read in the SA-search kernel), MEME_BENCH_CPU (reference | port | 0; default: the
 compiled reference, timed in this run), MEME_BENCH_CPU_READS (sample size), MEME_BENCH_CACHE (0 disables the /dev/shm caches),
 MEME_BENCH_SA (device | host: where the suffix array is built), MEME_BENCH_CHAIN / MEME_BENCH_BSW / MEME_BENCH_E2E (0 disables the leg), MEME_BENCH_E2E_PAIRS (read pairs of the end-to-end leg, default
-10,000,000 = BASELINE configs[2]), MEME_BENCH_C4 / MEME_BENCH_C4_E2E (0 disables the configs[4]-class leg / its end-to-end part), MEME_BENCH_BUDGET_S (wall budget in seconds after which optional legs are skipped, default 1500).
+10,000,000 = BASELINE configs[2]), MEME_BENCH_C4 / MEME_BENCH_C4_E2E (0 disables the configs[4]-class leg / its end-to-end part), MEME_BENCH_BUDGET_S (wall budget in seconds after which optional legs are skipped, default 540:
+a --full run ends within ten minutes; 1500 runs every leg, about 13 minutes on one MI355X).
 """
 import argparse
+import ctypes as C
 import json
 import os
 import shutil
@@ -34,6 +40,7 @@ import subprocess
 import sys
 import tempfile
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -70,6 +77,125 @@ def host_cpu_quota():
 
 def log(msg):
     print("[bench r%s +%.0fs] %s" % (os.environ.get("RANK", "0"), time.time() - T_START, msg), file=sys.stderr, flush=True)
+
+
+HOST_WORKERS = min(16, os.cpu_count() or 1)
+
+
+def uniform_below(rng, shape, p, pool, parts=HOST_WORKERS):
+    """rng.random(shape) < p with the doubles drawn in `parts` slices side by side.  PCG64 spends one 64-bit output per double, so slice k
+    starts where a jump of k slices lands; afterwards the generator stands where the single call would have left it (the jump clears the
+    buffered 32-bit half, which the call itself leaves alone)."""
+    bg = rng.bit_generator
+    assert isinstance(bg, np.random.PCG64)
+    total = int(np.prod(shape))
+    st = bg.state
+    out = np.empty(total, dtype=bool)
+    step = -(-total // parts)
+
+    def part(k):
+        b = np.random.PCG64()
+        b.state = st
+        b.advance(k * step)
+        out[k * step:(k + 1) * step] = np.random.Generator(b).random(max(0, min(step, total - k * step))) < p
+    list(pool.map(part, range(parts)))
+    bg.advance(total)
+    st2 = bg.state
+    st2["has_uint32"], st2["uinteger"] = st["has_uint32"], st["uinteger"]
+    bg.state = st2
+    return out.reshape(shape)
+
+
+def sample_reads(genome, n_reads, read_len, seed, sub_rate=0.01, n_frac=0.02, indel_frac=0.15, chunk=1 << 20):
+    """workload.make_reads_fast, byte for byte (tests/test_bench_sampler.py): the same draws from the same generator in the same order,
+    with the gathers and edits between them done by a thread pool, chunk after chunk, while the next chunk is drawn."""
+    rng = np.random.default_rng(seed)
+    out = np.empty((n_reads, read_len), dtype=np.uint8)
+    span = read_len + 4
+    ar = np.arange(read_len)
+    win = np.lib.stride_tricks.sliding_window_view(genome, span)
+
+    def edit(s, pos, sub, shift, has, col, dl, rcm, wn, wcol):
+        frag = np.where(sub, (win[pos] + shift) & 3, win[pos]).astype(np.uint8)
+        # deletion of 1..3 bases at a random column for a subset: shift the tail left
+        idx = ar[None, :] + np.where((ar[None, :] >= col[:, None]) & has[:, None], dl[:, None], 0)
+        reads = np.take_along_axis(frag, idx, axis=1)
+        reads[rcm] = 3 - reads[rcm][:, ::-1]
+        reads[wn, wcol] = 4
+        out[s:s + reads.shape[0]] = reads
+
+    with ThreadPoolExecutor(HOST_WORKERS) as ex, ThreadPoolExecutor(HOST_WORKERS) as draw:
+        jobs = []
+        for s in range(0, n_reads, chunk):
+            m = min(chunk, n_reads - s)
+            pos = rng.integers(0, genome.shape[0] - span, size=m)
+            sub = uniform_below(rng, (m, span), sub_rate, draw)
+            shift = rng.integers(1, 4, size=(m, span), dtype=np.uint8)
+            has = rng.random(m) < indel_frac
+            col = rng.integers(10, read_len - 10, size=m)
+            dl = rng.integers(1, 4, size=m)
+            rcm = rng.random(m) < 0.5
+            wn = np.nonzero(rng.random(m) < n_frac)[0]
+            wcol = rng.integers(0, read_len, size=wn.size)
+            jobs.append(ex.submit(edit, s, pos, sub, shift, has, col, dl, rcm, wn, wcol))
+        for j in jobs:
+            j.result()
+    return out
+
+
+DUMP_BLOCKS, DUMP_BLOCK_READS, DUMP_SEED = 32, 1024, 2024
+
+
+def dump_outputs(d, ctx, res, nreads):
+    """--dump-outputs: what the timed path handed its caller in the last step (meme_seed_batch_device: SMEMs and their hit lists in HBM) for a
+    fixed, seeded sample of DUMP_BLOCKS runs of DUMP_BLOCK_READS consecutive reads, as float64 .npy files (every value is an integer below 2^53).
+    A read's SMEMs are written in the reference harness's dump order (start ascending, end descending), each with its hits in that order:
+    the same content whatever order the kernels wrote it in.  About 20 MB at the default workload."""
+    ctx.sync()
+    cp = hipapi.lib().hipMemcpy                    # the HIP runtime the library itself runs on (found through its dependencies)
+    cp.restype, cp.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+
+    def d2h(ptr, first, count, dtype):
+        out = np.empty(count, dtype=dtype)
+        if count:
+            isz = np.dtype(dtype).itemsize
+            rc = cp(out.ctypes.data, ptr + first * isz, count * isz, 2)          # hipMemcpyDeviceToHost
+            if rc != 0:
+                raise RuntimeError("hipMemcpy of the step's outputs failed (%d)" % rc)
+        return out
+    so = d2h(res.d_smem_off, 0, nreads + 1, np.int64)
+    ho = d2h(res.d_hit_off, 0, nreads + 1, np.int64)
+    if not (so[0] == 0 and so[-1] == res.total_smems and ho[0] == 0 and ho[-1] == res.total_hits and (np.diff(so) >= 0).all() and (np.diff(ho) >= 0).all()):
+        raise RuntimeError("the step's offset arrays do not match its totals")
+    blk = min(DUMP_BLOCK_READS, nreads)
+    nb = min(DUMP_BLOCKS, nreads // blk)
+    starts = np.sort(np.random.default_rng(DUMP_SEED).choice(nreads // blk, size=nb, replace=False)) * blk
+    rids, smems, hits, hit_base = [], [], [], []
+    nh = 0
+    for r0 in starts:
+        r1 = r0 + blk
+        sm = d2h(res.d_smems, int(so[r0]), int(so[r1] - so[r0]), hipapi.MEM_TL)
+        h = d2h(res.d_hits, int(ho[r0]), int(ho[r1] - ho[r0]), np.uint64)
+        rid = np.repeat(np.arange(r0, r1, dtype=np.int64), np.diff(so[r0:r1 + 1]))
+        if ((sm["hitbeg"] < 0) | (sm["hitcount"] < 0) | (sm["hitbeg"].astype(np.int64) + sm["hitcount"] > (ho[rid + 1] - ho[rid]))).any():
+            raise RuntimeError("an SMEM's hit list lies outside its read's hits")
+        rids.append(rid)
+        smems.append(sm)
+        hits.append(h)
+        hit_base.append(ho[rid] - ho[r0] + nh)
+        nh += h.shape[0]
+    rid, sm, h = np.concatenate(rids), np.concatenate(smems), np.concatenate(hits)
+    rid, start, end, hitcount, hits_c = _canon_seeds(rid, sm["start"], sm["end"], sm["hitbeg"].astype(np.int64), sm["hitcount"].astype(np.int64), h,
+                                                     np.concatenate(hit_base))
+    cache = sm["cache_refpos"][np.lexsort((-sm["end"].astype(np.int64), sm["start"].astype(np.int64), np.concatenate(rids)))]
+    sampled = (starts[:, None] + np.arange(blk)[None, :]).reshape(-1)
+    os.makedirs(d, exist_ok=True)
+    arrays = {"seed_reads": sampled, "seed_smem_count": np.diff(so)[sampled], "seed_hit_count": np.diff(ho)[sampled],
+              "seed_smems": np.stack([rid, start, end, hitcount, cache]).T, "seed_hits": hits_c,
+              "seed_totals": np.array([res.total_smems, res.total_hits, res.searches])}
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+    log("outputs of the last step (%d of its reads: %d SMEMs, %d hits) written to %s" % (sampled.shape[0], rid.shape[0], hits_c.shape[0], d))
 
 
 def fastq_bytes(reads: np.ndarray) -> np.ndarray:
@@ -657,7 +783,7 @@ def _live_pmc_traffic(steps, rfile, expect):
             out[key + "_kernels"] = {x[0][:48]: [x[1] / steps, x[2]] for x in stage}          # per launch, dispatches in the pass
             try:                                       # the pass's own bench line: the work it did must be the parent's (same reads, same index)
                 cl = json.loads(r.stdout.decode(errors="replace").strip().splitlines()[-1])
-                out[key + "_pass_work"] = {k: cl["config"].get(k) for k in ("smems_per_read", "hits_per_read", "searches_per_read")} | {"stage_ms": cl["roofline"].get("kernel_ms")}
+                out[key + "_pass_work"] = {k: cl["config"].get(k) for k in ("smems_per_read", "hits_per_read", "searches_per_read")} | {"stage_ms": cl["config"].get("search_stage_ms")}
             except Exception:
                 pass
             pw = out.get(key + "_pass_work")
@@ -940,6 +1066,7 @@ def self_launch(a):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(a.gpus), "--steps", str(a.steps), "--warmup", str(a.warmup)]
+    cmd += (["--full"] if a.full else []) + (["--dump-outputs", a.dump_outputs] if a.dump_outputs else [])
     log("spawning %d ranks: %s" % (a.gpus, " ".join(cmd[1:])))
     return subprocess.run(cmd, env=env).returncode
 
@@ -949,7 +1076,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of what the last step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity check, roofline, CPU baselines, the other legs and the counter passes (off: the headline only)")
     a = ap.parse_args()
+    if a.dump_outputs:
+        a.dump_outputs = os.path.abspath(a.dump_outputs)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1011,9 +1144,15 @@ def main():
     meta = torch.zeros(4, dtype=torch.int64, device=dev)
     fwd = text = sa = l1 = l2 = pre = None
     ctx = hipapi.Context(local)
+    rf = os.environ.get("MEME_BENCH_READS_FILE")          # (the counter passes re-execute this file: they take the parent's batch instead of sampling it again)
+    reads_job = sampler = None
     if rank == 0:
         t0 = time.time()
         fwd = synth.make_genome(l_pac, seed=11)
+        if not (rf and os.path.exists(rf) and world == 1):
+            # the batch is sampled on host threads while the GPU builds the index
+            sampler = ThreadPoolExecutor(1)
+            reads_job = sampler.submit(sample_reads, fwd, nreads, READ_LEN, 1000 + rank)
         cache = None
         # (only the host build is worth caching: the device build is faster than reading 62 GB back from /dev/shm)
         if os.environ.get("MEME_BENCH_CACHE", "1") != "0" and os.path.isdir("/dev/shm") and os.environ.get("MEME_BENCH_SA", "device") != "device":
@@ -1034,7 +1173,8 @@ def main():
                 d_text0, d_s = hipapi.build_sa_device(ctx, text)
                 t_sa = time.time() - t0 - t_gen
                 d_pos50 = hipapi.pos5_from_sa_torch(ctx, d_s, n)
-                sa = d_s.cpu().numpy().view(np.uint64)
+                if a.full:                                 # (host copies: only the parity check, roofline and reference legs read them)
+                    sa = d_s.cpu().numpy().view(np.uint64)
                 del d_s
                 torch.cuda.empty_cache()
                 t1 = time.time()
@@ -1042,9 +1182,11 @@ def main():
                 use_bits = bits if bits > 0 else (28 if 8.0 * n + 8 > 8.0e9 else 26 if 8.0 * n + 8 > 1.0e9 else 24)   # build_rmis_dna.sh:68-77
                 d_l2_0, n_l2_0, d_l1_0, n_l1_0 = hipapi.train_prmi_device(ctx, d_ent0, n, use_bits)
                 t_train = time.time() - t1
-                l2 = d_l2_0.cpu().numpy().view(hostapi.RMI_DTYPE)
-                l1 = d_l1_0.cpu().numpy().view(hostapi.RMI_DTYPE)[:n_l1_0]
+                if a.full:
+                    l2 = d_l2_0.cpu().numpy().view(hostapi.RMI_DTYPE)
+                    l1 = d_l1_0.cpu().numpy().view(hostapi.RMI_DTYPE)[:n_l1_0]
                 pre = (d_text0, d_pos50, d_l2_0, d_l1_0, d_pac0, d_ent0)
+                meta[1], meta[2] = n_l2_0, n_l1_0
                 log("genome %.0f Mbp synthesised in %.1f s; on the device: suffix array in %.1f s (incl. the upload of the text), "
                     "entries + P-RMI (2^%d leaves, %d partial) in %.1f s" % (l_pac / 1e6, t_gen, t_sa, use_bits, n_l1_0, t_train))
             else:
@@ -1069,7 +1211,9 @@ def main():
                             os.remove(cache + ext)
                         except OSError:
                             pass
-        meta[0], meta[1], meta[2] = n, l2.shape[0], l1.shape[0]
+        meta[0] = n
+        if l2 is not None:
+            meta[1], meta[2] = l2.shape[0], l1.shape[0]
     if world > 1:
         dist.broadcast(meta, 0)
     n_l2, n_l1 = int(meta[1]), int(meta[2])
@@ -1131,21 +1275,23 @@ def main():
     genome = fwd if rank == 0 else genome_t.cpu().numpy()
     del genome_t
     t0 = time.time()
-    rf = os.environ.get("MEME_BENCH_READS_FILE")          # (the counter passes re-execute this file: they take the parent's batch instead of sampling it again)
-    if rf and os.path.exists(rf) and world == 1:
+    if reads_job is not None:
+        reads = reads_job.result()
+        sampler.shutdown()
+    elif rf and os.path.exists(rf) and world == 1:
         reads = np.load(rf)
         assert reads.shape == (nreads, READ_LEN)
     else:
-        reads = workload.make_reads_fast(genome, nreads, READ_LEN, seed=1000 + rank)
+        reads = sample_reads(genome, nreads, READ_LEN, seed=1000 + rank)
     d_reads = torch.from_numpy(reads.reshape(-1)).to(dev)
     d_off = torch.arange(0, (nreads + 1) * READ_LEN, READ_LEN, dtype=torch.int64, device=dev)
     torch.cuda.synchronize()
-    log("%d reads sampled and uploaded in %.1f s" % (nreads, time.time() - t0))
+    log("%d reads sampled and uploaded; %.1f s spent waiting for them" % (nreads, time.time() - t0))
     # the batch as sampled, for the counter passes at the end of the run (they re-execute this file; sampling again was 18 s per pass)
     reads_file, reads_sum0 = None, int(reads.reshape(-1).view(np.uint64).sum(dtype=np.uint64)) if reads.size % 8 == 0 else None
     if os.environ.get("MEME_BENCH_KEEP_READS"):                  # (a probe: the batch as a file of its own)
         np.save(os.environ["MEME_BENCH_KEEP_READS"], reads)
-    if rank == 0 and world == 1 and not rf and os.environ.get("MEME_BENCH_PMC", "1") != "0" and os.environ.get("MEME_BENCH_PMC_READS_CACHE", "0") != "0" and os.path.isdir("/dev/shm") and shutil.which("rocprofv3"):
+    if a.full and rank == 0 and world == 1 and not rf and os.environ.get("MEME_BENCH_PMC", "1") != "0" and os.environ.get("MEME_BENCH_PMC_READS_CACHE", "0") != "0" and os.path.isdir("/dev/shm") and shutil.which("rocprofv3"):
         try:
             reads_file = os.path.join("/dev/shm", "meme_bench_reads_%d.npy" % os.getpid())
             np.save(reads_file, reads)
@@ -1213,29 +1359,8 @@ def main():
         k_ms = float(np.mean([k[0] for k in kernel_ms]))
         g_ms = float(np.mean([k[1] for k in kernel_ms]))
         rs_ms = float(np.mean([k[2] for k in kernel_ms]))
-        sample = reads[:20000]
-        bpr, per_read = algorithmic_bytes_per_read(text, sa, l1, l2, sample)
-        # parity at the benchmark's own size (index of n suffixes), by CONTENT: the GPU seeds the sample on its own and its
-        # full seed dump (every SMEM, every hit position, the harness's dump format) must equal the pinned oracle's
-        # (oracle/meme_oracle.c orc_seed_batch; the checker only -- nothing timed goes through it)
-        sys.path.insert(0, os.path.join(REPO, "tests"))
-        import oracle_py as O
-        # (round 4: 1 M reads instead of 20 000, in slices the oracle's fixed-capacity output arrays can hold; every SMEM and every hit
-        # position compared after the dump format's ordering -- SMEMs by (start asc, end desc), hits in suffix-array order)
-        ns = min(nreads, int(os.environ.get("MEME_BENCH_PARITY_READS", "600000")))
-        t_par = time.time()
-        sample_parity, o_idx = True, O.Index(text, sa)
-        SL = 50000
-        for p0 in range(0, ns, SL):
-            part = reads[p0:p0 + SL]
-            if not seeds_equal_oracle(ctx, O, o_idx, part, opt):
-                sample_parity = False
-                log("PARITY MISMATCH in reads %d..%d of the benchmark's batch: the GPU's seeds differ from the oracle's" % (p0, p0 + part.shape[0]))
-                break
-        log("parity: %d of the benchmark's reads against orc_seed_batch in %.1f s: %s" % (ns, time.time() - t_par, "identical" if sample_parity else "DIFFERENT"))
-        achieved = bpr * nreads / (k_ms * 1e-3) / 1e9
         out = {
-            "metric": "seeding_reads_per_sec", "value": (sum(per_rank) / dt) if sample_parity else None,
+            "metric": "seeding_reads_per_sec", "value": sum(per_rank) / dt,
             "unit": "reads/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64",
@@ -1249,37 +1374,66 @@ def main():
                        "smems_per_read": res.total_smems / nreads, "hits_per_read": res.total_hits / nreads,
                        "searches_per_read": res.searches / nreads,
                        "windows_per_search": windows / max(res.searches, 1),
-                       "sample_parity_with_oracle": bool(sample_parity),
-                       "sample_parity_check": "every SMEM and hit position of %d of the benchmark's reads vs orc_seed_batch" % ns},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0,
-                         "traffic": None, "kernel": "the SA-search stage: k_seed (rounds 1 and 3, re-seeding of repeated SMEMs) + k_reseed / _emit / _search / _resume "
-                                                    "(re-seeding of unique SMEMs on the plcp table); HIP events around the whole stage",
-                         "kernel_ms": k_ms, "of_which_reseed_kernels_ms": rs_ms, "gather_ms": g_ms,
-                         "algorithmic_bytes_per_read": bpr, "work_per_read": per_read},
+                       "search_stage_ms": k_ms, "of_which_reseed_kernels_ms": rs_ms, "pack_gather_ms": g_ms},
         }
-        # HBM traffic per launch from the committed PMC passes of this very configuration (rocprofv3 counters cannot be
-        # collected inside a timed run): FETCH_SIZE doubled as the gfx950 guide prescribes (128-byte line fills are
-        # tallied at 64 B; cross-checked against TCC_MISS x 128 B) + WRITE_SIZE
-        pmc = None
-        try:
-            pmc = json.load(open(os.path.join(REPO, "profiles", "pmc_named.json")))
-            c = pmc["config"]
-            if not (c["genome_bp"] == l_pac and c["reads_per_step"] == nreads and c["read_len"] == READ_LEN and
-                    c["rmi_leaves_log2"] == int(np.log2(n_l2))):
-                pmc = None
-        except (OSError, ValueError, KeyError):
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, ctx, res, nreads)
+        sample_parity = True
+        if a.full:                                   # the parity check, roofline and everything after it: --full only
+            sample = reads[:20000]
+            bpr, per_read = algorithmic_bytes_per_read(text, sa, l1, l2, sample)
+            # parity at the benchmark's own size (index of n suffixes), by CONTENT: the GPU seeds the sample on its own and its
+            # full seed dump (every SMEM, every hit position, the harness's dump format) must equal the pinned oracle's
+            # (oracle/meme_oracle.c orc_seed_batch; the checker only -- nothing timed goes through it)
+            sys.path.insert(0, os.path.join(REPO, "tests"))
+            import oracle_py as O
+            # (round 4: 1 M reads instead of 20 000, in slices the oracle's fixed-capacity output arrays can hold; every SMEM and every hit
+            # position compared after the dump format's ordering -- SMEMs by (start asc, end desc), hits in suffix-array order)
+            ns = min(nreads, int(os.environ.get("MEME_BENCH_PARITY_READS", "600000")))
+            t_par = time.time()
+            sample_parity, o_idx = True, O.Index(text, sa)
+            SL = 50000
+            for p0 in range(0, ns, SL):
+                part = reads[p0:p0 + SL]
+                if not seeds_equal_oracle(ctx, O, o_idx, part, opt):
+                    sample_parity = False
+                    log("PARITY MISMATCH in reads %d..%d of the benchmark's batch: the GPU's seeds differ from the oracle's" % (p0, p0 + part.shape[0]))
+                    break
+            log("parity: %d of the benchmark's reads against orc_seed_batch in %.1f s: %s" % (ns, time.time() - t_par, "identical" if sample_parity else "DIFFERENT"))
+            achieved = bpr * nreads / (k_ms * 1e-3) / 1e9
+            out["config"]["sample_parity_with_oracle"] = bool(sample_parity)
+            out["config"]["sample_parity_check"] = "every SMEM and hit position of %d of the benchmark's reads vs orc_seed_batch" % ns
+            if not sample_parity:
+                out["value"] = None
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0,
+                               "traffic": None, "kernel": "the SA-search stage: k_seed (rounds 1 and 3, re-seeding of repeated SMEMs) + k_reseed / _emit / _search / _resume "
+                                                          "(re-seeding of unique SMEMs on the plcp table); HIP events around the whole stage",
+                               "kernel_ms": k_ms, "of_which_reseed_kernels_ms": rs_ms, "gather_ms": g_ms,
+                               "algorithmic_bytes_per_read": bpr, "work_per_read": per_read}
+            # HBM traffic per launch from the committed PMC passes of this very configuration (rocprofv3 counters cannot be
+            # collected inside a timed run): FETCH_SIZE doubled as the gfx950 guide prescribes (128-byte line fills are
+            # tallied at 64 B; cross-checked against TCC_MISS x 128 B) + WRITE_SIZE
             pmc = None
-        if pmc:
             try:
-                out["roofline"]["traffic"] = (2 * pmc["fetch_size_kb_per_launch"] + pmc["write_size_kb_per_launch"]) * 1024.0
-                out["roofline"]["traffic_source"] = "committed PMC pass, not this run: " + pmc["source"]
-                out["roofline"]["l2_miss_lines_per_s"] = pmc["tcc_miss_lines_per_launch"] / (k_ms * 1e-3)
-                out["roofline"]["random_line_roofline_lines_per_s"] = 50e9     # scripts/microbench/gather_roofline.hip
-            except Exception as e:  # never lose the headline line over an annotation
-                log("pmc annotation skipped: %r" % (e,))
-        budget = float(os.environ.get("MEME_BENCH_BUDGET_S", "1500"))
+                pmc = json.load(open(os.path.join(REPO, "profiles", "pmc_named.json")))
+                c = pmc["config"]
+                if not (c["genome_bp"] == l_pac and c["reads_per_step"] == nreads and c["read_len"] == READ_LEN and
+                        c["rmi_leaves_log2"] == int(np.log2(n_l2))):
+                    pmc = None
+            except (OSError, ValueError, KeyError):
+                pmc = None
+            if pmc:
+                try:
+                    out["roofline"]["traffic"] = (2 * pmc["fetch_size_kb_per_launch"] + pmc["write_size_kb_per_launch"]) * 1024.0
+                    out["roofline"]["traffic_source"] = "committed PMC pass, not this run: " + pmc["source"]
+                    out["roofline"]["l2_miss_lines_per_s"] = pmc["tcc_miss_lines_per_launch"] / (k_ms * 1e-3)
+                    out["roofline"]["random_line_roofline_lines_per_s"] = 50e9     # scripts/microbench/gather_roofline.hip
+                except Exception as e:  # never lose the headline line over an annotation
+                    log("pmc annotation skipped: %r" % (e,))
+        budget = float(os.environ.get("MEME_BENCH_BUDGET_S", "540"))
         rd_prefix = rd_genome = None
-        single = True        # (rank 0 is alone from here on at every N: the other ranks have left after the timed region)
+        # (rank 0 is alone from here on at every N: the other ranks have left after the timed region; the legs below run with --full only)
+        single = a.full
         cores = min(256, os.cpu_count() or 1)
         refcache = RefCache(l_pac, bits)
         # ---- the reference's own file formats on disk, for the two legs that run compiled reference binaries ----------
@@ -1318,7 +1472,8 @@ def main():
             # gets (the boxes this was developed on: 256 threads visible, 16 by quota) -- every host-side figure of this line runs against that
             cpu["host_threads_visible"] = os.cpu_count() or 1
             cpu["host_cpu_quota"] = host_cpu_quota()
-        out["cpu_baseline"] = cpu
+        if single:
+            out["cpu_baseline"] = cpu
         if single and os.environ.get("MEME_BENCH_BSW", "1") != "0":
             try:
                 out["bsw"] = bsw_leg(ctx, dev, world)

@@ -15,10 +15,11 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_gpus_2_self_started_one_json_line():
     env = dict(os.environ, MEME_BENCH_MBP="64", MEME_BENCH_READS="200000", MEME_BENCH_CACHE="0", MEME_BENCH_E2E_PAIRS="20000",
-               MEME_BENCH_CPU_READS="20000", MEME_BENCH_BSW_PAIRS="100000")
+               MEME_BENCH_CPU_READS="20000", MEME_BENCH_BSW_PAIRS="100000", MEME_BENCH_BUDGET_S="1500")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"], capture_output=True, env=env,
+    # --full: the parity check and the reported extras asserted below
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], capture_output=True, env=env,
                        timeout=1500, cwd=REPO)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
