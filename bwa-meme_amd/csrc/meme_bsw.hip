@@ -713,9 +713,9 @@ int launch_cls(meme_ctx* ctx, BswArgs A, int qmax, i64 dev_cus) {
         // BandedPairWiseSW's 16-bit class takes sequences below 32768 bases (src/bandedSWA.h:47-86): rows in an HBM workspace
         if (qmax > 32768) { meme_set_error("query of %d bases: beyond the 32768 the reference's banded SW accepts", qmax); return MEME_E_ARG; }
         if (blocks > dev_cus * 2) blocks = dev_cus * 2;
-        int rc = meme_buf_reserve(ctx, ctx->bsw_ws, per_grp * GROUPS * (size_t)blocks);
+        int rc = meme_buf_reserve(ctx, ctx->bsw.ws, per_grp * GROUPS * (size_t)blocks);
         if (rc) return rc;
-        A.gws = (unsigned char*)ctx->bsw_ws.p;
+        A.gws = (unsigned char*)ctx->bsw.ws.p;
         lds = 0;
     }
     if (lds > 64 * 1024)
@@ -735,14 +735,14 @@ int launch_bsw(meme_ctx* ctx, meme_seqpair* d_pairs, const uint8_t* d_ref, const
     // counters (ints): [0..SORT_KEYS) histogram by query length, [SORT_KEYS..2*SORT_KEYS] exclusive offsets (+ total),
     // then the scatter cursors, the longest query of the pairs the lane kernel cannot take, and the kernels' tickets
     const size_t n_ints = 3 * (size_t)SORT_KEYS + 32;
-    if ((rc = meme_buf_reserve(ctx, ctx->counters, n_ints * sizeof(int)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->bsw_order, (size_t)npairs * sizeof(int)))) return rc;
-    int* hist = (int*)ctx->counters.p;
+    if ((rc = meme_buf_reserve(ctx, ctx->bsw.hist, n_ints * sizeof(int)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->bsw.order, (size_t)npairs * sizeof(int)))) return rc;
+    int* hist = (int*)ctx->bsw.hist.p;
     int* offs = hist + SORT_KEYS;
     int* cursor = offs + SORT_KEYS + 1;
     int* maxq = cursor + SORT_KEYS;
     unsigned int* tickets = (unsigned int*)(maxq + 1);
-    int* order = (int*)ctx->bsw_order.p;
+    int* order = (int*)ctx->bsw.order.p;
     const i64 dev_cus = ctx->n_cus;
     HIP_TRY(hipMemsetAsync(hist, 0, n_ints * sizeof(int), ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
@@ -879,19 +879,19 @@ extern "C" int meme_bsw_batch(meme_ctx* ctx, meme_seqpair* pairs, const uint8_t*
     }
     int rc;
     const double t1 = trace ? now() : 0;
-    if ((rc = meme_buf_reserve(ctx, ctx->pairs, (size_t)npairs * sizeof(meme_seqpair)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->refb, (size_t)ref_bytes + 16))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->qerb, (size_t)qer_bytes + 16))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->pairs.p, pairs, (size_t)npairs * sizeof(meme_seqpair), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->refb.p, ref_buf, (size_t)ref_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->qerb.p, qer_buf, (size_t)qer_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = meme_buf_reserve(ctx, ctx->bsw.pairs, (size_t)npairs * sizeof(meme_seqpair)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->bsw.refb, (size_t)ref_bytes + 16))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->bsw.qerb, (size_t)qer_bytes + 16))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->bsw.pairs.p, pairs, (size_t)npairs * sizeof(meme_seqpair), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->bsw.refb.p, ref_buf, (size_t)ref_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->bsw.qerb.p, qer_buf, (size_t)qer_bytes, hipMemcpyHostToDevice, ctx->stream));
     // one host synchronisation per call: the class ranges stay on the device (the host knows the longest query)
     const double t2 = trace ? now() : 0;
-    rc = launch_bsw(ctx, (meme_seqpair*)ctx->pairs.p, (const uint8_t*)ctx->refb.p, (const uint8_t*)ctx->qerb.p, npairs, w,
+    rc = launch_bsw(ctx, (meme_seqpair*)ctx->bsw.pairs.p, (const uint8_t*)ctx->bsw.refb.p, (const uint8_t*)ctx->bsw.qerb.p, npairs, w,
                     opt, maxq);
     if (rc) return rc;
     const double t3 = trace ? now() : 0;
-    HIP_TRY(hipMemcpyAsync(pairs, ctx->pairs.p, (size_t)npairs * sizeof(meme_seqpair), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(pairs, ctx->bsw.pairs.p, (size_t)npairs * sizeof(meme_seqpair), hipMemcpyDeviceToHost, ctx->stream));
     rc = finish_bsw(ctx);
     if (trace)
         fprintf(stderr, "[meme bsw] %d pairs, %.1f MB in: validate %.2f ms, reserve + H2D enqueue %.2f ms, launches %.2f ms, D2H + wait %.2f ms (GPU %.2f ms)\n",

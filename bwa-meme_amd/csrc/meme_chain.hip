@@ -1340,12 +1340,10 @@ __global__ void __launch_bounds__(256) k_chain_counts(const ReadHdr* __restrict_
     }
 }
 
-unsigned blocks_of(i64 items, int per) { i64 b = (items + per - 1) / per; const i64 cap = 256 * 64; return (unsigned)(b < cap ? (b < 1 ? 1 : b) : cap); }
-
 }  // namespace
 
-// Chains of the batch the ctx has just seeded, left in HBM: ctx->chain[5] = {chain_off[n+1], seed_off[n+1], nch[n+1], nsd[n+1], tree[n], fb[n]},
-// [6] = packed meme_chain, [7] = packed meme_chain_seed, [3] = frac_rep.  totals[0..1] = chains, seeds.
+// Chains of the batch the ctx has just seeded, left in HBM: ctx->chain.counts (ChainCounts), .chains = packed meme_chain, .seeds = packed
+// meme_chain_seed, .frac = frac_rep.  totals[0..1] = chains, seeds.
 //
 // Order of events: k_chain_route sends reads to the wavefront tiers by the number of hits they have to walk; then the lane-per-read tier
 // (everything else, main stream) and the three sizes of the LDS tier (> chain_light_hits, > 256, > 512 hits), each on a side stream of its
@@ -1380,55 +1378,43 @@ int make_set(meme_ctx* ctx, DevBuf& buf, const i64* d_list, const i64* d_woff, i
 }
 }  // namespace
 
-int meme_chain_run(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs, const meme_chain_opt* opt, i64* totals) {
-    const i64 n = ctx->last_seed_reads;
+int meme_chain_reserve(meme_ctx* ctx, i64 n) {
+    ChainWs& C = ctx->chain;
+    const size_t rows = (size_t)((n + 63) / 64 * 64);
     int rc;
-    for (int i = 0; i < n_contigs; ++i)            // bntann1_t: 64-bit offset, 32-bit length; ascending, inside the forward strand
-        if (contigs[i].len < 1 || contigs[i].offset < 0 || contigs[i].offset + contigs[i].len > opt->l_pac || (i > 0 && contigs[i].offset < contigs[i - 1].offset + contigs[i - 1].len)) {
-            meme_set_error("contig %d (offset %lld, length %d) is not a valid reference sequence of a %lld-base genome", i, (long long)contigs[i].offset, contigs[i].len,
-                           (long long)opt->l_pac);
-            return MEME_E_ARG;
-        }
+    if ((rc = meme_buf_reserve(ctx, C.ch1, rows * CHAIN_CAP * sizeof(DChain))) || (rc = meme_buf_reserve(ctx, C.sd1, rows * CHAIN_CAP * SEED_CAP * sizeof(DSeed))) ||
+        (rc = meme_buf_reserve(ctx, C.hdr, (size_t)n * sizeof(ReadHdr))) || (rc = meme_buf_reserve(ctx, C.frac, (size_t)n * sizeof(float))) ||
+        (rc = meme_buf_reserve(ctx, C.counts, ChainCounts(nullptr, n).bytes)) || (rc = meme_buf_reserve(ctx, C.lists, ChainLists(nullptr, n).bytes))) return rc;
+    return MEME_OK;
+}
+
+int meme_chain_run(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs, const meme_chain_opt* opt, i64* totals) {
+    const i64 n = ctx->batch.last_seed_reads;
+    ChainWs& C = ctx->chain;
+    int rc;
+    std::vector<unsigned char> tab;
+    ContigTab ct(nullptr, 0, true);
+    if ((rc = meme_stage_contigs(ctx, C.contigs, tab, contigs, n_contigs, opt->l_pac, true, "", &ct))) return rc;
     // however this function is left (the error returns below included), the kernels on the side streams have finished: a caller that
     // retries with a smaller batch or destroys the ctx must not race them
     struct SideGuard { meme_ctx* c; ~SideGuard() { for (auto st : c->stream_side) if (st) (void)hipStreamSynchronize(st); } } side_guard{ctx};
-    DevBuf* B = ctx->chain;     // 0 tier-1 chains, 1 tier-1 seeds, 2 headers, 3 frac, 4 contig table, 5 counts/offsets, 6 packed chains, 7 packed seeds,
-                                // 8 lists + work + offsets of the five wavefront launches + read classes, 9 .. 13 their scratch sets
-    if ((rc = meme_buf_reserve(ctx, B[0], (size_t)((n + 63) / 64 * 64) * CHAIN_CAP * sizeof(DChain)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, B[1], (size_t)((n + 63) / 64 * 64) * CHAIN_CAP * SEED_CAP * sizeof(DSeed)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, B[2], (size_t)n * sizeof(ReadHdr)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, B[3], (size_t)n * sizeof(float)))) return rc;
-    const size_t ctab = (size_t)n_contigs * (8 + 4 + 1) + 64;
-    if ((rc = meme_buf_reserve(ctx, B[4], ctab))) return rc;
-    const size_t cnt_bytes = ((size_t)(n + 1) * 8 * 4 + (size_t)n * 4 + (size_t)n + 64 + 15) / 16 * 16 + 64;   // (+ five counters at the end)
-    if ((rc = meme_buf_reserve(ctx, B[5], cnt_bytes))) return rc;
-    if ((rc = meme_buf_reserve(ctx, B[8], (size_t)(n + 1) * 8 * 15 + (size_t)n + 64))) return rc;
-    std::vector<unsigned char> tab(ctab, 0);
-    i64* t_off = (i64*)tab.data();
-    int* t_len = (int*)(tab.data() + (size_t)n_contigs * 8);
-    unsigned char* t_alt = tab.data() + (size_t)n_contigs * 12;
-    for (int i = 0; i < n_contigs; ++i) { t_off[i] = contigs[i].offset; t_len[i] = contigs[i].len; t_alt[i] = contigs[i].is_alt ? 1 : 0; }
-    HIP_TRY(hipMemcpyAsync(B[4].p, tab.data(), ctab, hipMemcpyHostToDevice, ctx->stream));
-    unsigned long long* d_cnt4 = (unsigned long long*)((unsigned char*)B[5].p + cnt_bytes - 64);
-    HIP_TRY(hipMemsetAsync(d_cnt4, 0, 64, ctx->stream));
+    if ((rc = meme_chain_reserve(ctx, n))) return rc;
+    const ChainCounts cc(C.counts.p, n);
+    HIP_TRY(hipMemsetAsync(cc.route, 0, 64, ctx->stream));
     ChainArgs A;
-    A.smems = (const meme_mem_tl*)ctx->smems.p; A.smem_off = (const i64*)ctx->smem_off.p;
-    A.hits = (const u64*)ctx->hits.p; A.hit_off = (const i64*)ctx->hit_off.p; A.read_off = (const i64*)ctx->read_off.p;
+    A.smems = (const meme_mem_tl*)ctx->batch.smems.p; A.smem_off = (const i64*)ctx->batch.smem_off.p;
+    A.hits = (const u64*)ctx->batch.hits.p; A.hit_off = (const i64*)ctx->batch.hit_off.p; A.read_off = (const i64*)ctx->batch.read_off.p;
     A.nreads = n;
-    A.contig_off = (const i64*)B[4].p; A.contig_len = (const int*)((unsigned char*)B[4].p + (size_t)n_contigs * 8);
-    A.contig_alt = (const unsigned char*)B[4].p + (size_t)n_contigs * 12; A.n_contigs = n_contigs;
+    A.contig_off = ct.off; A.contig_len = ct.len; A.contig_alt = ct.alt; A.n_contigs = n_contigs;
     A.o = *opt;
     A.hit_cap1 = (int)ctx->chain_lane_hits;
-    A.ch = (DChain*)B[0].p; A.sd = (DSeed*)B[1].p; A.hdr = (ReadHdr*)B[2].p; A.frac_rep = (float*)B[3].p;
+    A.ch = (DChain*)C.ch1.p; A.sd = (DSeed*)C.sd1.p; A.hdr = (ReadHdr*)C.hdr.p; A.frac_rep = (float*)C.frac.p;
     // lists: [k] list, work, offsets for k = 0 / 1 / 2 LDS tier of 256 / 512 / 1 024 chains (routed), 3 LDS tier of 256 chains (left by the
-    // lane tier), 4 B-tree tier; scratch set k + 1 in B[9 + k]
-    i64* L8 = (i64*)B[8].p;
-    i64 *d_list[5], *d_work[5], *d_woff[5];
-    for (int k = 0; k < 5; ++k) { d_list[k] = L8 + (size_t)(3 * k) * (size_t)(n + 1); d_work[k] = d_list[k] + (n + 1); d_woff[k] = d_work[k] + (n + 1); }
-    unsigned char* d_cls = (unsigned char*)(L8 + (size_t)15 * (size_t)(n + 1));
+    // lane tier), 4 B-tree tier; scratch set k + 1 in C.wave[k]
+    const ChainLists L(C.lists.p, n);
     const bool wave_tiers = ctx->chain_wave_tiers != 0;     // (0: tests drive everything the lane tier leaves through the B-tree tier)
-    A.cls = d_cls;
-    hipEvent_t* ev = ctx->ev_chain;
+    A.cls = L.cls;
+    Events<5>& ev = C.ev;
     for (int i = 0; i < 5; ++i) if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
     for (int i = 0; i < 3; ++i) {
         { const int src = meme_side_stream(ctx, i); if (src) return src; }     // (tuning "chain_side_priority": the routed tiers' streams above the lane tier's in the hardware queues)
@@ -1439,18 +1425,18 @@ int meme_chain_run(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs,
     // ---- route by work
     const i64 never = (i64)1 << 60;
     const i64 light = wave_tiers ? ctx->chain_light_hits : never, heavy = wave_tiers ? 256 : never, huge = wave_tiers ? 512 : never;
-    hipLaunchKernelGGL(k_chain_route, dim3(blocks_of(n, 256)), dim3(256), 0, ctx->stream, A.smems, A.smem_off, A.read_off, n, opt->max_occ, opt->min_seed_len, light, heavy, huge,
-                       d_cls, d_cnt4, d_list[0], d_work[0], d_list[1], d_work[1], d_list[2], d_work[2]);
+    hipLaunchKernelGGL(k_chain_route, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, A.smems, A.smem_off, A.read_off, n, opt->max_occ, opt->min_seed_len, light, heavy, huge,
+                       L.cls, cc.route, L.list[0], L.work[0], L.list[1], L.work[1], L.list[2], L.work[2]);
     unsigned long long h_cnt[5] = {0, 0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt4, 24, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(h_cnt, cc.route, 24, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));                           // (also: `tab` is a local)
     i64 nl[5] = {(i64)h_cnt[0], (i64)h_cnt[1], (i64)h_cnt[2], 0, 0}, tw[5] = {0, 0, 0, 0, 0};
     WaveArgs W[5];
     memset(W, 0, sizeof(W));
     bool used[5] = {false, false, false, false, false};
-    for (int k = 0; k < 3; ++k) if (nl[k] > 0) { if ((rc = meme_scan_exclusive(ctx, d_work[k], d_woff[k], nl[k]))) return rc; HIP_TRY(hipMemcpyAsync(&tw[k], d_woff[k] + nl[k], 8, hipMemcpyDeviceToHost, ctx->stream)); }
+    for (int k = 0; k < 3; ++k) if (nl[k] > 0) { if ((rc = meme_scan_exclusive(ctx, L.work[k], L.woff[k], nl[k]))) return rc; HIP_TRY(hipMemcpyAsync(&tw[k], L.woff[k] + nl[k], 8, hipMemcpyDeviceToHost, ctx->stream)); }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 3; ++k) if (nl[k] > 0) { if ((rc = make_set(ctx, B[9 + k], d_list[k], d_woff[k], nl[k], tw[k], 1 + k, false, &W[k]))) return rc; used[k] = true; }
+    for (int k = 0; k < 3; ++k) if (nl[k] > 0) { if ((rc = make_set(ctx, C.wave[k], L.list[k], L.woff[k], nl[k], tw[k], 1 + k, false, &W[k]))) return rc; used[k] = true; }
     HIP_TRY(hipEventRecord(ctx->ev_aux, ctx->stream));
     // ---- four launches at once (the longest-running first)
     for (int k = 2; k >= 0; --k) {
@@ -1464,15 +1450,15 @@ int meme_chain_run(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs,
     hipLaunchKernelGGL((k_chain<CHAIN_CAP, SEED_CAP>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, A);
     HIP_TRY(hipEventRecord(ev[1], ctx->stream));
     // ---- what the lane tier left: LDS tier of 256 chains (or, with that switched off, the B-tree tier)
-    hipLaunchKernelGGL(k_chain_redo, dim3(blocks_of(n, 256)), dim3(256), 0, ctx->stream, (const ReadHdr*)B[2].p, n, 1, (const unsigned char*)d_cls, d_cnt4 + 3, d_list[3], d_work[3]);   // (routed reads: their tiers may still be writing)
-    HIP_TRY(hipMemcpyAsync(&h_cnt[3], d_cnt4 + 3, 8, hipMemcpyDeviceToHost, ctx->stream));
+    hipLaunchKernelGGL(k_chain_redo, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, (const ReadHdr*)C.hdr.p, n, 1, (const unsigned char*)L.cls, cc.route + 3, L.list[3], L.work[3]);   // (routed reads: their tiers may still be writing)
+    HIP_TRY(hipMemcpyAsync(&h_cnt[3], cc.route + 3, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     nl[3] = (i64)h_cnt[3];
     if (nl[3] > 0) {
-        if ((rc = meme_scan_exclusive(ctx, d_work[3], d_woff[3], nl[3]))) return rc;
-        HIP_TRY(hipMemcpyAsync(&tw[3], d_woff[3] + nl[3], 8, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = meme_scan_exclusive(ctx, L.work[3], L.woff[3], nl[3]))) return rc;
+        HIP_TRY(hipMemcpyAsync(&tw[3], L.woff[3] + nl[3], 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if ((rc = make_set(ctx, B[12], d_list[3], d_woff[3], nl[3], tw[3], 4, !wave_tiers, &W[3]))) return rc;
+        if ((rc = make_set(ctx, C.wave[3], L.list[3], L.woff[3], nl[3], tw[3], 4, !wave_tiers, &W[3]))) return rc;
         used[3] = true;
         if (wave_tiers) hipLaunchKernelGGL((k_chain_lds<256>), dim3((unsigned)nl[3]), dim3(64), 0, ctx->stream, A, W[3]);
         else hipLaunchKernelGGL((k_chain_wave<288, 2048>), dim3((unsigned)nl[3]), dim3(64), 0, ctx->stream, A, W[3], (i64)0);
@@ -1480,39 +1466,33 @@ int meme_chain_run(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs,
     for (int k = 0; k < 3; ++k) if (nl[k] > 0) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_side[k], 0));
     HIP_TRY(hipEventRecord(ev[4], ctx->stream));
     // ---- the B-tree tier for what is left (fallback == 3)
-    hipLaunchKernelGGL(k_chain_redo, dim3(blocks_of(n, 256)), dim3(256), 0, ctx->stream, (const ReadHdr*)B[2].p, n, 3, (const unsigned char*)nullptr, d_cnt4 + 4, d_list[4], d_work[4]);
-    HIP_TRY(hipMemcpyAsync(&h_cnt[4], d_cnt4 + 4, 8, hipMemcpyDeviceToHost, ctx->stream));
+    hipLaunchKernelGGL(k_chain_redo, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, (const ReadHdr*)C.hdr.p, n, 3, (const unsigned char*)nullptr, cc.route + 4, L.list[4], L.work[4]);
+    HIP_TRY(hipMemcpyAsync(&h_cnt[4], cc.route + 4, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     nl[4] = (i64)h_cnt[4];
     if (nl[4] > 0) {
-        if ((rc = meme_scan_exclusive(ctx, d_work[4], d_woff[4], nl[4]))) return rc;
-        HIP_TRY(hipMemcpyAsync(&tw[4], d_woff[4] + nl[4], 8, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = meme_scan_exclusive(ctx, L.work[4], L.woff[4], nl[4]))) return rc;
+        HIP_TRY(hipMemcpyAsync(&tw[4], L.woff[4] + nl[4], 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if ((rc = make_set(ctx, B[13], d_list[4], d_woff[4], nl[4], tw[4], 5, true, &W[4]))) return rc;
+        if ((rc = make_set(ctx, C.wave[4], L.list[4], L.woff[4], nl[4], tw[4], 5, true, &W[4]))) return rc;
         used[4] = true;
         hipLaunchKernelGGL((k_chain_wave<288, 2048>), dim3((unsigned)nl[4]), dim3(64), 0, ctx->stream, A, W[4], (i64)0);
     }
     HIP_TRY(hipEventRecord(ev[2], ctx->stream));
-    i64* d_choff = (i64*)B[5].p;
-    i64* d_sdoff = d_choff + (n + 1);
-    i64* d_nch = d_sdoff + (n + 1);
-    i64* d_nsd = d_nch + (n + 1);
-    int* d_tree = (int*)(d_nsd + (n + 1));
-    unsigned char* d_fb = (unsigned char*)(d_tree + n);
-    hipLaunchKernelGGL(k_chain_counts, dim3(blocks_of(n, 256)), dim3(256), 0, ctx->stream, (const ReadHdr*)B[2].p, n, d_nch, d_nsd, d_tree, d_fb);
-    if ((rc = meme_scan_exclusive(ctx, d_nch, d_choff, n))) return rc;
+    hipLaunchKernelGGL(k_chain_counts, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, (const ReadHdr*)C.hdr.p, n, cc.nch, cc.nsd, cc.tree, cc.fb);
+    if ((rc = meme_scan_exclusive(ctx, cc.nch, cc.chain_off, n))) return rc;
     i64 tot[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(&tot[0], d_choff + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = meme_scan_exclusive(ctx, d_nsd, d_sdoff, n))) return rc;
-    HIP_TRY(hipMemcpyAsync(&tot[1], d_sdoff + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&tot[0], cc.chain_off + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = meme_scan_exclusive(ctx, cc.nsd, cc.seed_off, n))) return rc;
+    HIP_TRY(hipMemcpyAsync(&tot[1], cc.seed_off + n, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if ((rc = meme_buf_reserve(ctx, B[6], (size_t)(tot[0] + 1) * sizeof(meme_chain)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, B[7], (size_t)(tot[1] + 1) * sizeof(meme_chain_seed)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, C.chains, (size_t)(tot[0] + 1) * sizeof(meme_chain)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, C.seeds, (size_t)(tot[1] + 1) * sizeof(meme_chain_seed)))) return rc;
     PackSets PS;
     memset(&PS, 0, sizeof(PS));
     for (int k = 0; k < 5; ++k) if (used[k]) { PS.woff[k + 1] = W[k].woff; PS.C[k + 1] = W[k].C; PS.S[k + 1] = W[k].S; PS.F[k + 1] = W[k].F; }
-    hipLaunchKernelGGL(k_chain_pack, dim3(blocks_of(n, 256)), dim3(256), 0, ctx->stream, (const DChain*)B[0].p, (const DSeed*)B[1].p, PS,
-                       (const ReadHdr*)B[2].p, (const i64*)d_choff, (const i64*)d_sdoff, n, (meme_chain*)B[6].p, (meme_chain_seed*)B[7].p);
+    hipLaunchKernelGGL(k_chain_pack, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, (const DChain*)C.ch1.p, (const DSeed*)C.sd1.p, PS,
+                       (const ReadHdr*)C.hdr.p, (const i64*)cc.chain_off, (const i64*)cc.seed_off, n, (meme_chain*)C.chains.p, (meme_chain_seed*)C.seeds.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev[3], ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1548,33 +1528,29 @@ extern "C" int meme_chain_last_batch_host(meme_ctx* ctx, const meme_contig* cont
     if (opt->max_occ < 1 || opt->l_pac < 1) { meme_set_error("meme_chain_last_batch_host: bad options"); return MEME_E_ARG; }
     HIP_TRY(hipSetDevice(ctx->device));
     memset(out, 0, sizeof(*out));
-    const i64 n = ctx->last_seed_reads;
-    if (n <= 0 || !ctx->smem_off.p || !ctx->read_off.p) { meme_set_error("meme_chain_last_batch_host: no seeded batch on this ctx"); return MEME_E_STATE; }
+    const i64 n = ctx->batch.last_seed_reads;
+    if (n <= 0 || !ctx->batch.smem_off.p || !ctx->batch.read_off.p) { meme_set_error("meme_chain_last_batch_host: no seeded batch on this ctx"); return MEME_E_STATE; }
     int rc;
     i64 tot[2];
     if ((rc = meme_chain_run(ctx, contigs, n_contigs, opt, tot))) return rc;
-    DevBuf* B = ctx->chain;
-    const i64* d_choff = (const i64*)B[5].p;
-    const i64* d_sdoff = d_choff + (n + 1);
-    const int* d_tree = (const int*)(d_sdoff + 3 * (n + 1));
-    const unsigned char* d_fb = (const unsigned char*)(d_tree + n);
-    meme_ctx::HostBuf* Hb = ctx->h_chain;   // 0 chain_off, 1 chains, 2 seed_off, 3 seeds, 4 tree sizes, 5 frac_rep, 6 fallback flags
-    if ((rc = meme_hostbuf_reserve(ctx, Hb[0], (size_t)(n + 1) * 8)) || (rc = meme_hostbuf_reserve(ctx, Hb[1], (size_t)(tot[0] + 1) * sizeof(meme_chain))) ||
-        (rc = meme_hostbuf_reserve(ctx, Hb[2], (size_t)(n + 1) * 8)) || (rc = meme_hostbuf_reserve(ctx, Hb[3], (size_t)(tot[1] + 1) * sizeof(meme_chain_seed))) ||
-        (rc = meme_hostbuf_reserve(ctx, Hb[4], (size_t)n * 4)) || (rc = meme_hostbuf_reserve(ctx, Hb[5], (size_t)n * 4)) ||
-        (rc = meme_hostbuf_reserve(ctx, Hb[6], (size_t)n))) return rc;
-    HIP_TRY(hipMemcpyAsync(Hb[0].p, d_choff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(Hb[2].p, d_sdoff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (tot[0]) HIP_TRY(hipMemcpyAsync(Hb[1].p, B[6].p, (size_t)tot[0] * sizeof(meme_chain), hipMemcpyDeviceToHost, ctx->stream));
-    if (tot[1]) HIP_TRY(hipMemcpyAsync(Hb[3].p, B[7].p, (size_t)tot[1] * sizeof(meme_chain_seed), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(Hb[4].p, d_tree, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(Hb[5].p, B[3].p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(Hb[6].p, d_fb, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    ChainWs& C = ctx->chain;
+    const ChainCounts cc(C.counts.p, n);
+    if ((rc = meme_hostbuf_reserve(ctx, C.h_chain_off, (size_t)(n + 1) * 8)) || (rc = meme_hostbuf_reserve(ctx, C.h_chains, (size_t)(tot[0] + 1) * sizeof(meme_chain))) ||
+        (rc = meme_hostbuf_reserve(ctx, C.h_seed_off, (size_t)(n + 1) * 8)) || (rc = meme_hostbuf_reserve(ctx, C.h_seeds, (size_t)(tot[1] + 1) * sizeof(meme_chain_seed))) ||
+        (rc = meme_hostbuf_reserve(ctx, C.h_tree, (size_t)n * 4)) || (rc = meme_hostbuf_reserve(ctx, C.h_frac, (size_t)n * 4)) ||
+        (rc = meme_hostbuf_reserve(ctx, C.h_fallback, (size_t)n))) return rc;
+    HIP_TRY(hipMemcpyAsync(C.h_chain_off.p, cc.chain_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(C.h_seed_off.p, cc.seed_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (tot[0]) HIP_TRY(hipMemcpyAsync(C.h_chains.p, C.chains.p, (size_t)tot[0] * sizeof(meme_chain), hipMemcpyDeviceToHost, ctx->stream));
+    if (tot[1]) HIP_TRY(hipMemcpyAsync(C.h_seeds.p, C.seeds.p, (size_t)tot[1] * sizeof(meme_chain_seed), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(C.h_tree.p, cc.tree, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(C.h_frac.p, C.frac.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(C.h_fallback.p, cc.fb, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     out->nreads = n;
-    out->chain_off = (const int64_t*)Hb[0].p; out->chains = (const meme_chain*)Hb[1].p;
-    out->seed_off = (const int64_t*)Hb[2].p; out->seeds = (const meme_chain_seed*)Hb[3].p;
-    out->tree_size = (const int32_t*)Hb[4].p; out->frac_rep = (const float*)Hb[5].p; out->fallback = (const uint8_t*)Hb[6].p;
+    out->chain_off = (const int64_t*)C.h_chain_off.p; out->chains = (const meme_chain*)C.h_chains.p;
+    out->seed_off = (const int64_t*)C.h_seed_off.p; out->seeds = (const meme_chain_seed*)C.h_seeds.p;
+    out->tree_size = (const int32_t*)C.h_tree.p; out->frac_rep = (const float*)C.h_frac.p; out->fallback = (const uint8_t*)C.h_fallback.p;
     out->total_chains = tot[0]; out->total_seeds = tot[1];
     i64 nfb = 0;
     for (i64 i = 0; i < n; ++i) nfb += out->fallback[i] ? 1 : 0;
@@ -1593,20 +1569,20 @@ extern "C" int meme_chain_batch_host(meme_ctx* ctx, const meme_mem_tl* smems, co
     const i64 ns = smem_off[nreads], nh = hit_off[nreads];
     if (smem_off[0] != 0 || hit_off[0] != 0 || ns < 0 || nh < 0 || (ns > 0 && !smems) || (nh > 0 && !hits)) { meme_set_error("meme_chain_batch_host: bad offsets"); return MEME_E_ARG; }
     int rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->smems, (size_t)(ns + 1) * sizeof(meme_mem_tl))) || (rc = meme_buf_reserve(ctx, ctx->hits, (size_t)(nh + 1) * 8)) ||
-        (rc = meme_buf_reserve(ctx, ctx->smem_off, (size_t)(nreads + 1) * 8)) || (rc = meme_buf_reserve(ctx, ctx->hit_off, (size_t)(nreads + 1) * 8)) ||
-        (rc = meme_buf_reserve(ctx, ctx->read_off, (size_t)(nreads + 1) * 8))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->batch.smems, (size_t)(ns + 1) * sizeof(meme_mem_tl))) || (rc = meme_buf_reserve(ctx, ctx->batch.hits, (size_t)(nh + 1) * 8)) ||
+        (rc = meme_buf_reserve(ctx, ctx->batch.smem_off, (size_t)(nreads + 1) * 8)) || (rc = meme_buf_reserve(ctx, ctx->batch.hit_off, (size_t)(nreads + 1) * 8)) ||
+        (rc = meme_buf_reserve(ctx, ctx->batch.read_off, (size_t)(nreads + 1) * 8))) return rc;
     std::vector<i64> roff((size_t)nreads + 1, 0);
     for (i64 i = 0; i < nreads; ++i) roff[(size_t)i + 1] = roff[(size_t)i] + read_len[i];
-    if (ns) HIP_TRY(hipMemcpyAsync(ctx->smems.p, smems, (size_t)ns * sizeof(meme_mem_tl), hipMemcpyHostToDevice, ctx->stream));
-    if (nh) HIP_TRY(hipMemcpyAsync(ctx->hits.p, hits, (size_t)nh * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->smem_off.p, smem_off, (size_t)(nreads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->hit_off.p, hit_off, (size_t)(nreads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->read_off.p, roff.data(), (size_t)(nreads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (ns) HIP_TRY(hipMemcpyAsync(ctx->batch.smems.p, smems, (size_t)ns * sizeof(meme_mem_tl), hipMemcpyHostToDevice, ctx->stream));
+    if (nh) HIP_TRY(hipMemcpyAsync(ctx->batch.hits.p, hits, (size_t)nh * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->batch.smem_off.p, smem_off, (size_t)(nreads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->batch.hit_off.p, hit_off, (size_t)(nreads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->batch.read_off.p, roff.data(), (size_t)(nreads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->last_seed_reads = nreads;
-    ctx->reads_resident = false;       // (the seeds are the caller's; whatever bases an earlier seeding call left here do not belong to them)
-    ctx->last_seed_max_len = 0;
-    for (i64 i = 0; i < nreads; ++i) ctx->last_seed_max_len = read_len[i] > ctx->last_seed_max_len ? read_len[i] : ctx->last_seed_max_len;
+    ctx->batch.last_seed_reads = nreads;
+    ctx->batch.reads_resident = false;       // (the seeds are the caller's; whatever bases an earlier seeding call left here do not belong to them)
+    ctx->batch.last_seed_max_len = 0;
+    for (i64 i = 0; i < nreads; ++i) ctx->batch.last_seed_max_len = read_len[i] > ctx->batch.last_seed_max_len ? read_len[i] : ctx->batch.last_seed_max_len;
     return meme_chain_last_batch_host(ctx, contigs, n_contigs, opt, out);
 }

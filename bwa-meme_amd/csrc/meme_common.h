@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -48,9 +49,113 @@ struct DevIndex {
     const uint8_t* plcp = nullptr;
 };
 
-struct DevBuf {   // growable device workspace
+// Workspaces free themselves (a ctx is destroyed with its device current and its streams idle) and cannot be copied.
+template <bool HOST> struct Buf {   // growable device workspace (meme_buf_reserve) / pinned host staging (meme_hostbuf_reserve)
     void* p = nullptr;
     size_t cap = 0;
+    Buf() = default;
+    Buf(const Buf&) = delete; Buf& operator=(const Buf&) = delete;
+    ~Buf() { if (p) (void)(HOST ? hipHostFree(p) : hipFree(p)); }
+};
+typedef Buf<false> DevBuf;
+typedef Buf<true> HostBuf;
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value && !std::is_copy_constructible<HostBuf>::value &&
+              !std::is_copy_assignable<HostBuf>::value, "a workspace owns its memory: a copy would free it twice");
+template <int N> struct Events {    // events of a stage, created on first use, destroyed with the stage
+    hipEvent_t e[N] = {};
+    Events() = default;
+    Events(const Events&) = delete; Events& operator=(const Events&) = delete;
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    hipEvent_t& operator[](int i) { return e[i]; }
+};
+
+// Packed layouts: typed arrays carved out of one allocation in order.  The same code gives the total bytes (base == nullptr) and the pointers.
+struct Carve {
+    unsigned char* base;
+    size_t bytes = 0;
+    explicit Carve(void* b) : base((unsigned char*)b) {}
+    template <class T> T* take(size_t count, size_t align = 1) { bytes = (bytes + align - 1) / align * align; T* q = base ? (T*)(base + bytes) : nullptr; bytes += count * sizeof(T); return q; }
+    i64* col(i64 n) { return take<i64>((size_t)n + 1); }   // one column of n + 1 values
+};
+struct ContigTab {     // chaining and mate rescue: offset[n], len[n], is_alt[n] (chaining only), 64 bytes of padding
+    i64* off; int* len; unsigned char* alt; size_t bytes;
+    ContigTab(void* base, i64 n, bool with_alt) { Carve c(base); off = c.take<i64>(n); len = c.take<int>(n); alt = c.take<unsigned char>((with_alt ? n : 0) + 64); bytes = c.bytes; }
+};
+struct ChainCounts {   // per read, then the reads each wavefront launch takes (5 counters)
+    i64 *chain_off, *seed_off, *nch, *nsd; int* tree; unsigned char* fb; unsigned long long* route; size_t bytes;
+    ChainCounts(void* base, i64 n) { Carve c(base); chain_off = c.col(n); seed_off = c.col(n); nch = c.col(n); nsd = c.col(n); tree = c.take<int>(n); fb = c.take<unsigned char>(n + 64);
+                                     route = c.take<unsigned long long>(8, 16); bytes = c.bytes; }
+};
+struct ChainLists {    // list, work and work offsets of the five wavefront launches, read classes
+    i64 *list[5], *work[5], *woff[5]; unsigned char* cls; size_t bytes;
+    ChainLists(void* base, i64 n) { Carve c(base); for (int k = 0; k < 5; ++k) { list[k] = c.col(n); work[k] = c.col(n); woff[k] = c.col(n); } cls = c.take<unsigned char>(n + 64); bytes = c.bytes; }
+};
+struct ExtCounts {     // jobs left / right and sequence bytes per read, their scans, seeds selected per round and its scan
+    i64 *cntL, *cntR, *cntB, *offL, *offR, *offB, *cntS, *offS; size_t bytes;
+    ExtCounts(void* base, i64 n) { Carve c(base); cntL = c.col(n); cntR = c.col(n); cntB = c.col(n); offL = c.col(n); offR = c.col(n); offB = c.col(n); cntS = c.col(n); offS = c.col(n); bytes = c.bytes; }
+};
+struct ExtRounds {     // extension in rounds: per-read state, reads still active, seeds selected
+    int4* state; uint8_t* act; uint8_t* sel; size_t bytes;
+    ExtRounds(void* base, i64 n, i64 seeds) { Carve c(base); state = c.take<int4>(n + 1); act = c.take<uint8_t>(n + 1); sel = c.take<uint8_t>(seeds + 64); bytes = c.bytes; }
+};
+struct GcigCols {      // per CIGAR job: sizes, scans, the DP list and its classes; then the first bad job
+    i64 *zsz, *csz, *zoff, *coff, *ncig, *ooff, *msz, *moff, *psz, *poff, *isdp, *dpoff, *dplist, *is16, *o16, *is32, *o32, *is64, *o64, *is128, *o128, *bad; size_t bytes;
+    GcigCols(void* base, i64 n) { Carve c(base); zsz = c.col(n); csz = c.col(n); zoff = c.col(n); coff = c.col(n); ncig = c.col(n); ooff = c.col(n); msz = c.col(n); moff = c.col(n);
+        psz = c.col(n); poff = c.col(n); isdp = c.col(n); dpoff = c.col(n); dplist = c.col(n); is16 = c.col(n); o16 = c.col(n); is32 = c.col(n); o32 = c.col(n); is64 = c.col(n);
+        o64 = c.col(n); is128 = c.col(n); o128 = c.col(n); bad = c.take<i64>(8); bytes = c.bytes; }
+};
+struct MateCounts {    // gar entries, jobs, window bases and query bases per read, and their scans
+    i64 *cntQ, *cntJ, *cntR, *cntY, *offQ, *offJ, *offR, *offY; size_t bytes;
+    MateCounts(void* base, i64 n) { Carve c(base); cntQ = c.col(n); cntJ = c.col(n); cntR = c.col(n); cntY = c.col(n); offQ = c.col(n); offJ = c.col(n); offR = c.col(n); offY = c.col(n); bytes = c.bytes; }
+};
+struct SamCols {       // per record slot: scratch bound, its scan, text length, its scan; then the first bad record
+    i64 *bound, *soff, *len, *toff, *bad; size_t bytes;
+    SamCols(void* base, i64 n) { Carve c(base); bound = c.col(n); soff = c.col(n); len = c.col(n); toff = c.col(n); bad = c.take<i64>(8); bytes = c.bytes; }
+};
+// ---- per-stage workspaces of a ctx -----------------------------------------------------------------
+// What a seeding call leaves on the ctx for the stages behind it.  Invariant: only the calls that set a new batch (the seeding calls, and
+// meme_chain_batch_host, which brings its seeds in place of one) reserve these buffers; chaining, extension, CIGAR, SAM and mate calls only
+// read them.  meme_matesw_batch_host(..., reads_of, ...) relies on this when it reads another ctx's batch.
+struct ResidentBatch {
+    DevBuf reads, read_off, packed, smems, hits, smem_off, hit_off;
+    i64 last_seed_reads = 0;           // reads of the batch whose seeds are in smems / hits (input of meme_chain_last_batch_host)
+    i64 last_seed_max_len = 0;         // longest read of that batch
+    bool reads_resident = false;       // reads holds the bases of that batch (false after meme_chain_batch_host: seeds brought by the caller)
+};
+enum { SEED_CTR_OVERFLOW = 2, SEED_CTR_BLK = 14, SEED_CTR_BLK_OUT = 15, SEED_CTRS = 16 };   // a seeding counter set (u64): reads left for the next tier, blocked-region cursors
+struct SeedWs {
+    DevBuf slots[3], ovf[2];           // SMEM slots of a tier; reads that overflow it (tier & 1)
+    DevBuf slot_cnt, slot_hits, slot_loc, counters, pend, blk;
+    HostBuf h_smems, h_hits, h_smem_off, h_hit_off;   // results of meme_seed_batch_host
+    unsigned long long* counter_set(int cset) { return (unsigned long long*)counters.p + SEED_CTRS * cset; }   // two sets: an overflow tier may run beside the re-seeding kernels
+};
+struct ChainWs {
+    DevBuf ch1, sd1, hdr, frac, contigs, counts, chains, seeds, lists;   // lane-tier chains / seeds, read headers, frac_rep, ContigTab, ChainCounts, packed chains / seeds, ChainLists
+    DevBuf wave[5];                                                       // scratch sets of the five wavefront launches
+    HostBuf h_chain_off, h_chains, h_seed_off, h_seeds, h_tree, h_frac, h_fallback;
+    Events<5> ev;
+    const i64* chain_off() const { return (const i64*)counts.p; }   // (ChainCounts)
+    const i64* seed_off(i64 n) const { return ChainCounts(counts.p, n).seed_off; }
+};
+enum { EXT_CTR_RETRY = 0, EXT_CTR_FLT_JOBS = 2, EXT_CTR_CENSUS = 8, EXT_CTR_HEAVY = 24, EXT_CTR_BYTES = 256 };   // ExtWs::counters (u64); the census takes 11
+struct ExtWs {
+    DevBuf rmax, regs, order, counts, pairs_l, pairs_r, retry, seq, counters;   // counts: ExtCounts; retry: two halves
+    DevBuf flt_sc, flt_jobs, flt_cnt, flt_seeds, flt_score, flt_hsp;           // the seed filter's: scores, jobs, counts + new seed offsets, kept seeds, their scores, thresholds
+    DevBuf live_cnt, live_regs, rounds, heavy;                                 // surviving records (counts + scan, packed), ExtRounds, the heavy reads
+    HostBuf h_reg_off, h_regs; Events<2> ev;
+};
+struct BswWs { DevBuf pairs, refb, qerb, order, ws, hist; };   // hist: histogram, offsets, cursors, longest query and tickets of the query-length sort
+struct GcigWs {        // cols: GcigCols; cig: CIGAR scratch, ops: packed; nm: nm + mdlen
+    DevBuf jobs, cols, z, cig, res, ops, md, nm, md_packed, cjobs, cres; HostBuf h_res, h_ops, h_md; Events<2> ev;
+};
+struct KswvWs {        // mate rescue poses into jobs, ref and qer; k_kswv reads them
+    DevBuf jobs, order, ref, qer, res, rowmax, rm_off; HostBuf h_res; Events<2> ev;
+};
+struct MateWs {        // contigs: ContigTab; counts: MateCounts; batch_off: gar and job offsets of the worker batches
+    DevBuf regs, reg_off, contigs, counts, gar, aux, batch_off; HostBuf h_gar, h_batch_off, h_jobs;
+};
+struct SamWs {         // cols: SamCols; contigs: contig name offsets + names + read group
+    DevBuf names, name_off, quals, recs, blob, cols, scratch, text, contigs; HostBuf h_text_off, h_text; Events<2> ev;
 };
 
 struct meme_ctx {
@@ -61,14 +166,10 @@ struct meme_ctx {
     bool owns_index = false;
     std::vector<std::pair<void*, size_t>> owned;   // device allocations of the index (pointer, bytes)
     void* plcp_aux = nullptr;                      // the plcp table of an attached index (meme_index_attach: the arrays are the caller's, this is ours)
-    // workspaces
-    DevBuf reads, read_off, slots[3], ovf[2], slot_cnt, slot_hits, slot_loc, smem_off, hit_off, smems, hits,
-           scan_tmp, counters, pend, blk, pairs, refb, qerb, packed, bsw_order, bsw_ws, chain[14], ext[19], gcig[11], kswv[7], sam[9], mate[8];
-    // pinned host staging owned by the ctx (results of meme_seed_batch_host, inputs of meme_bsw_batch)
-    struct HostBuf { void* p = nullptr; size_t cap = 0; } h_smems, h_hits, h_smem_off, h_hit_off, h_misc, h_chain[7], h_ext[2], h_gcig[3], h_kswv, h_sam[2], h_mate[4];
-    i64 last_seed_max_len = 0;         // longest read of that batch
-    i64 last_seed_reads = 0;           // reads of the batch whose seeds are in smems / hits (input of meme_chain_last_batch_host)
-    bool reads_resident = false;       // ctx->reads holds the bases of that batch (false after meme_chain_batch_host: seeds brought by the caller)
+    // workspaces (scan_tmp: tiles of the prefix sums, meme_scan_exclusive and the seeding gather)
+    ResidentBatch batch;
+    DevBuf scan_tmp;
+    SeedWs seed; ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam;
     // tuning
     i64 seed_blocks = 0;               // 0 = auto
     i64 smem_cap = 128;                // per-read SMEM slots in the search kernel's scratch (tier 0; 3 KB per read.  With 64 a handful of
@@ -96,11 +197,6 @@ struct meme_ctx {
                                        // lanes-per-pair kernel (latency: a lone pair takes ~6 ms on one lane, ~0.3 ms on 64)
     // timings
     hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_chain[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_ext[2] = {nullptr, nullptr};
-    hipEvent_t ev_gcig[2] = {nullptr, nullptr};
-    hipEvent_t ev_kswv[2] = {nullptr, nullptr};
-    hipEvent_t ev_sam[2] = {nullptr, nullptr};
     i64 sam_text_reads = 0;            // reads of the batch whose names / qualities meme_sam_stage_text staged (0: none)
     bool sam_has_quals = false;
     hipStream_t stream_side[3] = {nullptr, nullptr, nullptr};   // the routed chaining tiers run beside the lane-per-read tier
@@ -110,6 +206,10 @@ struct meme_ctx {
     hipEvent_t ev_emit[2] = {nullptr, nullptr};
     i64 chain_reads = 0, chain_tier2_reads = 0, chain_tier3_reads = 0;   // of the last meme_chain_run(): reads chained, of which by the wavefront-per-read tier
     meme_timings tm = {};
+    ~meme_ctx() {                      // the ctx's own events and streams; the stages release theirs, every workspace frees itself
+        for (hipEvent_t e : {ev[0], ev[1], ev[2], ev[3], ev[4], ev[5], ev[6], ev[7], ev_side[0], ev_side[1], ev_side[2], ev_aux, ev_emit[0], ev_emit[1]}) if (e) (void)hipEventDestroy(e);
+        for (hipStream_t st : {stream_side[0], stream_side[1], stream_side[2], stream_emit, stream}) if (st) (void)hipStreamDestroy(st);
+    }
 };
 
 void meme_set_error(const char* fmt, ...);
@@ -117,7 +217,13 @@ int meme_buf_reserve(meme_ctx* ctx, DevBuf& b, size_t bytes);
 // side stream i of the ctx (the routed chaining tiers, the early overflow tier of seeding), created on first use -- ONE place, so that the tuning
 // "chain_side_priority" applies to all three whichever stage touches a stream first (advisor, round 5)
 int meme_side_stream(meme_ctx* ctx, int i);
-int meme_hostbuf_reserve(meme_ctx* ctx, meme_ctx::HostBuf& b, size_t bytes);
+int meme_hostbuf_reserve(meme_ctx* ctx, HostBuf& b, size_t bytes);
+// workgroups of a grid-stride launch over `items`, `per` to a workgroup: at least one, at most `cap` (256 x 64: 64 per CU of a 256-CU device)
+inline unsigned grid_blocks(i64 items, int per, i64 cap = 256 * 64) { i64 b = (items + per - 1) / per; return (unsigned)(b < cap ? (b < 1 ? 1 : b) : cap); }
+// the contigs checked (ascending, inside the forward strand of an l_pac-base genome; the error message starts with `prefix`) and staged into `buf` as a
+// ContigTab through `host`, which the caller keeps until its stream has passed the copy
+int meme_stage_contigs(meme_ctx* ctx, DevBuf& buf, std::vector<unsigned char>& host, const meme_contig* contigs, int32_t n_contigs, i64 l_pac, bool with_alt,
+                       const char* prefix, ContigTab* out);
 // exclusive prefix sum of n 64-bit counts into out[0..n] (out[n] = total), asynchronous on ctx->stream (meme_scan.hip)
 int meme_scan_exclusive(meme_ctx* ctx, const i64* d_in, i64* d_out, i64 n);
 // the banded-SW kernels on device-resident pairs, no host synchronisation (meme_bsw.hip); host_maxq = an upper bound of the query lengths or -1
@@ -128,10 +234,12 @@ int meme_bsw_launch(meme_ctx* ctx, meme_seqpair* d_pairs, const uint8_t* d_ref, 
 constexpr int MEME_SEEDSW_MAX = 200;    // MEM_SHORT_LEN, src/bwamem.cpp:250: windows are shorter
 struct meme_seedsw_job { i64 rb; i64 qoff; int seed; short tlen, qlen; };
 int meme_seedsw_launch(meme_ctx* ctx, const meme_seedsw_job* d_jobs, const unsigned long long* d_njobs, i64 max_jobs, int* d_sc, const meme_ext_opt* o);
-// the mate-rescue kernels on jobs whose sequences are already in ctx->kswv[2] / [3] and whose records are in ctx->kswv[0] (meme_kswv.hip; the jobs also on the host,
+// the mate-rescue kernels on jobs whose sequences are already in ctx->kswv.ref / qer and whose records are in ctx->kswv.jobs (meme_kswv.hip; the jobs also on the host,
 // for the sort into LDS classes); staged = false: meme_kswv_batch_host's own path (sequences and jobs come from the host)
 int meme_kswv_run(meme_ctx* ctx, const meme_kswv_job* jobs, int64_t njobs, const uint8_t* ref, int64_t ref_bytes, const uint8_t* qer, int64_t qer_bytes, const meme_bsw_opt* opt,
                   bool staged, meme_kswv_host_result* out);
+// the chaining workspace that depends on the read count alone (meme_chain.hip)
+int meme_chain_reserve(meme_ctx* ctx, i64 n);
 // chains of the batch just seeded, left in HBM (meme_chain.hip); totals[0..1] = chains, chained seeds
 int meme_chain_run(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs, const meme_chain_opt* opt, i64* totals);
 

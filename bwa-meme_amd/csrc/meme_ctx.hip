@@ -46,7 +46,7 @@ int meme_side_stream(meme_ctx* ctx, int i) {
     return MEME_OK;
 }
 
-int meme_hostbuf_reserve(meme_ctx* ctx, meme_ctx::HostBuf& b, size_t bytes) {
+int meme_hostbuf_reserve(meme_ctx* ctx, HostBuf& b, size_t bytes) {
     if (bytes <= b.cap) return MEME_OK;
     if (b.p) { HIP_TRY(hipStreamSynchronize(ctx->stream)); HIP_TRY(hipHostFree(b.p)); b.p = nullptr; b.cap = 0; }
     size_t want = bytes + bytes / 4 + 4096;
@@ -96,50 +96,33 @@ extern "C" meme_ctx* meme_ctx_create(int device) {
     return ctx;
 }
 
-static void free_buf(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-}
-
 extern "C" void meme_ctx_destroy(meme_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    DevBuf* bufs[] = {&ctx->reads, &ctx->read_off, &ctx->slots[0], &ctx->slots[1], &ctx->slots[2], &ctx->ovf[0],
-                      &ctx->ovf[1], &ctx->slot_cnt, &ctx->slot_hits, &ctx->slot_loc, &ctx->smem_off, &ctx->hit_off,
-                      &ctx->smems, &ctx->hits, &ctx->scan_tmp, &ctx->counters, &ctx->pairs, &ctx->refb, &ctx->qerb,
-                      &ctx->packed, &ctx->bsw_order, &ctx->bsw_ws, &ctx->pend, &ctx->blk};
-    for (DevBuf* b : bufs) free_buf(*b);
-    for (DevBuf& b : ctx->chain) free_buf(b);
-    for (DevBuf& b : ctx->ext) free_buf(b);
-    for (DevBuf& b : ctx->gcig) free_buf(b);
-    for (DevBuf& b : ctx->sam) free_buf(b);
-    for (DevBuf& b : ctx->kswv) free_buf(b);
-    for (DevBuf& b : ctx->mate) free_buf(b);
-    for (meme_ctx::HostBuf& h : ctx->h_chain) if (h.p) (void)hipHostFree(h.p);
-    for (meme_ctx::HostBuf& h : ctx->h_ext) if (h.p) (void)hipHostFree(h.p);
-    for (meme_ctx::HostBuf& h : ctx->h_gcig) if (h.p) (void)hipHostFree(h.p);
-    for (meme_ctx::HostBuf& h : ctx->h_sam) if (h.p) (void)hipHostFree(h.p);
-    for (meme_ctx::HostBuf& h : ctx->h_mate) if (h.p) (void)hipHostFree(h.p);
-    if (ctx->h_kswv.p) (void)hipHostFree(ctx->h_kswv.p);
+    for (hipStream_t st : {ctx->stream, ctx->stream_side[0], ctx->stream_side[1], ctx->stream_side[2], ctx->stream_emit})
+        if (st) (void)hipStreamSynchronize(st);
     if (ctx->owns_index) for (auto& o : ctx->owned) (void)hipFree(o.first);
     if (ctx->plcp_aux) (void)hipFree(ctx->plcp_aux);
-    for (meme_ctx::HostBuf* h : {&ctx->h_smems, &ctx->h_hits, &ctx->h_smem_off, &ctx->h_hit_off, &ctx->h_misc})
-        if (h->p) (void)hipHostFree(h->p);
-    for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->ev_chain) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->ev_ext) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->ev_gcig) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->ev_sam) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->ev_kswv) if (e) (void)hipEventDestroy(e);
-    if (ctx->ev_aux) (void)hipEventDestroy(ctx->ev_aux);
-    for (auto& e : ctx->ev_emit) if (e) (void)hipEventDestroy(e);
-    if (ctx->stream_emit) { (void)hipStreamSynchronize(ctx->stream_emit); (void)hipStreamDestroy(ctx->stream_emit); }
-    for (auto& e : ctx->ev_side) if (e) (void)hipEventDestroy(e);
-    for (auto& st : ctx->stream_side) if (st) (void)hipStreamDestroy(st);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
+}
+
+int meme_stage_contigs(meme_ctx* ctx, DevBuf& buf, std::vector<unsigned char>& host, const meme_contig* contigs, int32_t n_contigs, i64 l_pac, bool with_alt,
+                       const char* prefix, ContigTab* out) {
+    for (int i = 0; i < n_contigs; ++i)            // bntann1_t: 64-bit offset, 32-bit length; ascending, inside the forward strand
+        if (contigs[i].len < 1 || contigs[i].offset < 0 || contigs[i].offset + contigs[i].len > l_pac || (i > 0 && contigs[i].offset < contigs[i - 1].offset + contigs[i - 1].len)) {
+            meme_set_error("%scontig %d (offset %lld, length %d) is not a valid reference sequence of a %lld-base genome", prefix, i, (long long)contigs[i].offset, contigs[i].len,
+                           (long long)l_pac);
+            return MEME_E_ARG;
+        }
+    const size_t bytes = ContigTab(nullptr, n_contigs, with_alt).bytes;
+    int rc = meme_buf_reserve(ctx, buf, bytes);
+    if (rc) return rc;
+    host.assign(bytes, 0);
+    ContigTab t(host.data(), n_contigs, with_alt);
+    for (int i = 0; i < n_contigs; ++i) { t.off[i] = contigs[i].offset; t.len[i] = contigs[i].len; if (with_alt) t.alt[i] = contigs[i].is_alt ? 1 : 0; }
+    HIP_TRY(hipMemcpyAsync(buf.p, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    *out = ContigTab(buf.p, n_contigs, with_alt);
+    return MEME_OK;
 }
 
 extern "C" int meme_ctx_sync(meme_ctx* ctx) {
@@ -185,7 +168,6 @@ extern "C" int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value) {
     return MEME_OK;
 }
 
-static unsigned stage_blocks(i64 items);
 extern "C" int meme_index_share(meme_ctx* ctx, meme_ctx* owner);
 // ---- staging kernels ---------------------------------------------------------------------------------
 extern "C" int64_t meme_index_pac64_words(int64_t sa_num) { return ((sa_num + 31) >> 5) + 8; }
@@ -295,7 +277,7 @@ __global__ void __launch_bounds__(256) k_build_plcp(const SaEnt* __restrict__ en
 extern "C" int meme_stage_build_plcp(meme_ctx* ctx, const void* d_sa_ent, int64_t n, const void* d_pac64, void* d_plcp) {
     if (!ctx || !d_sa_ent || !d_pac64 || !d_plcp || n <= 0) return MEME_E_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_build_plcp, dim3(stage_blocks(n)), dim3(256), 0, ctx->stream, (const SaEnt*)d_sa_ent, (i64)n, (const u64*)d_pac64,
+    hipLaunchKernelGGL(k_build_plcp, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, (const SaEnt*)d_sa_ent, (i64)n, (const u64*)d_pac64,
                        (uint8_t*)d_plcp);
     HIP_TRY(hipGetLastError());
     return MEME_OK;
@@ -305,7 +287,7 @@ extern "C" int meme_stage_pack_text(meme_ctx* ctx, const uint8_t* d_text, int64_
     if (!ctx || !d_text || !d_pac64 || n <= 0) return MEME_E_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     i64 words = meme_index_pac64_words(n);
-    hipLaunchKernelGGL(k_pack_text, dim3(stage_blocks(words)), dim3(256), 0, ctx->stream, d_text, n,
+    hipLaunchKernelGGL(k_pack_text, dim3(grid_blocks(words, 256)), dim3(256), 0, ctx->stream, d_text, n,
                        (u64*)d_pac64, words);
     HIP_TRY(hipGetLastError());
     return MEME_OK;
@@ -315,7 +297,7 @@ extern "C" int meme_stage_build_entries(meme_ctx* ctx, const uint8_t* d_pos_pack
                                         void* d_sa_ent) {
     if (!ctx || !d_pos_packed || !d_pac64 || !d_sa_ent || n <= 0) return MEME_E_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_build_entries, dim3(stage_blocks(n)), dim3(256), 0, ctx->stream, d_pos_packed,
+    hipLaunchKernelGGL(k_build_entries, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, d_pos_packed,
                        (const u64*)nullptr, (i64)n, (const u64*)d_pac64, (SaEnt*)d_sa_ent);
     HIP_TRY(hipGetLastError());
     return MEME_OK;
@@ -325,7 +307,7 @@ extern "C" int meme_stage_entries_from_sa(meme_ctx* ctx, const uint64_t* d_sa, i
                                           void* d_sa_ent) {
     if (!ctx || !d_sa || !d_pac64 || !d_sa_ent || n <= 0) return MEME_E_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_build_entries, dim3(stage_blocks(n)), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(k_build_entries, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream,
                        (const uint8_t*)nullptr, (const u64*)d_sa, (i64)n, (const u64*)d_pac64, (SaEnt*)d_sa_ent);
     HIP_TRY(hipGetLastError());
     return MEME_OK;
@@ -334,7 +316,7 @@ extern "C" int meme_stage_entries_from_sa(meme_ctx* ctx, const uint64_t* d_sa, i
 extern "C" int meme_stage_pos5_from_sa(meme_ctx* ctx, const uint64_t* d_sa, int64_t n, void* d_pos5) {
     if (!ctx || !d_sa || !d_pos5 || n <= 0) return MEME_E_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_pos5_from_sa, dim3(stage_blocks(n)), dim3(256), 0, ctx->stream, (const u64*)d_sa, (i64)n, (uint8_t*)d_pos5);
+    hipLaunchKernelGGL(k_pos5_from_sa, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, (const u64*)d_sa, (i64)n, (uint8_t*)d_pos5);
     HIP_TRY(hipGetLastError());
     return MEME_OK;
 }
@@ -343,18 +325,12 @@ extern "C" int meme_stage_rmi32(meme_ctx* ctx, const void* d_rmi24, int64_t reco
     if (!ctx || !d_rmi32 || records < 0 || (records > 0 && !d_rmi24)) return MEME_E_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     if (records == 0) return MEME_OK;
-    hipLaunchKernelGGL(k_rmi32, dim3(stage_blocks(records)), dim3(256), 0, ctx->stream, (const RmiRec*)d_rmi24, (i64)records, (Rmi32*)d_rmi32);
+    hipLaunchKernelGGL(k_rmi32, dim3(grid_blocks(records, 256)), dim3(256), 0, ctx->stream, (const RmiRec*)d_rmi24, (i64)records, (Rmi32*)d_rmi32);
     HIP_TRY(hipGetLastError());
     return MEME_OK;
 }
 
 // ---- index objects ------------------------------------------------------------------------------------
-static unsigned stage_blocks(i64 items) {
-    i64 b = (items + 255) / 256;
-    const i64 cap = 256 * 64;           // 64 workgroups per CU, grid-stride beyond that
-    return (unsigned)(b < cap ? (b < 1 ? 1 : b) : cap);
-}
-
 static int set_rmi(meme_ctx* ctx, i64 l2_records, i64 l1_records) {
     if (l2_records <= 0 || (l2_records & (l2_records - 1)) != 0) {
         // learned_index_load() requires num_model to be a power of two (src/LearnedIndex_seeding.cpp:113-119)
@@ -433,15 +409,15 @@ static int index_build_from(meme_ctx* ctx, int64_t n, int64_t l1_bytes, int64_t 
     if (stream) {
         // every piece of the position image becomes entries as soon as it is on the device; the same for the model records
         if ((rc = stream(1, 5, [&](const void* d_piece, i64 first, i64 count, hipStream_t st) {
-                hipLaunchKernelGGL(k_build_entries, dim3(stage_blocks(count)), dim3(256), 0, st, (const uint8_t*)d_piece, (const u64*)nullptr, count,
+                hipLaunchKernelGGL(k_build_entries, dim3(grid_blocks(count, 256)), dim3(256), 0, st, (const uint8_t*)d_piece, (const u64*)nullptr, count,
                                    (const u64*)d_pac, (SaEnt*)d_ent + first);
             }))) return fail(rc);
         lap("position image -> entries (streamed)");
         if ((rc = stream(2, 24, [&](const void* d_piece, i64 first, i64 count, hipStream_t st) {
-                hipLaunchKernelGGL(k_rmi32, dim3(stage_blocks(count)), dim3(256), 0, st, (const RmiRec*)d_piece, count, (Rmi32*)d_l2 + first);
+                hipLaunchKernelGGL(k_rmi32, dim3(grid_blocks(count, 256)), dim3(256), 0, st, (const RmiRec*)d_piece, count, (Rmi32*)d_l2 + first);
             }))) return fail(rc);
         if (n_l1 > 0 && (rc = stream(3, 24, [&](const void* d_piece, i64 first, i64 count, hipStream_t st) {
-                hipLaunchKernelGGL(k_rmi32, dim3(stage_blocks(count)), dim3(256), 0, st, (const RmiRec*)d_piece, count, (Rmi32*)d_l1 + first);
+                hipLaunchKernelGGL(k_rmi32, dim3(grid_blocks(count, 256)), dim3(256), 0, st, (const RmiRec*)d_piece, count, (Rmi32*)d_l1 + first);
             }))) return fail(rc);
         if (hipGetLastError() != hipSuccess) return fail(MEME_E_HIP);
     } else {

@@ -589,8 +589,6 @@ __global__ void __launch_bounds__(256) k_ext_split(const i64* __restrict__ seed_
     }
 }
 
-unsigned grid_of(i64 items, int per) { i64 b = (items + per - 1) / per; const i64 cap = 256 * 64; return (unsigned)(b < cap ? (b < 1 ? 1 : b) : cap); }
-
 // tuning "ext_live_only": what mem_kernel2_core does first with the stage's records (src/bwamem.cpp:1680-1693: every record with qe <= qb -- the purged
 // ones -- is dropped, the others keep their order) done before the records cross to the host: a read's surviving records counted, then packed.
 __global__ void __launch_bounds__(256) k_ext_live_count(const i64* __restrict__ seed_off, const meme_alnreg* __restrict__ regs, i64 n, i64* __restrict__ cnt) {
@@ -655,8 +653,8 @@ extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* con
     if (copt->max_occ < 1 || copt->l_pac < 1 || eopt->e_del < 1 || eopt->e_ins < 1 || eopt->w < 1) { meme_set_error("meme_extend_last_batch_host: bad options"); return MEME_E_ARG; }
     HIP_TRY(hipSetDevice(ctx->device));
     memset(out, 0, sizeof(*out));
-    const i64 n = ctx->last_seed_reads;
-    if (n <= 0 || !ctx->smem_off.p || !ctx->read_off.p || !ctx->reads.p || !ctx->reads_resident) {
+    const i64 n = ctx->batch.last_seed_reads;
+    if (n <= 0 || !ctx->batch.smem_off.p || !ctx->batch.read_off.p || !ctx->batch.reads.p || !ctx->batch.reads_resident) {
         meme_set_error("meme_extend_last_batch_host: no seeded batch on this ctx (a seeding call has to stage the reads; meme_chain_batch_host brings seeds only)");
         return MEME_E_STATE;
     }
@@ -665,25 +663,26 @@ extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* con
     int rc;
     i64 tot[2];
     if ((rc = meme_chain_run(ctx, contigs, n_contigs, copt, tot))) return rc;
-    hipEvent_t* ev = ctx->ev_ext;
+    ExtWs& E = ctx->ext;
+    const ChainWs& C = ctx->chain;
+    Events<2>& ev = E.ev;
     for (int i = 0; i < 2; ++i) if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
     HIP_TRY(hipEventRecord(ev[0], ctx->stream));
-    DevBuf* B = ctx->chain;
-    DevBuf* E = ctx->ext;       // 0 rmax, 1 regs, 2 order, 3 counts + scans, 4 L pairs, 5 R pairs, 6 retry pairs (two halves), 7 sequences, 8 counters,
-                                // 9 .. 14 the seed filter's: scores, jobs, counts + new seed offsets, kept seeds, their scores, thresholds; 15, 16 surviving records: counts + scan, packed
-    const i64* d_choff = (const i64*)B[5].p;
-    const i64* d_sdoff = d_choff + (n + 1);
+    const i64* d_choff = C.chain_off();
+    const i64* d_sdoff = C.seed_off(n);
+    const ContigTab ct(C.contigs.p, n_contigs, true);
     const i64 n_chains = tot[0];
     i64 n_seeds = tot[1];
-    if ((rc = meme_buf_reserve(ctx, E[8], 256))) return rc;
+    if ((rc = meme_buf_reserve(ctx, E.counters, EXT_CTR_BYTES))) return rc;
+    unsigned long long* const ctr = (unsigned long long*)E.counters.p;
     // ---- mem_flt_chained_seeds: the read lengths it runs for and their thresholds, evaluated the way the reference's host code does
     // (:579-583: float coefficients, double min_l, libm's log).  Never with reads below ~760 bases unless -W is given.
-    const meme_chain_seed* d_seeds = (const meme_chain_seed*)B[7].p;
+    const meme_chain_seed* d_seeds = (const meme_chain_seed*)C.seeds.p;
     const int* d_score = nullptr;
-    unsigned long long* d_fltcnt = (unsigned long long*)E[8].p + 2;
+    unsigned long long* d_fltcnt = ctr + EXT_CTR_FLT_JOBS;
     bool flt = false;
     {
-        const i64 max_len = ctx->last_seed_max_len;
+        const i64 max_len = ctx->batch.last_seed_max_len;
         std::vector<int> hsp((size_t)max_len + 2, -1);
         for (i64 l = 2; l <= max_len; ++l) {
             const int l_query = (int)l;
@@ -695,17 +694,17 @@ extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* con
         }
         if (flt && n_seeds > 0) {
             if (n_seeds >= 0x7fffffff) { meme_set_error("meme_extend_last_batch_host: %lld chained seeds in one batch", (long long)n_seeds); return MEME_E_CAPACITY; }
-            if ((rc = meme_buf_reserve(ctx, E[9], (size_t)(n_seeds + 1) * 4)) || (rc = meme_buf_reserve(ctx, E[10], (size_t)(n_seeds + 1) * sizeof(meme_seedsw_job))) ||
-                (rc = meme_buf_reserve(ctx, E[11], (size_t)(n + 1) * 16)) || (rc = meme_buf_reserve(ctx, E[12], (size_t)(n_seeds + 1) * sizeof(meme_chain_seed))) ||
-                (rc = meme_buf_reserve(ctx, E[13], (size_t)(n_seeds + 1) * 4)) || (rc = meme_buf_reserve(ctx, E[14], hsp.size() * 4))) return rc;
-            HIP_TRY(hipMemcpyAsync(E[14].p, hsp.data(), hsp.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+            if ((rc = meme_buf_reserve(ctx, E.flt_sc, (size_t)(n_seeds + 1) * 4)) || (rc = meme_buf_reserve(ctx, E.flt_jobs, (size_t)(n_seeds + 1) * sizeof(meme_seedsw_job))) ||
+                (rc = meme_buf_reserve(ctx, E.flt_cnt, (size_t)(n + 1) * 16)) || (rc = meme_buf_reserve(ctx, E.flt_seeds, (size_t)(n_seeds + 1) * sizeof(meme_chain_seed))) ||
+                (rc = meme_buf_reserve(ctx, E.flt_score, (size_t)(n_seeds + 1) * 4)) || (rc = meme_buf_reserve(ctx, E.flt_hsp, hsp.size() * 4))) return rc;
+            HIP_TRY(hipMemcpyAsync(E.flt_hsp.p, hsp.data(), hsp.size() * 4, hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(hipMemsetAsync(d_fltcnt, 0, 8, ctx->stream));
             FltArgs F;
             memset(&F, 0, sizeof(F));
-            F.read_off = (const i64*)ctx->read_off.p; F.n = n; F.chain_off = d_choff; F.chains = (meme_chain*)B[6].p; F.seed_off = d_sdoff; F.seeds = d_seeds;
-            F.l_pac = copt->l_pac; F.contig_off = (const i64*)B[4].p; F.contig_len = (const int*)((unsigned char*)B[4].p + (size_t)n_contigs * 8); F.n_contigs = n_contigs;
-            F.hsp = (const int*)E[14].p; F.a = eopt->a; F.sc = (int*)E[9].p; F.jobs = (meme_seedsw_job*)E[10].p; F.n_jobs = d_fltcnt;
-            F.cnt = (i64*)E[11].p; F.off2 = F.cnt + (n + 1); F.seeds2 = (meme_chain_seed*)E[12].p; F.score2 = (int*)E[13].p;
+            F.read_off = (const i64*)ctx->batch.read_off.p; F.n = n; F.chain_off = d_choff; F.chains = (meme_chain*)C.chains.p; F.seed_off = d_sdoff; F.seeds = d_seeds;
+            F.l_pac = copt->l_pac; F.contig_off = ct.off; F.contig_len = ct.len; F.n_contigs = n_contigs;
+            F.hsp = (const int*)E.flt_hsp.p; F.a = eopt->a; F.sc = (int*)E.flt_sc.p; F.jobs = (meme_seedsw_job*)E.flt_jobs.p; F.n_jobs = d_fltcnt;
+            F.cnt = (i64*)E.flt_cnt.p; F.off2 = F.cnt + (n + 1); F.seeds2 = (meme_chain_seed*)E.flt_seeds.p; F.score2 = (int*)E.flt_score.p;
             hipLaunchKernelGGL(k_flt_pose, dim3((unsigned)n), dim3(64), 0, ctx->stream, F);
             if ((rc = meme_seedsw_launch(ctx, F.jobs, d_fltcnt, n_seeds, F.sc, eopt))) return rc;
             hipLaunchKernelGGL((k_flt_apply<false>), dim3((unsigned)n), dim3(64), 0, ctx->stream, F);
@@ -715,43 +714,42 @@ extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* con
             d_sdoff = F.off2; d_seeds = F.seeds2; d_score = F.score2;
         } else flt = false;
     }
-    if ((rc = meme_buf_reserve(ctx, E[0], (size_t)(n_chains + 1) * 16)) || (rc = meme_buf_reserve(ctx, E[1], (size_t)(n_seeds + 1) * sizeof(meme_alnreg))) ||
-        (rc = meme_buf_reserve(ctx, E[2], (size_t)(n_seeds + 1) * 4)) || (rc = meme_buf_reserve(ctx, E[3], (size_t)(n + 1) * 8 * 8))) return rc;
+    if ((rc = meme_buf_reserve(ctx, E.rmax, (size_t)(n_chains + 1) * 16)) || (rc = meme_buf_reserve(ctx, E.regs, (size_t)(n_seeds + 1) * sizeof(meme_alnreg))) ||
+        (rc = meme_buf_reserve(ctx, E.order, (size_t)(n_seeds + 1) * 4)) || (rc = meme_buf_reserve(ctx, E.counts, ExtCounts(nullptr, n).bytes))) return rc;
     ExtArgs A;
     memset(&A, 0, sizeof(A));
-    A.reads = (const uint8_t*)ctx->reads.p; A.read_off = (const i64*)ctx->read_off.p; A.g0 = 0; A.ns = n;
-    A.chain_off = d_choff; A.chains = (const meme_chain*)B[6].p; A.seed_off = d_sdoff; A.seeds = d_seeds; A.seed_score = d_score; A.frac_rep = (const float*)B[3].p;
+    A.reads = (const uint8_t*)ctx->batch.reads.p; A.read_off = (const i64*)ctx->batch.read_off.p; A.g0 = 0; A.ns = n;
+    A.chain_off = d_choff; A.chains = (const meme_chain*)C.chains.p; A.seed_off = d_sdoff; A.seeds = d_seeds; A.seed_score = d_score; A.frac_rep = (const float*)C.frac.p;
     A.pac = ctx->idx.pac; A.l_pac = copt->l_pac;
-    A.contig_off = (const i64*)B[4].p; A.contig_len = (const int*)((unsigned char*)B[4].p + (size_t)n_contigs * 8);
+    A.contig_off = ct.off; A.contig_len = ct.len;
     A.o = *eopt;
-    A.rmax = (i64*)E[0].p; A.regs = (meme_alnreg*)E[1].p; A.order = (int*)E[2].p;
-    i64* d_cnt = (i64*)E[3].p;
-    i64* d_off = d_cnt + 3 * (n + 1);
-    A.cntL = d_cnt; A.cntR = d_cnt + (n + 1); A.cntB = d_cnt + 2 * (n + 1);
+    A.rmax = (i64*)E.rmax.p; A.regs = (meme_alnreg*)E.regs.p; A.order = (int*)E.order.p;
+    const ExtCounts ec(E.counts.p, n);
+    A.cntL = ec.cntL; A.cntR = ec.cntR; A.cntB = ec.cntB;
     meme_bsw_opt bl, br;
     memset(&bl, 0, sizeof(bl));
     bl.o_del = eopt->o_del; bl.e_del = eopt->e_del; bl.o_ins = eopt->o_ins; bl.e_ins = eopt->e_ins; bl.zdrop = eopt->zdrop; bl.a = eopt->a; bl.b = eopt->b;
     br = bl;
     bl.end_bonus = eopt->pen_clip5;                   // bswLeft / bswRight, src/bwamem.cpp:2953-2959
     br.end_bonus = eopt->pen_clip3;
-    unsigned long long* d_nretry = (unsigned long long*)E[8].p;
-    i64* d_cntS = d_cnt + 6 * (n + 1);              // seeds selected per read in a round, and its scan
-    i64* d_offS = d_cnt + 7 * (n + 1);
-    unsigned long long* d_census = (unsigned long long*)E[8].p + 8;
+    unsigned long long* d_nretry = ctr + EXT_CTR_RETRY;
+    i64* d_cntS = ec.cntS;                          // seeds selected per read in a round, and its scan
+    i64* d_offS = ec.offS;
+    unsigned long long* d_census = ctr + EXT_CTR_CENSUS;
     if (ctx->ext_census) HIP_TRY(hipMemsetAsync(d_census, 0, 11 * 8, ctx->stream));
     // ---- light and heavy reads (round 6): the list of reads with more than EXT_LIGHT chained seeds; everything else runs eight lanes per read
     i64 n_heavy = 0;
     const i64* d_heavy = nullptr;
     const bool split = ctx->ext_split != 0;
     if (split) {
-        if ((rc = meme_buf_reserve(ctx, E[18], (size_t)(n + 1) * 8))) return rc;
-        unsigned long long* d_nheavy = (unsigned long long*)E[8].p + 24;
+        if ((rc = meme_buf_reserve(ctx, E.heavy, (size_t)(n + 1) * 8))) return rc;
+        unsigned long long* d_nheavy = ctr + EXT_CTR_HEAVY;
         HIP_TRY(hipMemsetAsync(d_nheavy, 0, 8, ctx->stream));
-        hipLaunchKernelGGL(k_ext_split, dim3(grid_of(n, 256)), dim3(256), 0, ctx->stream, d_sdoff, n, (i64*)E[18].p, d_nheavy);
+        hipLaunchKernelGGL(k_ext_split, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, d_sdoff, n, (i64*)E.heavy.p, d_nheavy);
         unsigned long long h = 0;
         HIP_TRY(hipMemcpyAsync(&h, d_nheavy, 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        n_heavy = (i64)h; d_heavy = (const i64*)E[18].p;
+        n_heavy = (i64)h; d_heavy = (const i64*)E.heavy.p;
     }
     // a kernel that walks the reads of [X.g0, X.g0 + X.ns): one launch of wavefronts, or -- split, and the range is the whole batch -- eight lanes per light read + a wavefront per listed read
     auto launch_jobs = [&](ExtArgs X, bool write) {
@@ -781,9 +779,9 @@ extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* con
     auto run_jobs = [&](i64* n_sel_out) -> int {
         int rc;
         if (A.mode != 2) launch_jobs(A, false);      // (in rounds k_ext_advance has counted)
-        for (int k = 0; k < 3; ++k) if ((rc = meme_scan_exclusive(ctx, d_cnt + k * (n + 1), d_off + k * (n + 1), n))) return rc;
+        for (int k = 0; k < 3; ++k) if ((rc = meme_scan_exclusive(ctx, ec.cntL + k * (n + 1), ec.offL + k * (n + 1), n))) return rc;
         i64 tot3[3] = {0, 0, 0};
-        for (int k = 0; k < 3; ++k) HIP_TRY(hipMemcpyAsync(&tot3[k], d_off + k * (n + 1) + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+        for (int k = 0; k < 3; ++k) HIP_TRY(hipMemcpyAsync(&tot3[k], ec.offL + k * (n + 1) + n, 8, hipMemcpyDeviceToHost, ctx->stream));
         if (n_sel_out) {
             if ((rc = meme_scan_exclusive(ctx, d_cntS, d_offS, n))) return rc;
             HIP_TRY(hipMemcpyAsync(n_sel_out, d_offS + n, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -800,7 +798,7 @@ extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* con
         if (tot3[0] + tot3[1] == 0) return MEME_OK;
         if (!one_slab) {
             h_off.resize((size_t)(3 * (n + 1)));
-            HIP_TRY(hipMemcpyAsync(h_off.data(), d_off, h_off.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(h_off.data(), ec.offL, h_off.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(hipStreamSynchronize(ctx->stream));
         }
         const i64* oL = one_slab ? nullptr : h_off.data();
@@ -821,34 +819,34 @@ extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* con
                 j0L = oL[g0]; j0R = oR[g0]; b0 = oB[g0];
             }
             const i64 nmax = nL > nR ? nL : nR;
-            if ((rc = meme_buf_reserve(ctx, E[4], (size_t)(nL + 1) * sizeof(meme_seqpair))) || (rc = meme_buf_reserve(ctx, E[5], (size_t)(nR + 1) * sizeof(meme_seqpair))) ||
-                (rc = meme_buf_reserve(ctx, E[6], (size_t)(2 * nmax + 2) * sizeof(meme_seqpair))) || (rc = meme_buf_reserve(ctx, E[7], (size_t)nB + 256))) return rc;
+            if ((rc = meme_buf_reserve(ctx, E.pairs_l, (size_t)(nL + 1) * sizeof(meme_seqpair))) || (rc = meme_buf_reserve(ctx, E.pairs_r, (size_t)(nR + 1) * sizeof(meme_seqpair))) ||
+                (rc = meme_buf_reserve(ctx, E.retry, (size_t)(2 * nmax + 2) * sizeof(meme_seqpair))) || (rc = meme_buf_reserve(ctx, E.seq, (size_t)nB + 256))) return rc;
             ExtArgs S = A;
             S.g0 = g0; S.ns = g1 - g0;
             // (the scans cover the whole batch: a slab's first read has its own offsets to subtract)
-            S.offL = d_off + g0; S.offR = d_off + (n + 1) + g0; S.offB = d_off + 2 * (n + 1) + g0;
+            S.offL = ec.offL + g0; S.offR = ec.offR + g0; S.offB = ec.offB + g0;
             S.job0L = j0L; S.job0R = j0R; S.byte0 = b0;
-            S.L = (meme_seqpair*)E[4].p; S.R = (meme_seqpair*)E[5].p; S.seq = (uint8_t*)E[7].p;
+            S.L = (meme_seqpair*)E.pairs_l.p; S.R = (meme_seqpair*)E.pairs_r.p; S.seq = (uint8_t*)E.seq.p;
             launch_jobs(S, true);
             HIP_TRY(hipGetLastError());
             if (ctx->ext_census) {
-                if (nL) hipLaunchKernelGGL(k_ext_census, dim3(grid_of(nL, 256)), dim3(256), 0, ctx->stream, (const meme_seqpair*)S.L, nL, (const uint8_t*)S.seq, eopt->w, d_census);
-                if (nR) hipLaunchKernelGGL(k_ext_census, dim3(grid_of(nR, 256)), dim3(256), 0, ctx->stream, (const meme_seqpair*)S.R, nR, (const uint8_t*)S.seq, eopt->w, d_census);
+                if (nL) hipLaunchKernelGGL(k_ext_census, dim3(grid_blocks(nL, 256)), dim3(256), 0, ctx->stream, (const meme_seqpair*)S.L, nL, (const uint8_t*)S.seq, eopt->w, d_census);
+                if (nR) hipLaunchKernelGGL(k_ext_census, dim3(grid_blocks(nR, 256)), dim3(256), 0, ctx->stream, (const meme_seqpair*)S.R, nR, (const uint8_t*)S.seq, eopt->w, d_census);
             }
             for (int dir = 0; dir < 2; ++dir) {
                 meme_seqpair* P = dir == 0 ? S.L : S.R;
                 i64 np = dir == 0 ? nL : nR;
-                if (dir == 1 && np > 0) hipLaunchKernelGGL(k_ext_h0, dim3(grid_of(np, 256)), dim3(256), 0, ctx->stream, P, np, (const meme_alnreg*)A.regs);
+                if (dir == 1 && np > 0) hipLaunchKernelGGL(k_ext_h0, dim3(grid_blocks(np, 256)), dim3(256), 0, ctx->stream, P, np, (const meme_alnreg*)A.regs);
                 for (int attempt = 0; attempt < EXT_BAND_TRIES && np > 0; ++attempt) {
                     const int w = eopt->w << attempt;
-                    if ((rc = meme_bsw_launch(ctx, P, S.seq, S.seq, (int)np, w, dir == 0 ? &bl : &br, (int)ctx->last_seed_max_len))) return rc;
+                    if ((rc = meme_bsw_launch(ctx, P, S.seq, S.seq, (int)np, w, dir == 0 ? &bl : &br, (int)ctx->batch.last_seed_max_len))) return rc;
                     HIP_TRY(hipMemsetAsync(d_nretry, 0, 8, ctx->stream));
                     FoldArgs F;
                     F.pairs = P; F.n = np; F.regs = A.regs; F.chains = A.chains; F.seed_off = A.seed_off; F.seeds = A.seeds; F.read_off = A.read_off;
                     F.o = *eopt; F.w = w; F.last = attempt + 1 == EXT_BAND_TRIES;
-                    F.retry = (meme_seqpair*)E[6].p + (size_t)(attempt & 1) * (size_t)(nmax + 1); F.n_retry = d_nretry;
-                    if (dir == 0) hipLaunchKernelGGL((k_ext_fold<true>), dim3(grid_of(np, 256)), dim3(256), 0, ctx->stream, F);
-                    else hipLaunchKernelGGL((k_ext_fold<false>), dim3(grid_of(np, 256)), dim3(256), 0, ctx->stream, F);
+                    F.retry = (meme_seqpair*)E.retry.p + (size_t)(attempt & 1) * (size_t)(nmax + 1); F.n_retry = d_nretry;
+                    if (dir == 0) hipLaunchKernelGGL((k_ext_fold<true>), dim3(grid_blocks(np, 256)), dim3(256), 0, ctx->stream, F);
+                    else hipLaunchKernelGGL((k_ext_fold<false>), dim3(grid_blocks(np, 256)), dim3(256), 0, ctx->stream, F);
                     unsigned long long h_retry = 0;
                     HIP_TRY(hipMemcpyAsync(&h_retry, d_nretry, 8, hipMemcpyDeviceToHost, ctx->stream));
                     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -877,9 +875,10 @@ extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* con
         n_seeds_ext = h_flt[0];
     } else {
         // ---- in rounds (see k_ext_advance): records + extension order first, then `rounds` rounds of one seed per read, one round with everything still ahead
-        if ((rc = meme_buf_reserve(ctx, E[17], (size_t)(n + 1) * 16 + (size_t)(n + 1) + (size_t)n_seeds + 64))) return rc;
+        if ((rc = meme_buf_reserve(ctx, E.rounds, ExtRounds(nullptr, n, n_seeds).bytes))) return rc;
+        const ExtRounds er(E.rounds.p, n, n_seeds);
         AdvArgs V;
-        V.P = P; V.state = (int4*)E[17].p; V.act = (uint8_t*)(V.state + (n + 1)); V.sel = V.act + (n + 1); V.cntS = d_cntS;
+        V.P = P; V.state = er.state; V.act = er.act; V.sel = er.sel; V.cntS = d_cntS;
         V.rmax = A.rmax; V.cntL = A.cntL; V.cntR = A.cntR; V.cntB = A.cntB;
         A.mode = 1; A.state = V.state;
         launch_jobs(A, true);
@@ -908,26 +907,25 @@ extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* con
     const i64 n_flt_dropped = n_seeds - h_flt[0];
     n_seeds = h_flt[0];
     HIP_TRY(hipEventRecord(ev[1], ctx->stream));
-    meme_ctx::HostBuf* Hb = ctx->h_ext;
-    if ((rc = meme_hostbuf_reserve(ctx, Hb[0], (size_t)(n + 1) * 8))) return rc;
+    if ((rc = meme_hostbuf_reserve(ctx, E.h_reg_off, (size_t)(n + 1) * 8))) return rc;
     i64 n_out = n_seeds;                                // records that cross to the host
     if (ctx->ext_live_only) {
-        if ((rc = meme_buf_reserve(ctx, E[15], (size_t)(n + 1) * 16))) return rc;
-        i64* d_lcnt = (i64*)E[15].p;
+        if ((rc = meme_buf_reserve(ctx, E.live_cnt, (size_t)(n + 1) * 16))) return rc;
+        i64* d_lcnt = (i64*)E.live_cnt.p;
         i64* d_loff = d_lcnt + (n + 1);
-        hipLaunchKernelGGL(k_ext_live_count, dim3(grid_of(n, 256)), dim3(256), 0, ctx->stream, d_sdoff, (const meme_alnreg*)A.regs, n, d_lcnt);
+        hipLaunchKernelGGL(k_ext_live_count, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, d_sdoff, (const meme_alnreg*)A.regs, n, d_lcnt);
         if ((rc = meme_scan_exclusive(ctx, d_lcnt, d_loff, n))) return rc;
-        HIP_TRY(hipMemcpyAsync(Hb[0].p, d_loff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(E.h_reg_off.p, d_loff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        n_out = ((const i64*)Hb[0].p)[n];
-        if ((rc = meme_buf_reserve(ctx, E[16], (size_t)(n_out + 1) * sizeof(meme_alnreg))) || (rc = meme_hostbuf_reserve(ctx, Hb[1], (size_t)(n_out + 1) * sizeof(meme_alnreg)))) return rc;
-        hipLaunchKernelGGL(k_ext_live_pack, dim3(grid_of(n, 256)), dim3(256), 0, ctx->stream, d_sdoff, (const meme_alnreg*)A.regs, n, (const i64*)d_loff, (meme_alnreg*)E[16].p);
+        n_out = ((const i64*)E.h_reg_off.p)[n];
+        if ((rc = meme_buf_reserve(ctx, E.live_regs, (size_t)(n_out + 1) * sizeof(meme_alnreg))) || (rc = meme_hostbuf_reserve(ctx, E.h_regs, (size_t)(n_out + 1) * sizeof(meme_alnreg)))) return rc;
+        hipLaunchKernelGGL(k_ext_live_pack, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, d_sdoff, (const meme_alnreg*)A.regs, n, (const i64*)d_loff, (meme_alnreg*)E.live_regs.p);
         HIP_TRY(hipGetLastError());
-        if (n_out) HIP_TRY(hipMemcpyAsync(Hb[1].p, E[16].p, (size_t)n_out * sizeof(meme_alnreg), hipMemcpyDeviceToHost, ctx->stream));
+        if (n_out) HIP_TRY(hipMemcpyAsync(E.h_regs.p, E.live_regs.p, (size_t)n_out * sizeof(meme_alnreg), hipMemcpyDeviceToHost, ctx->stream));
     } else {
-        if ((rc = meme_hostbuf_reserve(ctx, Hb[1], (size_t)(n_seeds + 1) * sizeof(meme_alnreg)))) return rc;
-        HIP_TRY(hipMemcpyAsync(Hb[0].p, d_sdoff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (n_seeds) HIP_TRY(hipMemcpyAsync(Hb[1].p, A.regs, (size_t)n_seeds * sizeof(meme_alnreg), hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = meme_hostbuf_reserve(ctx, E.h_regs, (size_t)(n_seeds + 1) * sizeof(meme_alnreg)))) return rc;
+        HIP_TRY(hipMemcpyAsync(E.h_reg_off.p, d_sdoff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (n_seeds) HIP_TRY(hipMemcpyAsync(E.h_regs.p, A.regs, (size_t)n_seeds * sizeof(meme_alnreg), hipMemcpyDeviceToHost, ctx->stream));
     }
     unsigned long long h_census[11] = {0};
     if (ctx->ext_census) HIP_TRY(hipMemcpyAsync(h_census, d_census, 11 * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -937,7 +935,7 @@ extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* con
     for (int c = 0; c < 9; ++c) out->census_class[c] = ctx->ext_census ? (int64_t)h_census[2 + c] : -1;
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    out->nreads = n; out->reg_off = (const int64_t*)Hb[0].p; out->regs = (const meme_alnreg*)Hb[1].p; out->total_regs = n_out; out->total_seeds = n_seeds; out->n_ext_seeds = n_seeds_ext;
+    out->nreads = n; out->reg_off = (const int64_t*)E.h_reg_off.p; out->regs = (const meme_alnreg*)E.h_regs.p; out->total_regs = n_out; out->total_seeds = n_seeds; out->n_ext_seeds = n_seeds_ext;
     out->total_chains = n_chains; out->n_pairs = n_pairs; out->n_retried = n_retried; out->n_bsw_calls = n_calls;
     out->n_flt_jobs = h_flt[1]; out->n_flt_dropped = n_flt_dropped;
     out->n_tier2 = ctx->chain_tier2_reads; out->chain_ms = ctx->tm.chain_kernel_ms; out->ext_ms = ms; out->bsw_ms = bsw_ms;

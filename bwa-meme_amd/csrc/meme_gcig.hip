@@ -628,9 +628,7 @@ __global__ void __launch_bounds__(256) k_md_pack(const meme_gres* __restrict__ r
     }
 }
 
-unsigned grid_of(i64 items, int per) { i64 b = (items + per - 1) / per; const i64 cap = 256 * 64; return (unsigned)(b < cap ? (b < 1 ? 1 : b) : cap); }
-
-// The batch from the jobs in G[0] (device) to packed results: scratch sizes, the alignment kernel, the packed operations (and MD strings).
+// The batch from the jobs in ctx->gcig.jobs (device) to packed results: scratch sizes, the alignment kernel, the packed operations (and MD strings).
 // with_md: NM + MD of every job (meme_gen_cigar_batch_host); host_jobs (may be null) only serves the error message of a bad query span.
 struct GcigRun { i64 tops = 0, tmd = 0; };
 constexpr int Z_LDS_WINDOW = 2048;          // ... and when matrices do not fit anyway: the window the walk back reads them through
@@ -645,30 +643,9 @@ int gcig_run(meme_ctx* ctx, i64 njobs, int qmax, int tmax, const meme_bsw_opt* o
     const int zauto = (size_t)tmax * 33 <= (size_t)Z_LDS_CAP ? Z_LDS_CAP : Z_LDS_WINDOW;
     const int zwant = ctx->gcig_zcap >= 0 ? (int)ctx->gcig_zcap : zauto;
     const int zcap = lds_base + (size_t)zwant <= 32 * 1024 ? zwant : 0;          // (long reads: their rows fill the LDS, the matrix stays in global memory)
-    DevBuf* G = ctx->gcig;      // 0 jobs, 1 sizes + offsets (8 x (n+1)), 2 z, 3 cigar scratch, 4 results, 5 packed cigars, 6 MD scratch, 7 nm + mdlen, 8 packed MD, 9 cjobs, 10 cres
-    if ((rc = meme_buf_reserve(ctx, G[1], (size_t)(njobs + 1) * 8 * 21 + 64)) || (rc = meme_buf_reserve(ctx, G[4], (size_t)njobs * sizeof(meme_gres)))) return rc;
-    i64* d_zsz = (i64*)G[1].p;
-    i64* d_csz = d_zsz + (njobs + 1);
-    i64* d_zoff = d_csz + (njobs + 1);
-    i64* d_coff = d_zoff + (njobs + 1);
-    i64* d_ncig = d_coff + (njobs + 1);
-    i64* d_ooff = d_ncig + (njobs + 1);
-    i64* d_msz = d_ooff + (njobs + 1);
-    i64* d_moff = d_msz + (njobs + 1);
-    i64* d_psz = d_moff + (njobs + 1);
-    i64* d_poff = d_psz + (njobs + 1);
-    i64* d_isdp = d_poff + (njobs + 1);
-    i64* d_dpoff = d_isdp + (njobs + 1);
-    i64* d_dplist = d_dpoff + (njobs + 1);
-    i64* d_is16 = d_dplist + (njobs + 1);
-    i64* d_o16 = d_is16 + (njobs + 1);
-    i64* d_is32 = d_o16 + (njobs + 1);
-    i64* d_o32 = d_is32 + (njobs + 1);
-    i64* d_is64 = d_o32 + (njobs + 1);
-    i64* d_o64 = d_is64 + (njobs + 1);
-    i64* d_is128 = d_o64 + (njobs + 1);
-    i64* d_o128 = d_is128 + (njobs + 1);
-    i64* d_bad = d_o128 + (njobs + 1);
+    GcigWs& G = ctx->gcig;
+    if ((rc = meme_buf_reserve(ctx, G.cols, GcigCols(nullptr, njobs).bytes)) || (rc = meme_buf_reserve(ctx, G.res, (size_t)njobs * sizeof(meme_gres)))) return rc;
+    const GcigCols gc(G.cols.p, njobs);
     // Several jobs per wavefront for narrow bands (k_gcig_grp; tuning "gcig_groups" = 0: every job a wavefront): per group rings for H and E, the query, the
     // target and a matrix of 16 (32) columns x the longest target, as long as a wavefront's groups stay within 24 KB (six wavefronts per CU and more)
     const int grp_qcap = (qmax + 3) & ~3, grp_tcap = (tmax + 3) & ~3;
@@ -685,29 +662,29 @@ int gcig_run(meme_ctx* ctx, i64 njobs, int qmax, int tmax, const meme_bsw_opt* o
     // (measured, profiles/r06_gcig.md: 23 % fewer instructions per job than two 64-column chunks and 6 % MORE time on the 250-bp class -- the class stays opt-in, gcig_groups = 2)
     const bool two = ctx->gcig_groups >= 2 && lds_two <= 32 * 1024;
     // the gap-free shortcut on the packed reads the seeding call left on the ctx (reads of at most 500 bases)
-    const bool fast = ctx->packed.p != nullptr && ctx->last_seed_max_len > 0;
-    const int pW = (int)((ctx->last_seed_max_len + 31) / 32) + 2, pMW = (int)((ctx->last_seed_max_len + 63) / 64);      // PackGeom of that batch (meme_seed.hip)
-    HIP_TRY(hipMemsetAsync(d_bad, 0xff, 8, ctx->stream));
-    hipLaunchKernelGGL(k_gcig_check, dim3(grid_of(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gjob*)G[0].p, (i64)njobs, (const i64*)ctx->read_off.p, d_bad);
-    hipLaunchKernelGGL(k_gcig_sizes, dim3(grid_of(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gjob*)G[0].p, (i64)njobs, (const i64*)ctx->read_off.p, fast, zcap, z16, z32, z64, two, d_zsz, d_csz,
-                       with_md ? d_msz : (i64*)nullptr, d_isdp, d_is16, d_is32, d_is64, d_is128);
-    if ((rc = meme_scan_exclusive(ctx, d_zsz, d_zoff, njobs)) || (rc = meme_scan_exclusive(ctx, d_csz, d_coff, njobs)) || (rc = meme_scan_exclusive(ctx, d_isdp, d_dpoff, njobs)) ||
-        (rc = meme_scan_exclusive(ctx, d_is16, d_o16, njobs)) || (rc = meme_scan_exclusive(ctx, d_is32, d_o32, njobs)) || (rc = meme_scan_exclusive(ctx, d_is64, d_o64, njobs)) ||
-        (rc = meme_scan_exclusive(ctx, d_is128, d_o128, njobs))) return rc;
-    hipLaunchKernelGGL(k_gcig_dplist, dim3(grid_of(njobs, 256)), dim3(256), 0, ctx->stream, (const i64*)d_isdp, (const i64*)d_dpoff, (const i64*)d_is16, (const i64*)d_o16,
-                       (const i64*)d_is32, (const i64*)d_o32, (const i64*)d_is64, (const i64*)d_o64, (const i64*)d_is128, (const i64*)d_o128, (i64)njobs, d_dplist);
-    if (with_md && (rc = meme_scan_exclusive(ctx, d_msz, d_moff, njobs))) return rc;
+    const bool fast = ctx->batch.packed.p != nullptr && ctx->batch.last_seed_max_len > 0;
+    const int pW = (int)((ctx->batch.last_seed_max_len + 31) / 32) + 2, pMW = (int)((ctx->batch.last_seed_max_len + 63) / 64);      // PackGeom of that batch (meme_seed.hip)
+    HIP_TRY(hipMemsetAsync(gc.bad, 0xff, 8, ctx->stream));
+    hipLaunchKernelGGL(k_gcig_check, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gjob*)G.jobs.p, (i64)njobs, (const i64*)ctx->batch.read_off.p, gc.bad);
+    hipLaunchKernelGGL(k_gcig_sizes, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gjob*)G.jobs.p, (i64)njobs, (const i64*)ctx->batch.read_off.p, fast, zcap, z16, z32, z64, two, gc.zsz, gc.csz,
+                       with_md ? gc.msz : (i64*)nullptr, gc.isdp, gc.is16, gc.is32, gc.is64, gc.is128);
+    if ((rc = meme_scan_exclusive(ctx, gc.zsz, gc.zoff, njobs)) || (rc = meme_scan_exclusive(ctx, gc.csz, gc.coff, njobs)) || (rc = meme_scan_exclusive(ctx, gc.isdp, gc.dpoff, njobs)) ||
+        (rc = meme_scan_exclusive(ctx, gc.is16, gc.o16, njobs)) || (rc = meme_scan_exclusive(ctx, gc.is32, gc.o32, njobs)) || (rc = meme_scan_exclusive(ctx, gc.is64, gc.o64, njobs)) ||
+        (rc = meme_scan_exclusive(ctx, gc.is128, gc.o128, njobs))) return rc;
+    hipLaunchKernelGGL(k_gcig_dplist, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const i64*)gc.isdp, (const i64*)gc.dpoff, (const i64*)gc.is16, (const i64*)gc.o16,
+                       (const i64*)gc.is32, (const i64*)gc.o32, (const i64*)gc.is64, (const i64*)gc.o64, (const i64*)gc.is128, (const i64*)gc.o128, (i64)njobs, gc.dplist);
+    if (with_md && (rc = meme_scan_exclusive(ctx, gc.msz, gc.moff, njobs))) return rc;
     i64 tz = 0, tc = 0, tm = 0, ndp = 0, n16 = 0, n32 = 0, n64 = 0, n128 = 0;
-    HIP_TRY(hipMemcpyAsync(&n128, d_o128 + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&n64, d_o64 + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&ndp, d_dpoff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&n16, d_o16 + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&n32, d_o32 + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&tz, d_zoff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&tc, d_coff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (with_md) HIP_TRY(hipMemcpyAsync(&tm, d_moff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&n128, gc.o128 + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&n64, gc.o64 + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&ndp, gc.dpoff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&n16, gc.o16 + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&n32, gc.o32 + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&tz, gc.zoff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&tc, gc.coff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (with_md) HIP_TRY(hipMemcpyAsync(&tm, gc.moff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
     i64 bad = -1;
-    HIP_TRY(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&bad, gc.bad, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (bad >= 0) {
         meme_set_error("%s: job %lld names a query span beyond the end of read it refers to", who, (long long)bad);
@@ -716,70 +693,70 @@ int gcig_run(meme_ctx* ctx, i64 njobs, int qmax, int tmax, const meme_bsw_opt* o
     {
         size_t free_b = 0, total_b = 0;
         const size_t need = (size_t)tz + (size_t)tc * 4 + (size_t)tm;
-        const size_t have = G[2].cap + G[3].cap + G[6].cap;
+        const size_t have = G.z.cap + G.cig.cap + G.md.cap;
         if (need > have && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b / 2 + have) {
             meme_set_error("%s: %lld alignments need %.1f GB of backtrack matrices, more than half of the free HBM: submit fewer at a time", who, (long long)njobs, need / 1e9);
             return MEME_E_CAPACITY;
         }
     }
-    if ((rc = meme_buf_reserve(ctx, G[2], (size_t)tz + 64)) || (rc = meme_buf_reserve(ctx, G[3], (size_t)(tc + 1) * 4))) return rc;
-    if (with_md && ((rc = meme_buf_reserve(ctx, G[6], (size_t)tm + 64)) || (rc = meme_buf_reserve(ctx, G[7], (size_t)njobs * 8 + 64)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, G.z, (size_t)tz + 64)) || (rc = meme_buf_reserve(ctx, G.cig, (size_t)(tc + 1) * 4))) return rc;
+    if (with_md && ((rc = meme_buf_reserve(ctx, G.md, (size_t)tm + 64)) || (rc = meme_buf_reserve(ctx, G.nm, (size_t)njobs * 8 + 64)))) return rc;
     GcigArgs A;
-    A.jobs = (const meme_gjob*)G[0].p; A.njobs = njobs; A.reads = (const uint8_t*)ctx->reads.p; A.read_off = (const i64*)ctx->read_off.p; A.pac = ctx->idx.pac;
-    A.o = *opt; A.zoff = d_zoff; A.z = (uint8_t*)G[2].p; A.coff = d_coff; A.cig = (uint32_t*)G[3].p; A.res = (meme_gres*)G[4].p;
-    A.mdoff = d_moff; A.md = with_md ? (char*)G[6].p : nullptr;
-    A.nm = with_md ? (int32_t*)G[7].p : nullptr; A.mdlen = with_md ? (int32_t*)G[7].p + njobs : nullptr;
-    A.zcap = zcap; A.dp_list = nullptr; A.packed = (const u64*)ctx->packed.p; A.pW = pW; A.pMW = pMW; A.pstride = 2 * pW + 2 * pMW + 1;
+    A.jobs = (const meme_gjob*)G.jobs.p; A.njobs = njobs; A.reads = (const uint8_t*)ctx->batch.reads.p; A.read_off = (const i64*)ctx->batch.read_off.p; A.pac = ctx->idx.pac;
+    A.o = *opt; A.zoff = gc.zoff; A.z = (uint8_t*)G.z.p; A.coff = gc.coff; A.cig = (uint32_t*)G.cig.p; A.res = (meme_gres*)G.res.p;
+    A.mdoff = gc.moff; A.md = with_md ? (char*)G.md.p : nullptr;
+    A.nm = with_md ? (int32_t*)G.nm.p : nullptr; A.mdlen = with_md ? (int32_t*)G.nm.p + njobs : nullptr;
+    A.zcap = zcap; A.dp_list = nullptr; A.packed = (const u64*)ctx->batch.packed.p; A.pW = pW; A.pMW = pMW; A.pstride = 2 * pW + 2 * pMW + 1;
     A.list_first = 0; A.grp_qcap = grp_qcap; A.grp_tcap = grp_tcap; A.grp_z = 0;
-    if (ndp + n16 + n32 + n64 + n128 < njobs) hipLaunchKernelGGL(k_gcig_nogap, dim3(grid_of(njobs, 256)), dim3(256), 0, ctx->stream, A);
+    if (ndp + n16 + n32 + n64 + n128 < njobs) hipLaunchKernelGGL(k_gcig_nogap, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, A);
     if (n16 > 0) {
         GcigArgs D = A;
-        D.dp_list = d_dplist; D.njobs = n16; D.list_first = 0; D.grp_z = z16;
+        D.dp_list = gc.dplist; D.njobs = n16; D.list_first = 0; D.grp_z = z16;
         hipLaunchKernelGGL(k_gcig_grp<16>, dim3((unsigned)((n16 + 3) / 4)), dim3(64), grp_lds(16, z16), ctx->stream, D);
     }
     if (n32 > 0) {
         GcigArgs D = A;
-        D.dp_list = d_dplist; D.njobs = n32; D.list_first = n16; D.grp_z = z32;
+        D.dp_list = gc.dplist; D.njobs = n32; D.list_first = n16; D.grp_z = z32;
         hipLaunchKernelGGL(k_gcig_grp<32>, dim3((unsigned)((n32 + 1) / 2)), dim3(64), grp_lds(32, z32), ctx->stream, D);
     }
     if (n64 > 0) {
         GcigArgs D = A;
-        D.dp_list = d_dplist; D.njobs = n64; D.list_first = n16 + n32; D.grp_z = z64;
+        D.dp_list = gc.dplist; D.njobs = n64; D.list_first = n16 + n32; D.grp_z = z64;
         hipLaunchKernelGGL(k_gcig_grp<64>, dim3((unsigned)n64), dim3(64), grp_lds(64, z64), ctx->stream, D);
     }
     if (n128 > 0) {
         GcigArgs D = A;
-        D.dp_list = d_dplist; D.njobs = n128; D.list_first = n16 + n32 + n64;
+        D.dp_list = gc.dplist; D.njobs = n128; D.list_first = n16 + n32 + n64;
         hipLaunchKernelGGL(k_gcig_t<true>, dim3((unsigned)n128), dim3(64), lds_two, ctx->stream, D);
     }
     ctx->tm.gcig_class_jobs[5] = n128;
     ctx->tm.gcig_class_jobs[0] = n16; ctx->tm.gcig_class_jobs[1] = n32; ctx->tm.gcig_class_jobs[2] = ndp; ctx->tm.gcig_class_jobs[3] = njobs - ndp - n16 - n32 - n64 - n128; ctx->tm.gcig_class_jobs[4] = n64;
     if (ndp > 0) {
         GcigArgs D = A;
-        D.dp_list = d_dplist; D.njobs = ndp; D.list_first = n16 + n32 + n64 + n128;
+        D.dp_list = gc.dplist; D.njobs = ndp; D.list_first = n16 + n32 + n64 + n128;
         const size_t lds = lds_base + (size_t)zcap;
         if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_gcig_t<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_gcig_t<false>, dim3((unsigned)ndp), dim3(64), lds, ctx->stream, D);
     }
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_gcig_ncig, dim3(grid_of(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gres*)G[4].p, (i64)njobs, d_ncig);
-    if ((rc = meme_scan_exclusive(ctx, d_ncig, d_ooff, njobs))) return rc;
+    hipLaunchKernelGGL(k_gcig_ncig, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gres*)G.res.p, (i64)njobs, gc.ncig);
+    if ((rc = meme_scan_exclusive(ctx, gc.ncig, gc.ooff, njobs))) return rc;
     if (with_md) {
-        hipLaunchKernelGGL(k_md_sizes, dim3(grid_of(njobs, 256)), dim3(256), 0, ctx->stream, (const int32_t*)A.mdlen, (i64)njobs, d_psz);
-        if ((rc = meme_scan_exclusive(ctx, d_psz, d_poff, njobs))) return rc;
+        hipLaunchKernelGGL(k_md_sizes, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const int32_t*)A.mdlen, (i64)njobs, gc.psz);
+        if ((rc = meme_scan_exclusive(ctx, gc.psz, gc.poff, njobs))) return rc;
     }
     i64 tops = 0, tmd = 0;
-    HIP_TRY(hipMemcpyAsync(&tops, d_ooff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (with_md) HIP_TRY(hipMemcpyAsync(&tmd, d_poff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&tops, gc.ooff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (with_md) HIP_TRY(hipMemcpyAsync(&tmd, gc.poff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if ((rc = meme_buf_reserve(ctx, G[5], (size_t)(tops + 1) * 4))) return rc;
-    hipLaunchKernelGGL(k_gcig_pack, dim3(grid_of(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gres*)G[4].p, (const i64*)d_coff, (const uint32_t*)G[3].p,
-                       (const i64*)d_ooff, (i64)njobs, (uint32_t*)G[5].p);
-    hipLaunchKernelGGL(k_gcig_fix, dim3(grid_of(njobs, 256)), dim3(256), 0, ctx->stream, (meme_gres*)G[4].p, (const i64*)d_ooff, (i64)njobs);
+    if ((rc = meme_buf_reserve(ctx, G.ops, (size_t)(tops + 1) * 4))) return rc;
+    hipLaunchKernelGGL(k_gcig_pack, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gres*)G.res.p, (const i64*)gc.coff, (const uint32_t*)G.cig.p,
+                       (const i64*)gc.ooff, (i64)njobs, (uint32_t*)G.ops.p);
+    hipLaunchKernelGGL(k_gcig_fix, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (meme_gres*)G.res.p, (const i64*)gc.ooff, (i64)njobs);
     if (with_md) {
-        if ((rc = meme_buf_reserve(ctx, G[8], (size_t)tmd + 64)) || (rc = meme_buf_reserve(ctx, G[10], (size_t)njobs * sizeof(meme_cres)))) return rc;
-        hipLaunchKernelGGL(k_md_pack, dim3(grid_of(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gres*)G[4].p, (const int32_t*)A.nm, (const int32_t*)A.mdlen,
-                           (const i64*)d_moff, (const char*)G[6].p, (const i64*)d_poff, (i64)njobs, (char*)G[8].p, (meme_cres*)G[10].p);
+        if ((rc = meme_buf_reserve(ctx, G.md_packed, (size_t)tmd + 64)) || (rc = meme_buf_reserve(ctx, G.cres, (size_t)njobs * sizeof(meme_cres)))) return rc;
+        hipLaunchKernelGGL(k_md_pack, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gres*)G.res.p, (const int32_t*)A.nm, (const int32_t*)A.mdlen,
+                           (const i64*)gc.moff, (const char*)G.md.p, (const i64*)gc.poff, (i64)njobs, (char*)G.md_packed.p, (meme_cres*)G.cres.p);
     }
     HIP_TRY(hipGetLastError());
     out->tops = tops; out->tmd = tmd;
@@ -790,11 +767,11 @@ int gcig_preamble(meme_ctx* ctx, const void* jobs, int64_t njobs, const meme_bsw
     if (!ctx || !jobs || njobs < 0 || !opt || !out) { meme_set_error("%s: null argument", who); return MEME_E_ARG; }
     HIP_TRY(hipSetDevice(ctx->device));
     if (njobs == 0) return MEME_OK;
-    const i64 nreads = ctx->last_seed_reads;
-    if (nreads <= 0 || !ctx->reads.p || !ctx->read_off.p || !ctx->idx.pac || !ctx->reads_resident) { meme_set_error("%s: no seeded batch on this ctx (the jobs name its reads)", who); return MEME_E_STATE; }
+    const i64 nreads = ctx->batch.last_seed_reads;
+    if (nreads <= 0 || !ctx->batch.reads.p || !ctx->batch.read_off.p || !ctx->idx.pac || !ctx->batch.reads_resident) { meme_set_error("%s: no seeded batch on this ctx (the jobs name its reads)", who); return MEME_E_STATE; }
     if (opt->e_del < 1 || opt->e_ins < 1) { meme_set_error("%s: gap extension penalties must be positive", who); return MEME_E_ARG; }
     if (ctx->max_batch > 0 && njobs > ctx->max_batch) { meme_set_error("%s: %lld jobs exceed the ctx's max_batch of %lld", who, (long long)njobs, (long long)ctx->max_batch); return MEME_E_CAPACITY; }
-    for (int i = 0; i < 2; ++i) if (!ctx->ev_gcig[i]) HIP_TRY(hipEventCreate(&ctx->ev_gcig[i]));
+    for (int i = 0; i < 2; ++i) if (!ctx->gcig.ev[i]) HIP_TRY(hipEventCreate(&ctx->gcig.ev[i]));
     return MEME_OK;
 }
 
@@ -806,7 +783,7 @@ extern "C" int meme_global_batch_host(meme_ctx* ctx, const meme_gjob* jobs, int6
     if ((rc = gcig_preamble(ctx, jobs, njobs, opt, out, who))) return rc;
     memset(out, 0, sizeof(*out));
     if (njobs == 0) return MEME_OK;
-    const i64 nreads = ctx->last_seed_reads;
+    const i64 nreads = ctx->batch.last_seed_reads;
     int qmax = 0, tmax = 0;
     for (i64 k = 0; k < njobs; ++k) {
         const meme_gjob& J = jobs[k];
@@ -820,21 +797,20 @@ extern "C" int meme_global_batch_host(meme_ctx* ctx, const meme_gjob* jobs, int6
         qmax = J.qlen > qmax ? J.qlen : qmax;
         tmax = J.tlen > tmax ? J.tlen : tmax;
     }
-    DevBuf* G = ctx->gcig;
-    if ((rc = meme_buf_reserve(ctx, G[0], (size_t)njobs * sizeof(meme_gjob)))) return rc;
-    HIP_TRY(hipMemcpyAsync(G[0].p, jobs, (size_t)njobs * sizeof(meme_gjob), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_gcig[0], ctx->stream));
+    GcigWs& G = ctx->gcig;
+    if ((rc = meme_buf_reserve(ctx, G.jobs, (size_t)njobs * sizeof(meme_gjob)))) return rc;
+    HIP_TRY(hipMemcpyAsync(G.jobs.p, jobs, (size_t)njobs * sizeof(meme_gjob), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->gcig.ev[0], ctx->stream));
     GcigRun R;
     if ((rc = gcig_run(ctx, njobs, qmax, tmax, opt, false, who, &R))) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev_gcig[1], ctx->stream));
-    meme_ctx::HostBuf* Hb = ctx->h_gcig;
-    if ((rc = meme_hostbuf_reserve(ctx, Hb[0], (size_t)njobs * sizeof(meme_gres))) || (rc = meme_hostbuf_reserve(ctx, Hb[1], (size_t)(R.tops + 1) * 4))) return rc;
-    HIP_TRY(hipMemcpyAsync(Hb[0].p, G[4].p, (size_t)njobs * sizeof(meme_gres), hipMemcpyDeviceToHost, ctx->stream));
-    if (R.tops) HIP_TRY(hipMemcpyAsync(Hb[1].p, G[5].p, (size_t)R.tops * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->gcig.ev[1], ctx->stream));
+    if ((rc = meme_hostbuf_reserve(ctx, G.h_res, (size_t)njobs * sizeof(meme_gres))) || (rc = meme_hostbuf_reserve(ctx, G.h_ops, (size_t)(R.tops + 1) * 4))) return rc;
+    HIP_TRY(hipMemcpyAsync(G.h_res.p, G.res.p, (size_t)njobs * sizeof(meme_gres), hipMemcpyDeviceToHost, ctx->stream));
+    if (R.tops) HIP_TRY(hipMemcpyAsync(G.h_ops.p, G.ops.p, (size_t)R.tops * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_gcig[0], ctx->ev_gcig[1]));
-    out->njobs = njobs; out->res = (const meme_gres*)Hb[0].p; out->cigars = (const uint32_t*)Hb[1].p; out->total_ops = R.tops; out->kernel_ms = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->gcig.ev[0], ctx->gcig.ev[1]));
+    out->njobs = njobs; out->res = (const meme_gres*)G.h_res.p; out->cigars = (const uint32_t*)G.h_ops.p; out->total_ops = R.tops; out->kernel_ms = ms;
     return MEME_OK;
 }
 
@@ -844,7 +820,7 @@ extern "C" int meme_gen_cigar_batch_host(meme_ctx* ctx, const meme_cjob* jobs, i
     if ((rc = gcig_preamble(ctx, jobs, njobs, opt, out, who))) return rc;
     memset(out, 0, sizeof(*out));
     if (njobs == 0) return MEME_OK;
-    const i64 nreads = ctx->last_seed_reads, l_pac = ctx->idx.n >> 1;
+    const i64 nreads = ctx->batch.last_seed_reads, l_pac = ctx->idx.n >> 1;
     int qmax = 0, tmax = 0;
     for (i64 k = 0; k < njobs; ++k) {
         const meme_cjob& J = jobs[k];
@@ -857,24 +833,23 @@ extern "C" int meme_gen_cigar_batch_host(meme_ctx* ctx, const meme_cjob* jobs, i
         qmax = J.qlen > qmax ? J.qlen : qmax;
         tmax = J.tlen > tmax ? J.tlen : tmax;
     }
-    DevBuf* G = ctx->gcig;
-    if ((rc = meme_buf_reserve(ctx, G[0], (size_t)njobs * sizeof(meme_gjob))) || (rc = meme_buf_reserve(ctx, G[9], (size_t)njobs * sizeof(meme_cjob)))) return rc;
-    HIP_TRY(hipMemcpyAsync(G[9].p, jobs, (size_t)njobs * sizeof(meme_cjob), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_gcig[0], ctx->stream));
-    hipLaunchKernelGGL(k_cjob_prep, dim3(grid_of(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_cjob*)G[9].p, (i64)njobs, l_pac, *opt, (meme_gjob*)G[0].p);
+    GcigWs& G = ctx->gcig;
+    if ((rc = meme_buf_reserve(ctx, G.jobs, (size_t)njobs * sizeof(meme_gjob))) || (rc = meme_buf_reserve(ctx, G.cjobs, (size_t)njobs * sizeof(meme_cjob)))) return rc;
+    HIP_TRY(hipMemcpyAsync(G.cjobs.p, jobs, (size_t)njobs * sizeof(meme_cjob), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->gcig.ev[0], ctx->stream));
+    hipLaunchKernelGGL(k_cjob_prep, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_cjob*)G.cjobs.p, (i64)njobs, l_pac, *opt, (meme_gjob*)G.jobs.p);
     GcigRun R;
     if ((rc = gcig_run(ctx, njobs, qmax, tmax, opt, true, who, &R))) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev_gcig[1], ctx->stream));
-    meme_ctx::HostBuf* Hb = ctx->h_gcig;
-    if ((rc = meme_hostbuf_reserve(ctx, Hb[0], (size_t)njobs * sizeof(meme_cres))) || (rc = meme_hostbuf_reserve(ctx, Hb[1], (size_t)(R.tops + 1) * 4)) ||
-        (rc = meme_hostbuf_reserve(ctx, Hb[2], (size_t)R.tmd + 64))) return rc;
-    HIP_TRY(hipMemcpyAsync(Hb[0].p, G[10].p, (size_t)njobs * sizeof(meme_cres), hipMemcpyDeviceToHost, ctx->stream));
-    if (R.tops) HIP_TRY(hipMemcpyAsync(Hb[1].p, G[5].p, (size_t)R.tops * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (R.tmd) HIP_TRY(hipMemcpyAsync(Hb[2].p, G[8].p, (size_t)R.tmd, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->gcig.ev[1], ctx->stream));
+    if ((rc = meme_hostbuf_reserve(ctx, G.h_res, (size_t)njobs * sizeof(meme_cres))) || (rc = meme_hostbuf_reserve(ctx, G.h_ops, (size_t)(R.tops + 1) * 4)) ||
+        (rc = meme_hostbuf_reserve(ctx, G.h_md, (size_t)R.tmd + 64))) return rc;
+    HIP_TRY(hipMemcpyAsync(G.h_res.p, G.cres.p, (size_t)njobs * sizeof(meme_cres), hipMemcpyDeviceToHost, ctx->stream));
+    if (R.tops) HIP_TRY(hipMemcpyAsync(G.h_ops.p, G.ops.p, (size_t)R.tops * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (R.tmd) HIP_TRY(hipMemcpyAsync(G.h_md.p, G.md_packed.p, (size_t)R.tmd, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_gcig[0], ctx->ev_gcig[1]));
-    out->njobs = njobs; out->res = (const meme_cres*)Hb[0].p; out->cigars = (const uint32_t*)Hb[1].p; out->total_ops = R.tops; out->md = (const char*)Hb[2].p; out->md_bytes = R.tmd;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->gcig.ev[0], ctx->gcig.ev[1]));
+    out->njobs = njobs; out->res = (const meme_cres*)G.h_res.p; out->cigars = (const uint32_t*)G.h_ops.p; out->total_ops = R.tops; out->md = (const char*)G.h_md.p; out->md_bytes = R.tmd;
     out->kernel_ms = ms;
     return MEME_OK;
 }

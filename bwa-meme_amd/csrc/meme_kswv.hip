@@ -289,7 +289,7 @@ int meme_seedsw_launch(meme_ctx* ctx, const meme_seedsw_job* d_jobs, const unsig
     memset(&A, 0, sizeof(A));
     A.a = o->a; A.b = o->b; A.o_del = o->o_del; A.e_del = o->e_del; A.o_ins = o->o_ins; A.e_ins = o->e_ins;
     const size_t lds = (size_t)(MEME_SEEDSW_MAX + 2) * 256;
-    hipLaunchKernelGGL(k_seedsw, dim3((unsigned)((max_jobs + 63) / 64)), dim3(64), lds, ctx->stream, d_jobs, d_njobs, ctx->idx.pac, ctx->idx.n >> 1, (const uint8_t*)ctx->reads.p, d_sc, A);
+    hipLaunchKernelGGL(k_seedsw, dim3((unsigned)((max_jobs + 63) / 64)), dim3(64), lds, ctx->stream, d_jobs, d_njobs, ctx->idx.pac, ctx->idx.n >> 1, (const uint8_t*)ctx->batch.reads.p, d_sc, A);
     HIP_TRY(hipGetLastError());
     return MEME_OK;
 }
@@ -353,26 +353,26 @@ int meme_kswv_run(meme_ctx* ctx, const meme_kswv_job* jobs, int64_t njobs, const
         p = e;
     }
     int rc;
-    DevBuf* K = ctx->kswv;      // 0 jobs, 1 order, 2 ref bytes, 3 query bytes, 4 results, 5 row maxima, 6 wavefront offsets
-    if ((rc = meme_buf_reserve(ctx, K[0], (size_t)n * sizeof(meme_kswv_job))) || (rc = meme_buf_reserve(ctx, K[1], (size_t)n * 4)) ||
-        (rc = meme_buf_reserve(ctx, K[2], (size_t)ref_bytes + 64)) || (rc = meme_buf_reserve(ctx, K[3], (size_t)qer_bytes + 64)) ||
-        (rc = meme_buf_reserve(ctx, K[4], (size_t)n * sizeof(meme_kswr))) || (rc = meme_buf_reserve(ctx, K[5], (size_t)rows_total * 128 + 256)) ||
-        (rc = meme_buf_reserve(ctx, K[6], rm_off.size() * 8 + 8))) return rc;
-    hipEvent_t* ev = ctx->ev_kswv;
+    KswvWs& K = ctx->kswv;
+    if ((rc = meme_buf_reserve(ctx, K.jobs, (size_t)n * sizeof(meme_kswv_job))) || (rc = meme_buf_reserve(ctx, K.order, (size_t)n * 4)) ||
+        (rc = meme_buf_reserve(ctx, K.ref, (size_t)ref_bytes + 64)) || (rc = meme_buf_reserve(ctx, K.qer, (size_t)qer_bytes + 64)) ||
+        (rc = meme_buf_reserve(ctx, K.res, (size_t)n * sizeof(meme_kswr))) || (rc = meme_buf_reserve(ctx, K.rowmax, (size_t)rows_total * 128 + 256)) ||
+        (rc = meme_buf_reserve(ctx, K.rm_off, rm_off.size() * 8 + 8))) return rc;
+    Events<2>& ev = K.ev;
     for (int i = 0; i < 2; ++i) if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
-    if (!staged) HIP_TRY(hipMemcpyAsync(K[0].p, jobs, (size_t)n * sizeof(meme_kswv_job), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(K[1].p, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (!staged) HIP_TRY(hipMemcpyAsync(K.jobs.p, jobs, (size_t)n * sizeof(meme_kswv_job), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(K.order.p, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     if (!staged) {                                     // (staged: the caller's kernels have written the jobs and both sequence buffers where they are read)
-        HIP_TRY(hipMemcpyAsync(K[2].p, ref, (size_t)ref_bytes, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(K[3].p, qer, (size_t)qer_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(K.ref.p, ref, (size_t)ref_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(K.qer.p, qer, (size_t)qer_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    HIP_TRY(hipMemcpyAsync(K[6].p, rm_off.data(), rm_off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(K.rm_off.p, rm_off.data(), rm_off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipEventRecord(ev[0], ctx->stream));
     for (const Launch& L : launches) {
         KswvArgs A;
-        A.jobs = (const meme_kswv_job*)K[0].p; A.order = (const int*)K[1].p; A.first = L.first; A.count = L.count;
-        A.ref = (const uint8_t*)K[2].p; A.qer = (const uint8_t*)K[3].p; A.out = (meme_kswr*)K[4].p;
-        A.rowmax = (unsigned short*)K[5].p; A.rm_off = (const i64*)K[6].p + L.w0;
+        A.jobs = (const meme_kswv_job*)K.jobs.p; A.order = (const int*)K.order.p; A.first = L.first; A.count = L.count;
+        A.ref = (const uint8_t*)K.ref.p; A.qer = (const uint8_t*)K.qer.p; A.out = (meme_kswr*)K.res.p;
+        A.rowmax = (unsigned short*)K.rowmax.p; A.rm_off = (const i64*)K.rm_off.p + L.w0;
         A.a = opt->a; A.b = opt->b; A.o_del = opt->o_del; A.e_del = opt->e_del; A.o_ins = opt->o_ins; A.e_ins = opt->e_ins;
         const size_t lds = (size_t)(L.qmax + 2) * 256;
         if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_kswv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -380,12 +380,11 @@ int meme_kswv_run(meme_ctx* ctx, const meme_kswv_job* jobs, int64_t njobs, const
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev[1], ctx->stream));
-    meme_ctx::HostBuf& Hb = ctx->h_kswv;
-    if ((rc = meme_hostbuf_reserve(ctx, Hb, (size_t)n * sizeof(meme_kswr)))) return rc;
-    HIP_TRY(hipMemcpyAsync(Hb.p, K[4].p, (size_t)n * sizeof(meme_kswr), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = meme_hostbuf_reserve(ctx, K.h_res, (size_t)n * sizeof(meme_kswr)))) return rc;
+    HIP_TRY(hipMemcpyAsync(K.h_res.p, K.res.p, (size_t)n * sizeof(meme_kswr), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    out->njobs = njobs; out->res = (const meme_kswr*)Hb.p; out->kernel_ms = ms;
+    out->njobs = njobs; out->res = (const meme_kswr*)K.h_res.p; out->kernel_ms = ms;
     return MEME_OK;
 }

@@ -148,8 +148,6 @@ __global__ void k_mate_batch_offs(const i64* __restrict__ offQ, const i64* __res
     job_off[b] = offJ[r];
 }
 
-unsigned blocks_for(i64 items, int per) { i64 b = (items + per - 1) / per; const i64 cap = 256 * 32; return (unsigned)(b < cap ? (b < 1 ? 1 : b) : cap); }
-
 }  // namespace
 
 extern "C" int meme_matesw_batch_host(meme_ctx* ctx, meme_ctx* reads_of, const meme_mate_reg* regs, const int64_t* reg_off, int64_t first_read, int64_t nreads, const meme_pestat* pes,
@@ -163,9 +161,9 @@ extern "C" int meme_matesw_batch_host(meme_ctx* ctx, meme_ctx* reads_of, const m
     // on the ctx that seeded the batch: the bases are only read, device pointers are valid across the ctxs of a device)
     meme_ctx* const rc_ = reads_of ? reads_of : ctx;
     if (rc_->device != ctx->device) { meme_set_error("%s: the ctx that holds the reads is on another device", who); return MEME_E_ARG; }
-    if (first_read < 0 || first_read + nreads > rc_->last_seed_reads || !rc_->reads_resident || !rc_->reads.p || !rc_->read_off.p) {
+    if (first_read < 0 || first_read + nreads > rc_->batch.last_seed_reads || !rc_->batch.reads_resident || !rc_->batch.reads.p || !rc_->batch.read_off.p) {
         meme_set_error("%s: reads [%lld, %lld) must lie in the batch resident on the ctx (a seeding call stages it; it holds %lld)", who, (long long)first_read, (long long)(first_read + nreads),
-                       (long long)rc_->last_seed_reads);
+                       (long long)rc_->batch.last_seed_reads);
         return MEME_E_STATE;
     }
     if ((nreads & 1) || (first_read & 1)) { meme_set_error("%s: an odd number of reads (or an odd first read) is not a set of pairs", who); return MEME_E_ARG; }
@@ -173,63 +171,50 @@ extern "C" int meme_matesw_batch_host(meme_ctx* ctx, meme_ctx* reads_of, const m
     if (opt->batch_reads < 2 || (opt->batch_reads & 1) || opt->max_matesw < 0 || opt->a < 1 || opt->min_seed_len < 1) { meme_set_error("%s: bad options", who); return MEME_E_ARG; }
     const i64 nrec = reg_off[nreads];
     if (reg_off[0] != 0 || nrec < 0 || (nrec > 0 && !regs)) { meme_set_error("%s: bad record offsets", who); return MEME_E_ARG; }
-    for (int i = 0; i < n_contigs; ++i)
-        if (contigs[i].len < 1 || contigs[i].offset < 0 || contigs[i].offset + contigs[i].len > l_pac || (i > 0 && contigs[i].offset < contigs[i - 1].offset + contigs[i - 1].len)) {
-            meme_set_error("%s: contig %d is not a valid reference sequence", who, i);
-            return MEME_E_ARG;
-        }
     const i64 n = nreads, nb = (n + opt->batch_reads - 1) / opt->batch_reads;
     int rc;
-    DevBuf* M = ctx->mate;       // 0 records, 1 record offsets, 2 contig table, 3 counts + scans (8 x (n + 1)), 4 gar, 5 aux, 6 batch offsets
-    if ((rc = meme_buf_reserve(ctx, M[0], (size_t)(nrec + 1) * sizeof(meme_mate_reg))) || (rc = meme_buf_reserve(ctx, M[1], (size_t)(n + 1) * 8)) ||
-        (rc = meme_buf_reserve(ctx, M[2], (size_t)n_contigs * 12 + 64)) || (rc = meme_buf_reserve(ctx, M[3], (size_t)(n + 1) * 8 * 8)) ||
-        (rc = meme_buf_reserve(ctx, M[6], (size_t)(nb + 1) * 16))) return rc;
-    std::vector<unsigned char> tab((size_t)n_contigs * 12 + 64, 0);
-    {
-        i64* t_off = (i64*)tab.data();
-        int* t_len = (int*)(tab.data() + (size_t)n_contigs * 8);
-        for (int i = 0; i < n_contigs; ++i) { t_off[i] = contigs[i].offset; t_len[i] = contigs[i].len; }
-    }
-    hipEvent_t* ev = ctx->ev_kswv;
+    MateWs& M = ctx->mate;
+    std::vector<unsigned char> tab;
+    ContigTab ct(nullptr, 0, false);
+    if ((rc = meme_stage_contigs(ctx, M.contigs, tab, contigs, n_contigs, l_pac, false, "meme_matesw_batch_host: ", &ct))) return rc;
+    if ((rc = meme_buf_reserve(ctx, M.regs, (size_t)(nrec + 1) * sizeof(meme_mate_reg))) || (rc = meme_buf_reserve(ctx, M.reg_off, (size_t)(n + 1) * 8)) ||
+        (rc = meme_buf_reserve(ctx, M.counts, MateCounts(nullptr, n).bytes)) || (rc = meme_buf_reserve(ctx, M.batch_off, (size_t)(nb + 1) * 16))) return rc;
+    Events<2>& ev = ctx->kswv.ev;
     for (int i = 0; i < 2; ++i) if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
-    if (nrec) HIP_TRY(hipMemcpyAsync(M[0].p, regs, (size_t)nrec * sizeof(meme_mate_reg), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(M[1].p, reg_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(M[2].p, tab.data(), tab.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (nrec) HIP_TRY(hipMemcpyAsync(M.regs.p, regs, (size_t)nrec * sizeof(meme_mate_reg), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(M.reg_off.p, reg_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     MateArgs A;
     memset(&A, 0, sizeof(A));
-    A.regs = (const meme_mate_reg*)M[0].p; A.reg_off = (const i64*)M[1].p; A.n = n; A.first = first_read; A.read_off = (const i64*)rc_->read_off.p;
+    A.regs = (const meme_mate_reg*)M.regs.p; A.reg_off = (const i64*)M.reg_off.p; A.n = n; A.first = first_read; A.read_off = (const i64*)rc_->batch.read_off.p;
     for (int o = 0; o < 4; ++o) A.pes[o] = pes[o];
-    A.l_pac = l_pac; A.contig_off = (const i64*)M[2].p; A.contig_len = (const int*)((unsigned char*)M[2].p + (size_t)n_contigs * 8); A.n_contigs = n_contigs;
+    A.l_pac = l_pac; A.contig_off = ct.off; A.contig_len = ct.len; A.n_contigs = n_contigs;
     A.a = opt->a; A.pen_unpaired = opt->pen_unpaired; A.max_matesw = opt->max_matesw; A.min_seed_len = opt->min_seed_len; A.batch_reads = opt->batch_reads;
-    i64* C = (i64*)M[3].p;
-    A.cntQ = C; A.cntJ = C + (n + 1); A.cntR = C + 2 * (n + 1); A.cntY = C + 3 * (n + 1);
-    i64* O = C + 4 * (n + 1);
-    A.offQ = O; A.offJ = O + (n + 1); A.offR = O + 2 * (n + 1); A.offY = O + 3 * (n + 1);
+    const MateCounts mc(M.counts.p, n);
+    A.cntQ = mc.cntQ; A.cntJ = mc.cntJ; A.cntR = mc.cntR; A.cntY = mc.cntY; A.offQ = mc.offQ; A.offJ = mc.offJ; A.offR = mc.offR; A.offY = mc.offY;
     HIP_TRY(hipEventRecord(ev[0], ctx->stream));
-    hipLaunchKernelGGL((k_mate_plan<false>), dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, A);
-    for (int k = 0; k < 4; ++k) if ((rc = meme_scan_exclusive(ctx, C + k * (n + 1), O + k * (n + 1), n))) return rc;
+    hipLaunchKernelGGL((k_mate_plan<false>), dim3(grid_blocks(n, 256, 256 * 32)), dim3(256), 0, ctx->stream, A);
+    for (int k = 0; k < 4; ++k) if ((rc = meme_scan_exclusive(ctx, mc.cntQ + k * (n + 1), mc.offQ + k * (n + 1), n))) return rc;
     i64 tot[4] = {0, 0, 0, 0};
-    for (int k = 0; k < 4; ++k) HIP_TRY(hipMemcpyAsync(&tot[k], O + k * (n + 1) + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    for (int k = 0; k < 4; ++k) HIP_TRY(hipMemcpyAsync(&tot[k], mc.offQ + k * (n + 1) + n, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));                                       // (also: `tab` is a local)
     const i64 nq = tot[0], nj = tot[1], ref_bytes = tot[2], qer_bytes = tot[3];
     if (nj > 0x7fffffff / 2 || 4 * nq > 0x7fffffff) { meme_set_error("%s: too many jobs in one call", who); return MEME_E_CAPACITY; }
-    DevBuf* K = ctx->kswv;        // (k_kswv's buffers: 0 jobs, 2 window bases, 3 query bases -- written here, read there)
-    meme_ctx::HostBuf* H = ctx->h_mate;      // 0 gar, 1 batch offsets (gar, jobs), 2 jobs
-    if ((rc = meme_buf_reserve(ctx, M[4], (size_t)(4 * nq + 4) * 4)) || (rc = meme_buf_reserve(ctx, M[5], (size_t)(nj + 1) * sizeof(MateAux))) ||
-        (rc = meme_buf_reserve(ctx, K[0], (size_t)(nj + 1) * sizeof(meme_kswv_job))) || (rc = meme_buf_reserve(ctx, K[2], (size_t)ref_bytes + 64)) ||
-        (rc = meme_buf_reserve(ctx, K[3], (size_t)qer_bytes + 64)) || (rc = meme_hostbuf_reserve(ctx, H[0], (size_t)(4 * nq + 4) * 4)) ||
-        (rc = meme_hostbuf_reserve(ctx, H[1], (size_t)(nb + 1) * 16)) || (rc = meme_hostbuf_reserve(ctx, H[2], (size_t)(nj + 1) * sizeof(meme_kswv_job)))) return rc;
-    A.gar = (int32_t*)M[4].p; A.jobs = (meme_kswv_job*)K[0].p; A.aux = (MateAux*)M[5].p;
-    hipLaunchKernelGGL((k_mate_plan<true>), dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, A);
-    if (nj) hipLaunchKernelGGL(k_mate_seq, dim3((unsigned)((nj + 3) / 4)), dim3(256), 0, ctx->stream, (const meme_kswv_job*)K[0].p, (const MateAux*)M[5].p, nj, ctx->idx.pac,
-                               (const uint8_t*)rc_->reads.p, (const i64*)rc_->read_off.p, (uint8_t*)K[2].p, (uint8_t*)K[3].p);
-    i64* d_goff = (i64*)M[6].p;
+    KswvWs& K = ctx->kswv;        // (k_kswv's jobs and sequences: written here, read there)
+    if ((rc = meme_buf_reserve(ctx, M.gar, (size_t)(4 * nq + 4) * 4)) || (rc = meme_buf_reserve(ctx, M.aux, (size_t)(nj + 1) * sizeof(MateAux))) ||
+        (rc = meme_buf_reserve(ctx, K.jobs, (size_t)(nj + 1) * sizeof(meme_kswv_job))) || (rc = meme_buf_reserve(ctx, K.ref, (size_t)ref_bytes + 64)) ||
+        (rc = meme_buf_reserve(ctx, K.qer, (size_t)qer_bytes + 64)) || (rc = meme_hostbuf_reserve(ctx, M.h_gar, (size_t)(4 * nq + 4) * 4)) ||
+        (rc = meme_hostbuf_reserve(ctx, M.h_batch_off, (size_t)(nb + 1) * 16)) || (rc = meme_hostbuf_reserve(ctx, M.h_jobs, (size_t)(nj + 1) * sizeof(meme_kswv_job)))) return rc;
+    A.gar = (int32_t*)M.gar.p; A.jobs = (meme_kswv_job*)K.jobs.p; A.aux = (MateAux*)M.aux.p;
+    hipLaunchKernelGGL((k_mate_plan<true>), dim3(grid_blocks(n, 256, 256 * 32)), dim3(256), 0, ctx->stream, A);
+    if (nj) hipLaunchKernelGGL(k_mate_seq, dim3((unsigned)((nj + 3) / 4)), dim3(256), 0, ctx->stream, (const meme_kswv_job*)K.jobs.p, (const MateAux*)M.aux.p, nj, ctx->idx.pac,
+                               (const uint8_t*)rc_->batch.reads.p, (const i64*)rc_->batch.read_off.p, (uint8_t*)K.ref.p, (uint8_t*)K.qer.p);
+    i64* d_goff = (i64*)M.batch_off.p;
     i64* d_joff = d_goff + (nb + 1);
     hipLaunchKernelGGL(k_mate_batch_offs, dim3((unsigned)((nb + 256) / 256)), dim3(256), 0, ctx->stream, A.offQ, A.offJ, n, opt->batch_reads, nb, d_goff, d_joff);
     HIP_TRY(hipGetLastError());
-    if (nq) HIP_TRY(hipMemcpyAsync(H[0].p, M[4].p, (size_t)(4 * nq) * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(H[1].p, M[6].p, (size_t)(nb + 1) * 16, hipMemcpyDeviceToHost, ctx->stream));
-    if (nj) HIP_TRY(hipMemcpyAsync(H[2].p, K[0].p, (size_t)nj * sizeof(meme_kswv_job), hipMemcpyDeviceToHost, ctx->stream));
+    if (nq) HIP_TRY(hipMemcpyAsync(M.h_gar.p, M.gar.p, (size_t)(4 * nq) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(M.h_batch_off.p, M.batch_off.p, (size_t)(nb + 1) * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (nj) HIP_TRY(hipMemcpyAsync(M.h_jobs.p, K.jobs.p, (size_t)nj * sizeof(meme_kswv_job), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipEventRecord(ev[1], ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     float pose_ms = 0.f;
@@ -240,10 +225,10 @@ extern "C" int meme_matesw_batch_host(meme_ctx* ctx, meme_ctx* reads_of, const m
         meme_bsw_opt bo;
         memset(&bo, 0, sizeof(bo));
         bo.a = opt->a; bo.b = opt->b; bo.o_del = opt->o_del; bo.e_del = opt->e_del; bo.o_ins = opt->o_ins; bo.e_ins = opt->e_ins;
-        if ((rc = meme_kswv_run(ctx, (const meme_kswv_job*)H[2].p, nj, nullptr, ref_bytes, nullptr, qer_bytes, &bo, true, &R))) return rc;
+        if ((rc = meme_kswv_run(ctx, (const meme_kswv_job*)M.h_jobs.p, nj, nullptr, ref_bytes, nullptr, qer_bytes, &bo, true, &R))) return rc;
     }
     out->nreads = n; out->nbatches = nb; out->njobs = nj; out->n_gar = 4 * nq;
-    out->gar = (const int32_t*)H[0].p; out->gar_off = (const int64_t*)H[1].p; out->job_off = (const int64_t*)H[1].p + (nb + 1);
-    out->jobs = (const meme_kswv_job*)H[2].p; out->res = R.res; out->pose_ms = pose_ms; out->kernel_ms = R.kernel_ms;
+    out->gar = (const int32_t*)M.h_gar.p; out->gar_off = (const int64_t*)M.h_batch_off.p; out->job_off = (const int64_t*)M.h_batch_off.p + (nb + 1);
+    out->jobs = (const meme_kswv_job*)M.h_jobs.p; out->res = R.res; out->pose_ms = pose_ms; out->kernel_ms = R.kernel_ms;
     return MEME_OK;
 }

@@ -171,12 +171,6 @@ __global__ void __launch_bounds__(256) k_prmi_third(const SaEnt* __restrict__ en
   }
 }
 
-unsigned blocks_for(i64 items) {
-  i64 b = (items + 255) / 256;
-  const i64 cap = 256 * 64;
-  return (unsigned)(b < cap ? (b < 1 ? 1 : b) : cap);
-}
-
 }  // namespace
 
 extern "C" int meme_prmi_train_device(meme_ctx* ctx, const void* d_sa_ent, int64_t n, int bits, int partial_threshold,
@@ -193,8 +187,8 @@ extern "C" int meme_prmi_train_device(meme_ctx* ctx, const void* d_sa_ent, int64
     auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->stream); release(); return code; };
     if (hipMalloc(&d_start, (size_t)(nleaf + 1) * 8) != hipSuccess || hipMalloc(&d_np, (size_t)(nleaf + 1) * 8) != hipSuccess ||
         hipMalloc(&d_pstart, (size_t)(nleaf + 1) * 8) != hipSuccess) { meme_set_error("meme_prmi_train_device: out of device memory"); return fail(MEME_E_HIP); }
-    hipLaunchKernelGGL(k_prmi_bounds, dim3(blocks_for(nleaf + 1)), dim3(256), 0, ctx->stream, ent, (i64)n, shift, nleaf, d_start);
-    hipLaunchKernelGGL(k_prmi_partials, dim3(blocks_for(nleaf)), dim3(256), 0, ctx->stream, d_start, nleaf, partial_threshold, d_np);
+    hipLaunchKernelGGL(k_prmi_bounds, dim3(grid_blocks(nleaf + 1, 256)), dim3(256), 0, ctx->stream, ent, (i64)n, shift, nleaf, d_start);
+    hipLaunchKernelGGL(k_prmi_partials, dim3(grid_blocks(nleaf, 256)), dim3(256), 0, ctx->stream, d_start, nleaf, partial_threshold, d_np);
     if (hipMemsetAsync(d_np + nleaf, 0, 8, ctx->stream) != hipSuccess) return fail(MEME_E_HIP);
     size_t scan_bytes = 0;
     if (rocprim::exclusive_scan(nullptr, scan_bytes, d_np, d_pstart, 0, (size_t)(nleaf + 1), rocprim::plus<>(), ctx->stream) != hipSuccess) return fail(MEME_E_HIP);
@@ -210,9 +204,9 @@ extern "C" int meme_prmi_train_device(meme_ctx* ctx, const void* d_sa_ent, int64
         meme_set_error("meme_prmi_train_device: %lld third-layer records, room for %lld", (long long)total, (long long)l1_capacity);
         return fail(MEME_E_CAPACITY);
     }
-    hipLaunchKernelGGL(k_prmi_leaves, dim3(blocks_for(nleaf)), dim3(256), 0, ctx->stream, ent, (i64)n, shift, nleaf, d_start, d_np, d_pstart, (uint8_t*)d_l2_24);
+    hipLaunchKernelGGL(k_prmi_leaves, dim3(grid_blocks(nleaf, 256)), dim3(256), 0, ctx->stream, ent, (i64)n, shift, nleaf, d_start, d_np, d_pstart, (uint8_t*)d_l2_24);
     if (total > 0)
-        hipLaunchKernelGGL(k_prmi_third, dim3(blocks_for(total)), dim3(256), 0, ctx->stream, ent, (i64)n, shift, nleaf, d_start, d_np, d_pstart, total, (uint8_t*)d_l1_24);
+        hipLaunchKernelGGL(k_prmi_third, dim3(grid_blocks(total, 256)), dim3(256), 0, ctx->stream, ent, (i64)n, shift, nleaf, d_start, d_np, d_pstart, total, (uint8_t*)d_l1_24);
     if (hipGetLastError() != hipSuccess) return fail(MEME_E_HIP);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { meme_set_error("meme_prmi_train_device: kernel failed"); return fail(MEME_E_HIP); }
     release();

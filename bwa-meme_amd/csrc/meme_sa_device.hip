@@ -184,12 +184,6 @@ __global__ void __launch_bounds__(256) k_iota_off(u64* __restrict__ out, i64 m, 
     for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += (i64)gridDim.x * blockDim.x) out[k] = (u64)(off + k);
 }
 
-unsigned grid_for(i64 items) {
-    i64 b = (items + 255) / 256;
-    const i64 cap = 256 * 32;
-    return (unsigned)(b < cap ? (b < 1 ? 1 : b) : cap);
-}
-
 struct Scratch {          // device allocations of one build, released together
     std::vector<void*> ptrs;
     ~Scratch() { for (void* p : ptrs) (void)hipFree(p); }
@@ -220,7 +214,7 @@ extern "C" int meme_sa_build_device(meme_ctx* ctx, const uint8_t* d_text0123, in
     HIP_TRY(hipMemsetAsync(d_cnt, 0, 264 * sizeof(unsigned long long), st));
     // ---- padded text: k = longest A / T run + 1 bases T behind the text (the reference's convention), N = n + k suffixes
     unsigned long long* d_run = d_cnt + 260;
-    hipLaunchKernelGGL(k_sa_runs, dim3(grid_for(n)), dim3(256), 0, st, d_text0123, (i64)n, d_run);
+    hipLaunchKernelGGL(k_sa_runs, dim3(grid_blocks(n, 256, 256 * 32)), dim3(256), 0, st, d_text0123, (i64)n, d_run);
     unsigned long long h_run = 0;
     HIP_TRY(hipMemcpyAsync(&h_run, d_run, sizeof(h_run), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -232,8 +226,8 @@ extern "C" int meme_sa_build_device(meme_ctx* ctx, const uint8_t* d_text0123, in
     if ((rc = S.get(&pac, (size_t)words))) return rc;
     if ((rc = S.get(&rank, (size_t)N))) return rc;
     if ((rc = S.get(&sa, (size_t)N))) return rc;
-    hipLaunchKernelGGL(k_sa_pack, dim3(grid_for(words)), dim3(256), 0, st, d_text0123, (i64)n, N, pac, words);
-    hipLaunchKernelGGL(k_sa_hist, dim3(grid_for(N)), dim3(256), 0, st, (const u64*)pac, N, d_cnt);
+    hipLaunchKernelGGL(k_sa_pack, dim3(grid_blocks(words, 256, 256 * 32)), dim3(256), 0, st, d_text0123, (i64)n, N, pac, words);
+    hipLaunchKernelGGL(k_sa_hist, dim3(grid_blocks(N, 256, 256 * 32)), dim3(256), 0, st, (const u64*)pac, N, d_cnt);
     unsigned long long h_hist[256];
     HIP_TRY(hipMemcpyAsync(h_hist, d_cnt, sizeof(h_hist), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -278,16 +272,16 @@ extern "C" int meme_sa_build_device(meme_ctx* ctx, const uint8_t* d_text0123, in
         i64 m = 0;
         for (unsigned b = g.first; b < g.second; ++b) m += (i64)h_hist[b];
         HIP_TRY(hipMemsetAsync(d_nsel, 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(k_sa_gather, dim3(grid_for((N + GATHER_ITEMS - 1) / GATHER_ITEMS)), dim3(256), 0, st, (const u64*)pac, N, g.first, g.second, d_nsel, ka, va);
+        hipLaunchKernelGGL(k_sa_gather, dim3(grid_blocks((N + GATHER_ITEMS - 1) / GATHER_ITEMS, 256, 256 * 32)), dim3(256), 0, st, (const u64*)pac, N, g.first, g.second, d_nsel, ka, va);
         rocprim::double_buffer<u64> dk(ka, kb), dv(va, vb);
         HIP_TRY(rocprim::radix_sort_pairs(tmp, tmp_bytes, dk, dv, m, 0, 64, st));
-        hipLaunchKernelGGL(k_sa_heads, dim3(grid_for(m)), dim3(256), 0, st, (const u64*)dk.current(), (const u64*)nullptr, m, head, vv);
+        hipLaunchKernelGGL(k_sa_heads, dim3(grid_blocks(m, 256, 256 * 32)), dim3(256), 0, st, (const u64*)dk.current(), (const u64*)nullptr, m, head, vv);
         HIP_TRY(rocprim::inclusive_scan(tmp, tmp_bytes, vv, gst, (size_t)(m), rocprim::maximum<i64>(), st));
-        hipLaunchKernelGGL(k_sa_emit, dim3(grid_for(m)), dim3(256), 0, st, (const u64*)dv.current(), (const unsigned char*)head,
+        hipLaunchKernelGGL(k_sa_emit, dim3(grid_blocks(m, 256, 256 * 32)), dim3(256), 0, st, (const u64*)dv.current(), (const unsigned char*)head,
                            (const i64*)gst, m, off, sa, rank, tied);
         // positions of the tied slots of this run
         u64* iota = dk.alternate();                       // (the key buffers are free again)
-        hipLaunchKernelGGL(k_iota_off, dim3(grid_for(m)), dim3(256), 0, st, iota, m, off);
+        hipLaunchKernelGGL(k_iota_off, dim3(grid_blocks(m, 256, 256 * 32)), dim3(256), 0, st, iota, m, off);
         u64* sel = dv.alternate();
         HIP_TRY(rocprim::select(tmp, tmp_bytes, iota, tied, sel, d_nsel, m, st));
         unsigned long long h_sel = 0;
@@ -335,7 +329,7 @@ extern "C" int meme_sa_build_device(meme_ctx* ctx, const uint8_t* d_text0123, in
         if (r3 > rb) rb = r3;
         unsigned char* rtmp = nullptr;
         if ((rc = R.get(&rtmp, rb))) return rc;
-        const unsigned g = grid_for(m);
+        const unsigned g = grid_blocks(m, 256, 256 * 32);
         hipLaunchKernelGGL(k_sa_prep, dim3(g), dim3(256), 0, st, (const u64*)upos, m, (const u64*)sa, (const u64*)rank, N, h, prim, sec, val, idx);
         // stable LSD: by the second rank, then by the first
         HIP_TRY(rocprim::radix_sort_pairs(rtmp, rb, (const u64*)sec, k2, (const unsigned*)idx, idx2, m, 0, 44, st));
@@ -373,8 +367,8 @@ extern "C" int meme_sa_build_device(meme_ctx* ctx, const uint8_t* d_text0123, in
         i64 found = 0;
         for (i64 o = 0; o < N; o += piece) {
             const i64 mlen = N - o < piece ? N - o : piece;
-            hipLaunchKernelGGL(k_sa_flag_padding, dim3(grid_for(mlen)), dim3(256), 0, st, (const u64*)(sa + o), mlen, (i64)n, flag);
-            hipLaunchKernelGGL(k_iota_off, dim3(grid_for(mlen)), dim3(256), 0, st, iota, mlen, o);
+            hipLaunchKernelGGL(k_sa_flag_padding, dim3(grid_blocks(mlen, 256, 256 * 32)), dim3(256), 0, st, (const u64*)(sa + o), mlen, (i64)n, flag);
+            hipLaunchKernelGGL(k_iota_off, dim3(grid_blocks(mlen, 256, 256 * 32)), dim3(256), 0, st, iota, mlen, o);
             HIP_TRY(rocprim::select(stmp, sb, iota, flag, pad_slots + found, d_cnt, mlen, st));
             unsigned long long h_sel = 0;
             HIP_TRY(hipMemcpyAsync(&h_sel, d_cnt, sizeof(h_sel), hipMemcpyDeviceToHost, st));
@@ -383,7 +377,7 @@ extern "C" int meme_sa_build_device(meme_ctx* ctx, const uint8_t* d_text0123, in
             if (found > k_pad) { meme_set_error("meme_sa_build_device: internal padding count mismatch"); return MEME_E_STATE; }
         }
         if (found != k_pad) { meme_set_error("meme_sa_build_device: internal padding count mismatch (%lld of %lld)", (long long)found, (long long)k_pad); return MEME_E_STATE; }
-        hipLaunchKernelGGL(k_sa_drop_padding, dim3(grid_for(N)), dim3(256), 0, st, (const u64*)sa, N, (i64)n, (const u64*)pad_slots, (int)k_pad, (u64*)d_sa);
+        hipLaunchKernelGGL(k_sa_drop_padding, dim3(grid_blocks(N, 256, 256 * 32)), dim3(256), 0, st, (const u64*)sa, N, (i64)n, (const u64*)pad_slots, (int)k_pad, (u64*)d_sa);
     }
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipGetLastError());

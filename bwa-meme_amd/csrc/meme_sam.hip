@@ -219,30 +219,28 @@ __global__ void __launch_bounds__(256) k_sam_pack(const i64* __restrict__ soff, 
     for (i64 i = threadIdx.x & 63; i < l; i += 64) dst[i] = src[i];
 }
 
-unsigned grid_of(i64 items, int per) { i64 b = (items + per - 1) / per; const i64 cap = 256 * 64; return (unsigned)(b < cap ? (b < 1 ? 1 : b) : cap); }
-
 }  // namespace
 
 extern "C" int meme_sam_stage_text(meme_ctx* ctx, const char* names, const int64_t* name_off, const char* quals) {
     if (!ctx || !names || !name_off) { meme_set_error("meme_sam_stage_text: null argument"); return MEME_E_ARG; }
     HIP_TRY(hipSetDevice(ctx->device));
-    const i64 n = ctx->last_seed_reads;
-    if (n <= 0 || !ctx->reads_resident || !ctx->read_off.p) { meme_set_error("meme_sam_stage_text: no seeded batch on this ctx"); return MEME_E_STATE; }
+    const i64 n = ctx->batch.last_seed_reads;
+    if (n <= 0 || !ctx->batch.reads_resident || !ctx->batch.read_off.p) { meme_set_error("meme_sam_stage_text: no seeded batch on this ctx"); return MEME_E_STATE; }
     if (name_off[0] != 0) { meme_set_error("meme_sam_stage_text: name_off[0] must be 0"); return MEME_E_ARG; }
     for (i64 r = 0; r < n; ++r) if (name_off[r + 1] < name_off[r]) { meme_set_error("meme_sam_stage_text: name offsets must not decrease (read %lld)", (long long)r); return MEME_E_ARG; }
     int rc;
-    DevBuf* S = ctx->sam;        // 0 names, 1 name offsets, 2 qualities, 3 records, 4 blob, 5 bounds + offsets + lengths, 6 scratch, 7 text, 8 contig names + offsets + rg
+    SamWs& S = ctx->sam;
     const i64 nb = name_off[n];
-    if ((rc = meme_buf_reserve(ctx, S[0], (size_t)nb + 64)) || (rc = meme_buf_reserve(ctx, S[1], (size_t)(n + 1) * 8))) return rc;
-    HIP_TRY(hipMemcpyAsync(S[0].p, names, (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(S[1].p, name_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = meme_buf_reserve(ctx, S.names, (size_t)nb + 64)) || (rc = meme_buf_reserve(ctx, S.name_off, (size_t)(n + 1) * 8))) return rc;
+    HIP_TRY(hipMemcpyAsync(S.names.p, names, (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(S.name_off.p, name_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     ctx->sam_has_quals = quals != nullptr;
     if (quals) {
         i64 total = 0;
-        HIP_TRY(hipMemcpyAsync(&total, (const i64*)ctx->read_off.p + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(&total, (const i64*)ctx->batch.read_off.p + n, 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if ((rc = meme_buf_reserve(ctx, S[2], (size_t)total + 64))) return rc;
-        HIP_TRY(hipMemcpyAsync(S[2].p, quals, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = meme_buf_reserve(ctx, S.quals, (size_t)total + 64))) return rc;
+        HIP_TRY(hipMemcpyAsync(S.quals.p, quals, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->sam_text_reads = n;
@@ -260,8 +258,8 @@ extern "C" int meme_sam_format_batch_host(meme_ctx* ctx, const meme_sam_rec* rec
     memset(out, 0, sizeof(*out));
     if (nrecs == 0) return MEME_OK;
     if (ctx->sam_max_batch > 0 && nrecs > ctx->sam_max_batch) { meme_set_error("%s: %lld record slots exceed the ctx's sam_max_batch of %lld", who, (long long)nrecs, (long long)ctx->sam_max_batch); return MEME_E_CAPACITY; }
-    const i64 nreads = ctx->last_seed_reads;
-    if (nreads <= 0 || !ctx->reads_resident || !ctx->reads.p || ctx->sam_text_reads != nreads) {
+    const i64 nreads = ctx->batch.last_seed_reads;
+    if (nreads <= 0 || !ctx->batch.reads_resident || !ctx->batch.reads.p || ctx->sam_text_reads != nreads) {
         meme_set_error("%s: the batch on this ctx has no names / qualities staged (meme_sam_stage_text after the seeding call)", who);
         return MEME_E_STATE;
     }
@@ -282,60 +280,55 @@ extern "C" int meme_sam_format_batch_host(meme_ctx* ctx, const meme_sam_rec* rec
     }
     const int rg_len = rg_id ? (int)strlen(rg_id) : 0;
     int rc;
-    DevBuf* S = ctx->sam;
+    SamWs& S = ctx->sam;
     const size_t ctab = (size_t)contig_name_off[n_contigs] + (size_t)(n_contigs + 1) * 4 + (size_t)rg_len + 64;
-    if ((rc = meme_buf_reserve(ctx, S[3], (size_t)nrecs * sizeof(meme_sam_rec))) || (rc = meme_buf_reserve(ctx, S[4], (size_t)blob_bytes + 128)) ||
-        (rc = meme_buf_reserve(ctx, S[5], (size_t)(nrecs + 1) * 8 * 4 + 64)) || (rc = meme_buf_reserve(ctx, S[8], ctab))) return rc;
-    for (int i = 0; i < 2; ++i) if (!ctx->ev_sam[i]) HIP_TRY(hipEventCreate(&ctx->ev_sam[i]));
-    HIP_TRY(hipMemcpyAsync(S[3].p, recs, (size_t)nrecs * sizeof(meme_sam_rec), hipMemcpyHostToDevice, ctx->stream));
-    if (blob_bytes) HIP_TRY(hipMemcpyAsync(S[4].p, blob, (size_t)blob_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemsetAsync((char*)S[4].p + blob_bytes, 0, 128, ctx->stream));            // (the strlen loops read 64 bytes at a time)
+    if ((rc = meme_buf_reserve(ctx, S.recs, (size_t)nrecs * sizeof(meme_sam_rec))) || (rc = meme_buf_reserve(ctx, S.blob, (size_t)blob_bytes + 128)) ||
+        (rc = meme_buf_reserve(ctx, S.cols, SamCols(nullptr, nrecs).bytes)) || (rc = meme_buf_reserve(ctx, S.contigs, ctab))) return rc;
+    for (int i = 0; i < 2; ++i) if (!S.ev[i]) HIP_TRY(hipEventCreate(&S.ev[i]));
+    HIP_TRY(hipMemcpyAsync(S.recs.p, recs, (size_t)nrecs * sizeof(meme_sam_rec), hipMemcpyHostToDevice, ctx->stream));
+    if (blob_bytes) HIP_TRY(hipMemcpyAsync(S.blob.p, blob, (size_t)blob_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync((char*)S.blob.p + blob_bytes, 0, 128, ctx->stream));            // (the strlen loops read 64 bytes at a time)
     // contig table: offsets (4-byte aligned first), names, read group
-    char* d_tab = (char*)S[8].p;
+    char* d_tab = (char*)S.contigs.p;
     const size_t off_bytes = (size_t)(n_contigs + 1) * 4;
     HIP_TRY(hipMemcpyAsync(d_tab, contig_name_off, off_bytes, hipMemcpyHostToDevice, ctx->stream));
     if (contig_name_off[n_contigs]) HIP_TRY(hipMemcpyAsync(d_tab + off_bytes, contig_names, (size_t)contig_name_off[n_contigs], hipMemcpyHostToDevice, ctx->stream));
     if (rg_len) HIP_TRY(hipMemcpyAsync(d_tab + off_bytes + contig_name_off[n_contigs], rg_id, (size_t)rg_len, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_sam[0], ctx->stream));
-    i64* d_bound = (i64*)S[5].p;
-    i64* d_soff = d_bound + (nrecs + 1);
-    i64* d_len = d_soff + (nrecs + 1);
-    i64* d_toff = d_len + (nrecs + 1);
-    i64* d_bad = d_toff + (nrecs + 1);
-    HIP_TRY(hipMemsetAsync(d_bad, 0xff, 8, ctx->stream));
-    hipLaunchKernelGGL(k_sam_bounds, dim3(grid_of(nrecs, 256)), dim3(256), 0, ctx->stream, (const meme_sam_rec*)S[3].p, (i64)nrecs, (const i64*)ctx->read_off.p, (const i64*)S[1].p,
-                       (const uint8_t*)S[4].p, (i64)blob_bytes, max_contig, rg_len, d_bound, d_bad);
-    if ((rc = meme_scan_exclusive(ctx, d_bound, d_soff, nrecs))) return rc;
+    HIP_TRY(hipEventRecord(S.ev[0], ctx->stream));
+    const SamCols sc(S.cols.p, nrecs);
+    HIP_TRY(hipMemsetAsync(sc.bad, 0xff, 8, ctx->stream));
+    hipLaunchKernelGGL(k_sam_bounds, dim3(grid_blocks(nrecs, 256)), dim3(256), 0, ctx->stream, (const meme_sam_rec*)S.recs.p, (i64)nrecs, (const i64*)ctx->batch.read_off.p, (const i64*)S.name_off.p,
+                       (const uint8_t*)S.blob.p, (i64)blob_bytes, max_contig, rg_len, sc.bound, sc.bad);
+    if ((rc = meme_scan_exclusive(ctx, sc.bound, sc.soff, nrecs))) return rc;
     i64 total_scratch = 0, bad = -1;
-    HIP_TRY(hipMemcpyAsync(&total_scratch, d_soff + nrecs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&total_scratch, sc.soff + nrecs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&bad, sc.bad, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (bad >= 0) { meme_set_error("%s: record %lld names a string that does not end inside the blob", who, (long long)bad); return MEME_E_ARG; }
-    if ((rc = meme_buf_reserve(ctx, S[6], (size_t)total_scratch + 64))) return rc;
+    if ((rc = meme_buf_reserve(ctx, S.scratch, (size_t)total_scratch + 64))) return rc;
     SamArgs A;
-    A.recs = (const meme_sam_rec*)S[3].p; A.nrecs = nrecs; A.blob = (const uint8_t*)S[4].p; A.reads = (const uint8_t*)ctx->reads.p; A.read_off = (const i64*)ctx->read_off.p;
-    A.names = (const char*)S[0].p; A.name_off = (const i64*)S[1].p; A.quals = ctx->sam_has_quals ? (const char*)S[2].p : nullptr;
+    A.recs = (const meme_sam_rec*)S.recs.p; A.nrecs = nrecs; A.blob = (const uint8_t*)S.blob.p; A.reads = (const uint8_t*)ctx->batch.reads.p; A.read_off = (const i64*)ctx->batch.read_off.p;
+    A.names = (const char*)S.names.p; A.name_off = (const i64*)S.name_off.p; A.quals = ctx->sam_has_quals ? (const char*)S.quals.p : nullptr;
     A.contig_name_off = (const int32_t*)d_tab; A.contig_names = d_tab + off_bytes; A.softclip = softclip ? 1 : 0;
     A.rg = d_tab + off_bytes + contig_name_off[n_contigs]; A.rg_len = rg_len;
-    A.soff = d_soff; A.scratch = (char*)S[6].p; A.len = d_len; A.over = d_bad;            // (d_bad is all-ones again: the bounds kernel found nothing)
+    A.soff = sc.soff; A.scratch = (char*)S.scratch.p; A.len = sc.len; A.over = sc.bad;            // (sc.bad is all-ones again: the bounds kernel found nothing)
     hipLaunchKernelGGL(k_sam_format, dim3((unsigned)((nrecs + 3) / 4)), dim3(256), 0, ctx->stream, A);
-    if ((rc = meme_scan_exclusive(ctx, d_len, d_toff, nrecs))) return rc;
+    if ((rc = meme_scan_exclusive(ctx, sc.len, sc.toff, nrecs))) return rc;
     i64 total = 0, over = -1;
-    HIP_TRY(hipMemcpyAsync(&total, d_toff + nrecs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&over, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&total, sc.toff + nrecs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&over, sc.bad, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (over >= 0) { meme_set_error("%s: the text of record %lld is longer than the slot k_sam_bounds gave it (formatter and bound disagree)", who, (long long)over); return MEME_E_STATE; }
-    if ((rc = meme_buf_reserve(ctx, S[7], (size_t)total + 64))) return rc;
-    hipLaunchKernelGGL(k_sam_pack, dim3((unsigned)((nrecs + 3) / 4)), dim3(256), 0, ctx->stream, (const i64*)d_soff, (const char*)S[6].p, (const i64*)d_toff, (i64)nrecs, (char*)S[7].p);
+    if ((rc = meme_buf_reserve(ctx, S.text, (size_t)total + 64))) return rc;
+    hipLaunchKernelGGL(k_sam_pack, dim3((unsigned)((nrecs + 3) / 4)), dim3(256), 0, ctx->stream, (const i64*)sc.soff, (const char*)S.scratch.p, (const i64*)sc.toff, (i64)nrecs, (char*)S.text.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_sam[1], ctx->stream));
-    meme_ctx::HostBuf* Hb = ctx->h_sam;
-    if ((rc = meme_hostbuf_reserve(ctx, Hb[0], (size_t)(nrecs + 1) * 8)) || (rc = meme_hostbuf_reserve(ctx, Hb[1], (size_t)total + 64))) return rc;
-    HIP_TRY(hipMemcpyAsync(Hb[0].p, d_toff, (size_t)(nrecs + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (total) HIP_TRY(hipMemcpyAsync(Hb[1].p, S[7].p, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipEventRecord(S.ev[1], ctx->stream));
+    if ((rc = meme_hostbuf_reserve(ctx, S.h_text_off, (size_t)(nrecs + 1) * 8)) || (rc = meme_hostbuf_reserve(ctx, S.h_text, (size_t)total + 64))) return rc;
+    HIP_TRY(hipMemcpyAsync(S.h_text_off.p, sc.toff, (size_t)(nrecs + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (total) HIP_TRY(hipMemcpyAsync(S.h_text.p, S.text.p, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_sam[0], ctx->ev_sam[1]));
-    out->nrecs = nrecs; out->text_off = (const int64_t*)Hb[0].p; out->text = (const char*)Hb[1].p; out->text_bytes = total; out->kernel_ms = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+    out->nrecs = nrecs; out->text_off = (const int64_t*)S.h_text_off.p; out->text = (const char*)S.h_text.p; out->text_bytes = total; out->kernel_ms = ms;
     return MEME_OK;
 }

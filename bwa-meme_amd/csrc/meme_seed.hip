@@ -186,14 +186,14 @@ int launch_k_seed(hipStream_t stream, const SeedArgs& A, size_t lds, i64 blocks)
 
 int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i64 nreads, i64 max_len, i64 total_bytes,
                 const meme_seed_opt* opt, meme_seed_result* out) {
-    unsigned long long h_counters[16];
+    unsigned long long h_counters[SEED_CTRS];
     int rc;
-    ctx->last_seed_reads = 0;          // whatever batch meme_chain_last_batch_host could have chained is being overwritten
+    ctx->batch.last_seed_reads = 0;          // whatever batch meme_chain_last_batch_host could have chained is being overwritten
     ctx->sam_text_reads = 0;           // ... and the names / qualities staged for it belong to the previous batch
-    if ((rc = meme_buf_reserve(ctx, ctx->slot_cnt, (size_t)nreads * sizeof(int)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->slot_hits, (size_t)nreads * sizeof(i64)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->slot_loc, (size_t)nreads * sizeof(i64)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->counters, 2 * 16 * sizeof(unsigned long long)))) return rc;     // two sets: an overflow tier may run beside the re-seeding kernels
+    if ((rc = meme_buf_reserve(ctx, ctx->seed.slot_cnt, (size_t)nreads * sizeof(int)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->seed.slot_hits, (size_t)nreads * sizeof(i64)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->seed.slot_loc, (size_t)nreads * sizeof(i64)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->seed.counters, 2 * SEED_CTRS * sizeof(unsigned long long)))) return rc;
     const int dev_cus = ctx->n_cus;
     // ---- pack the reads: 2 bits/base, both strands, N masks (k_pack_reads) ---------------------------------
     // the reference exits on reads longer than LEARNED_MAX_READ_LEN (src/bwamem.cpp:1259-1262): fail loudly, never seed part of a batch
@@ -207,7 +207,7 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
     geo.W = (int)((max_len + 31) / 32) + 2;
     geo.MW = (int)((max_len + 63) / 64);
     geo.stride = 2 * geo.W + 2 * geo.MW + 1;
-    if ((rc = meme_buf_reserve(ctx, ctx->packed, (size_t)nreads * geo.stride * 8))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->batch.packed, (size_t)nreads * geo.stride * 8))) return rc;
     HIP_TRY(hipEventRecord(ctx->ev[6], ctx->stream));
     {
         int rb = (int)((48 * 1024) / stage_len);                    // reads per workgroup: <= 48 KB of staged bytes
@@ -217,7 +217,7 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
         if (pblocks > (i64)dev_cus * 16) pblocks = (i64)dev_cus * 16;   // grid-stride beyond that
         size_t plds = ((size_t)rb * (size_t)stage_len + 16 + 48 + 3) & ~(size_t)3;   // + the packer's 9-dword reads past a read's last word
         hipLaunchKernelGGL(k_pack_reads, dim3((unsigned)pblocks), dim3(256), plds, ctx->stream, d_reads,
-                           d_read_off, nreads, total_bytes, geo, rb, (u64*)ctx->packed.p);
+                           d_read_off, nreads, total_bytes, geo, rb, (u64*)ctx->batch.packed.p);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(ctx->ev[7], ctx->stream));
@@ -226,14 +226,14 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
     TierTable tiers;
     for (int t = 0; t < N_TIERS; ++t) { tiers.base[t] = nullptr; tiers.cap[t] = 0; }
     // One k_seed launch of a tier: `n_todo` reads (tier 0: the batch; overflow tiers: the reads named in `pending`), SMEM slots in
-    // ctx->slots[tier], the reads that overflow THIS tier appended to ctx->ovf[tier & 1], counters in set `cset`.
+    // ctx->seed.slots[tier], the reads that overflow THIS tier appended to ctx->seed.ovf[tier & 1], counters in set `cset`.
     auto launch_tier = [&](int tier, i64 n_todo, const i64* pending, int cset, hipStream_t stream, bool defer) -> int {
         // overflow tiers hold a 512-entry SMEM ring per read in LDS: run them 32 lanes per read (8 reads per block)
         int G = tier == 0 ? (int)ctx->group_lanes : 32;
         const int cap = tier == 0 ? (int)ctx->smem_cap : TIER_CAP[tier];
         const int lcap = cap < TIER_LCAP[tier] ? cap : TIER_LCAP[tier];
-        DevBuf& sb = ctx->slots[tier];
-        DevBuf& ob = ctx->ovf[tier & 1];
+        DevBuf& sb = ctx->seed.slots[tier];
+        DevBuf& ob = ctx->seed.ovf[tier & 1];
         const size_t need = (size_t)n_todo * cap * sizeof(SlotRec);
         if (tier > 0 && need > sb.cap) {
             // overflow tiers re-run the reads that emitted more SMEMs than their slots hold, with 32 x more slots each:
@@ -249,19 +249,19 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
         int rc2;
         if ((rc2 = meme_buf_reserve(ctx, sb, need))) return rc2;
         if ((rc2 = meme_buf_reserve(ctx, ob, (size_t)n_todo * sizeof(i64)))) return rc2;
-        unsigned long long* counters = (unsigned long long*)ctx->counters.p + 16 * cset;
-        HIP_TRY(hipMemsetAsync(counters, 0, 16 * sizeof(unsigned long long), stream));
+        unsigned long long* counters = ctx->seed.counter_set(cset);
+        HIP_TRY(hipMemsetAsync(counters, 0, SEED_CTRS * sizeof(unsigned long long), stream));
         SeedArgs A;
         A.I = ctx->idx;
-        A.packed = (const u64*)ctx->packed.p;
+        A.packed = (const u64*)ctx->batch.packed.p;
         A.read_off = d_read_off;
         A.nreads = n_todo;
         A.geo = geo;
         A.opt = *opt;
         A.slots = (SlotRec*)sb.p;
-        A.slot_cnt = (int*)ctx->slot_cnt.p;
-        A.slot_hits = (i64*)ctx->slot_hits.p;
-        A.slot_loc = (i64*)ctx->slot_loc.p;
+        A.slot_cnt = (int*)ctx->seed.slot_cnt.p;
+        A.slot_hits = (i64*)ctx->seed.slot_hits.p;
+        A.slot_loc = (i64*)ctx->seed.slot_loc.p;
         A.pending = pending;
         A.ovf_list = (i64*)ob.p;
         A.cap = cap;
@@ -306,8 +306,8 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
     // ---- tier 0: the whole batch.  It leaves the re-seeding regions of unique SMEMs to k_reseed (a walk on the plcp table, one lane per
     // read) and the batches of searches behind it; the overflow tiers search everything themselves.
     const bool defer = ctx->seed_defer != 0 && ctx->idx.plcp != nullptr && opt->rounds >= 2;
-    if (defer && (rc = meme_buf_reserve(ctx, ctx->pend, (size_t)nreads * sizeof(i64)))) return rc;
-    if (defer && (rc = meme_buf_reserve(ctx, ctx->blk, (size_t)nreads * BLK_PER_READ * 2 * sizeof(BlkRec)))) return rc;
+    if (defer && (rc = meme_buf_reserve(ctx, ctx->seed.pend, (size_t)nreads * sizeof(i64)))) return rc;
+    if (defer && (rc = meme_buf_reserve(ctx, ctx->seed.blk, (size_t)nreads * BLK_PER_READ * 2 * sizeof(BlkRec)))) return rc;
     if ((rc = launch_tier(0, nreads, nullptr, 0, ctx->stream, defer))) return rc;
     i64 n_early = -1;                  // reads of the tier-1 launch that ran beside the re-seeding kernels (-1: none did)
     { const int src = meme_side_stream(ctx, 0); if (src) return src; }
@@ -317,11 +317,11 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
         const int cap = (int)ctx->smem_cap;
         HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
         ReseedArgs R;
-        R.I = ctx->idx; R.packed = (const u64*)ctx->packed.p; R.geo = geo; R.nreads = nreads; R.opt = *opt;
-        R.slots = (SlotRec*)ctx->slots[0].p; R.cap = cap; R.slot_cnt = (int*)ctx->slot_cnt.p; R.slot_hits = (i64*)ctx->slot_hits.p;
-        R.ovf_list = (i64*)ctx->ovf[0].p; R.counters = (unsigned long long*)ctx->counters.p; R.pend_list = (i64*)ctx->pend.p;
-        R.blk = (BlkRec*)ctx->blk.p; R.blk_out = R.blk + nreads * BLK_PER_READ; R.blk_cap = nreads * BLK_PER_READ;
-        R.blk_ctr = 14; R.blk_out_ctr = 15;
+        R.I = ctx->idx; R.packed = (const u64*)ctx->batch.packed.p; R.geo = geo; R.nreads = nreads; R.opt = *opt;
+        R.slots = (SlotRec*)ctx->seed.slots[0].p; R.cap = cap; R.slot_cnt = (int*)ctx->seed.slot_cnt.p; R.slot_hits = (i64*)ctx->seed.slot_hits.p;
+        R.ovf_list = (i64*)ctx->seed.ovf[0].p; R.counters = ctx->seed.counter_set(0); R.pend_list = (i64*)ctx->seed.pend.p;
+        R.blk = (BlkRec*)ctx->seed.blk.p; R.blk_out = R.blk + nreads * BLK_PER_READ; R.blk_cap = nreads * BLK_PER_READ;
+        R.blk_ctr = SEED_CTR_BLK; R.blk_out_ctr = SEED_CTR_BLK_OUT;
         i64 rblocks = (nreads + 255) / 256;
         if (rblocks > (i64)dev_cus * 32) rblocks = (i64)dev_cus * 32;
         hipLaunchKernelGGL(k_reseed, dim3((unsigned)rblocks), dim3(256), 0, ctx->stream, R);
@@ -340,7 +340,7 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
             hipLaunchKernelGGL(k_reseed_search, dim3(sblocks), dim3(256), 0, ctx->stream, R);
             if (round < ROUNDS - 1) {
                 hipLaunchKernelGGL(k_reseed_resume<false>, dim3(sblocks), dim3(256), 0, ctx->stream, R);
-                HIP_TRY(hipMemsetAsync((unsigned long long*)ctx->counters.p + R.blk_ctr, 0, sizeof(unsigned long long), ctx->stream));
+                HIP_TRY(hipMemsetAsync(ctx->seed.counter_set(0) + R.blk_ctr, 0, sizeof(unsigned long long), ctx->stream));
                 std::swap(R.blk, R.blk_out); std::swap(R.blk_ctr, R.blk_out_ctr);
             } else hipLaunchKernelGGL(k_reseed_resume<true>, dim3(sblocks), dim3(256), 0, ctx->stream, R);
         }
@@ -352,11 +352,11 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
         if (ctx->seed_early_tier != 0) {
             unsigned long long h_ovf = 0;
             HIP_TRY(hipStreamWaitEvent(ctx->stream_side[0], ctx->ev_aux, 0));
-            HIP_TRY(hipMemcpyAsync(&h_ovf, (unsigned long long*)ctx->counters.p + 2, 8, hipMemcpyDeviceToHost, ctx->stream_side[0]));
+            HIP_TRY(hipMemcpyAsync(&h_ovf, ctx->seed.counter_set(0) + SEED_CTR_OVERFLOW, 8, hipMemcpyDeviceToHost, ctx->stream_side[0]));
             HIP_TRY(hipStreamSynchronize(ctx->stream_side[0]));
             if (h_ovf > 0) {
                 n_early = (i64)h_ovf;
-                if ((rc = launch_tier(1, n_early, (const i64*)ctx->ovf[0].p, 1, ctx->stream_side[0], false))) return rc;
+                if ((rc = launch_tier(1, n_early, (const i64*)ctx->seed.ovf[0].p, 1, ctx->stream_side[0], false))) return rc;
                 HIP_TRY(hipEventRecord(ctx->ev_side[0], ctx->stream_side[0]));
                 HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_side[0], 0));
             }
@@ -364,7 +364,7 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_emit[1], 0));
     }
     HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    HIP_TRY(hipMemcpyAsync(h_counters, ctx->counters.p, sizeof(h_counters), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(h_counters, ctx->seed.counter_set(0), sizeof(h_counters), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     {
         float ms = 0.f;
@@ -385,8 +385,8 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
     }
     tally(h_counters);
     // ---- overflow tiers: reads that produced more SMEMs than their slots hold (pathological repeats) are re-run alone
-    i64 n_todo = (i64)h_counters[2];
-    const i64* pending = (const i64*)ctx->ovf[0].p;
+    i64 n_todo = (i64)h_counters[SEED_CTR_OVERFLOW];
+    const i64* pending = (const i64*)ctx->seed.ovf[0].p;
     for (int tier = 1; n_todo > 0; ++tier) {
         if (tier >= N_TIERS) {
             meme_set_error("a read produced more than %d SMEMs", TIER_CAP[N_TIERS - 1]);
@@ -395,22 +395,22 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
         const int cset = tier & 1;
         if (tier == 1 && n_early == n_todo) {
             // the launch beside the re-seeding kernels took them all: only its counters are left to read
-            HIP_TRY(hipMemcpyAsync(h_counters, (unsigned long long*)ctx->counters.p + 16 * cset, sizeof(h_counters), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(h_counters, ctx->seed.counter_set(cset), sizeof(h_counters), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(hipStreamSynchronize(ctx->stream));
         } else {
             // (tier 1 after an early launch that did not see every overflowed read: all of them again -- rare, and simple)
             HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
             if ((rc = launch_tier(tier, n_todo, pending, cset, ctx->stream, false))) return rc;
             HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-            HIP_TRY(hipMemcpyAsync(h_counters, (unsigned long long*)ctx->counters.p + 16 * cset, sizeof(h_counters), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(h_counters, ctx->seed.counter_set(cset), sizeof(h_counters), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(hipStreamSynchronize(ctx->stream));
             float ms = 0.f;
             HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
             ms_total += ms;
         }
         tally(h_counters);
-        n_todo = (i64)h_counters[2];
-        pending = (const i64*)ctx->ovf[tier & 1].p;
+        n_todo = (i64)h_counters[SEED_CTR_OVERFLOW];
+        pending = (const i64*)ctx->seed.ovf[tier & 1].p;
     }
     {
         float pms = 0.f;
@@ -425,40 +425,40 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
     // offsets
     i64 ntiles = (nreads + SCAN_TILE - 1) / SCAN_TILE;
     if ((rc = meme_buf_reserve(ctx, ctx->scan_tmp, (size_t)(2 * ntiles + 2) * sizeof(i64)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->smem_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->hit_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->batch.smem_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->batch.hit_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
     i64* tiles = (i64*)ctx->scan_tmp.p;
     i64* totals = tiles + 2 * ntiles;
     HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
-    hipLaunchKernelGGL(k_tile_sums, dim3((unsigned)ntiles), dim3(SCAN_BLOCK), 0, ctx->stream, (const int*)ctx->slot_cnt.p,
-                       (const i64*)ctx->slot_hits.p, nreads, tiles);
+    hipLaunchKernelGGL(k_tile_sums, dim3((unsigned)ntiles), dim3(SCAN_BLOCK), 0, ctx->stream, (const int*)ctx->seed.slot_cnt.p,
+                       (const i64*)ctx->seed.slot_hits.p, nreads, tiles);
     hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(SCAN_BLOCK), 0, ctx->stream, tiles, ntiles, totals);
-    hipLaunchKernelGGL(k_offsets, dim3((unsigned)ntiles), dim3(SCAN_BLOCK), 0, ctx->stream, (const int*)ctx->slot_cnt.p,
-                       (const i64*)ctx->slot_hits.p, nreads, (const i64*)tiles, (i64*)ctx->smem_off.p,
-                       (i64*)ctx->hit_off.p);
+    hipLaunchKernelGGL(k_offsets, dim3((unsigned)ntiles), dim3(SCAN_BLOCK), 0, ctx->stream, (const int*)ctx->seed.slot_cnt.p,
+                       (const i64*)ctx->seed.slot_hits.p, nreads, (const i64*)tiles, (i64*)ctx->batch.smem_off.p,
+                       (i64*)ctx->batch.hit_off.p);
     HIP_TRY(hipGetLastError());
     i64 h_tot[2];
     HIP_TRY(hipMemcpyAsync(h_tot, totals, sizeof(h_tot), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if ((rc = meme_buf_reserve(ctx, ctx->smems, (size_t)(h_tot[0] + 1) * sizeof(meme_mem_tl)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->hits, (size_t)(h_tot[1] + 1) * sizeof(u64)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->batch.smems, (size_t)(h_tot[0] + 1) * sizeof(meme_mem_tl)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->batch.hits, (size_t)(h_tot[1] + 1) * sizeof(u64)))) return rc;
     i64 gblocks = (nreads + 15) / 16;
     if (gblocks > (i64)dev_cus * 8) gblocks = (i64)dev_cus * 8;
     if (gblocks < 1) gblocks = 1;
     hipLaunchKernelGGL(k_gather, dim3((unsigned)gblocks), dim3(BLOCK), 0, ctx->stream, ctx->idx.sa, tiers,
-                       (const i64*)ctx->slot_loc.p, (const int*)ctx->slot_cnt.p, nreads, opt->hits_per_smem,
-                       (const i64*)ctx->smem_off.p, (const i64*)ctx->hit_off.p, (meme_mem_tl*)ctx->smems.p,
-                       (u64*)ctx->hits.p);
+                       (const i64*)ctx->seed.slot_loc.p, (const int*)ctx->seed.slot_cnt.p, nreads, opt->hits_per_smem,
+                       (const i64*)ctx->batch.smem_off.p, (const i64*)ctx->batch.hit_off.p, (meme_mem_tl*)ctx->batch.smems.p,
+                       (u64*)ctx->batch.hits.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     float gms = 0.f;
     HIP_TRY(hipEventElapsedTime(&gms, ctx->ev[2], ctx->ev[3]));
     ctx->tm.seed_gather_ms = gms;
-    out->d_smems = (const meme_mem_tl*)ctx->smems.p;
-    out->d_smem_off = (const i64*)ctx->smem_off.p;
-    out->d_hits = (const u64*)ctx->hits.p;
-    out->d_hit_off = (const i64*)ctx->hit_off.p;
+    out->d_smems = (const meme_mem_tl*)ctx->batch.smems.p;
+    out->d_smem_off = (const i64*)ctx->batch.smem_off.p;
+    out->d_hits = (const u64*)ctx->batch.hits.p;
+    out->d_hit_off = (const i64*)ctx->batch.hit_off.p;
     out->total_smems = h_tot[0];
     out->total_hits = h_tot[1];
     out->searches = searches;
@@ -532,14 +532,14 @@ extern "C" int meme_seed_batch(meme_ctx* ctx, const uint8_t* reads, const int64_
     if (nreads == 0) { smem_off[0] = 0; hit_off[0] = 0; if (total_smems) *total_smems = 0; if (total_hits) *total_hits = 0; return MEME_OK; }
     const i64 bases = read_off[nreads] - read_off[0];
     if (read_off[0] != 0) { meme_set_error("read_off[0] must be 0"); return MEME_E_ARG; }
-    if ((rc = meme_buf_reserve(ctx, ctx->reads, (size_t)bases + 16))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->read_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->reads.p, reads, (size_t)bases, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->read_off.p, read_off, (size_t)(nreads + 1) * sizeof(i64), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = meme_buf_reserve(ctx, ctx->batch.reads, (size_t)bases + 16))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->batch.read_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->batch.reads.p, reads, (size_t)bases, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->batch.read_off.p, read_off, (size_t)(nreads + 1) * sizeof(i64), hipMemcpyHostToDevice, ctx->stream));
     meme_seed_result res;
     i64 max_len = 0;
     for (i64 i = 0; i < nreads; ++i) max_len = read_off[i + 1] - read_off[i] > max_len ? read_off[i + 1] - read_off[i] : max_len;
-    rc = launch_seed(ctx, (const uint8_t*)ctx->reads.p, (const i64*)ctx->read_off.p, nreads, max_len, bases, opt, &res);
+    rc = launch_seed(ctx, (const uint8_t*)ctx->batch.reads.p, (const i64*)ctx->batch.read_off.p, nreads, max_len, bases, opt, &res);
     if (rc) return rc;
     if (total_smems) *total_smems = res.total_smems;
     if (total_hits) *total_hits = res.total_hits;
@@ -571,28 +571,30 @@ extern "C" int meme_seed_reserve(meme_ctx* ctx, int64_t nreads, int64_t total_ba
     const i64 len = total_bases / nreads + 32;
     const size_t stride = (size_t)(2 * ((len + 31) / 32 + 2) + 2 * ((len + 63) / 64) + 1);
     int rc;
+    ResidentBatch& B = ctx->batch; SeedWs& S = ctx->seed;
+    ChainWs& C = ctx->chain; ExtWs& E = ctx->ext;
     struct { DevBuf* b; size_t bytes; } dev[] = {
-        {&ctx->reads, (size_t)total_bases + 16}, {&ctx->read_off, (n + 1) * 8}, {&ctx->slot_cnt, n * 4}, {&ctx->slot_hits, n * 8},
-        {&ctx->slot_loc, n * 8}, {&ctx->counters, 2 * 16 * 8}, {&ctx->pend, n * 8}, {&ctx->blk, n * BLK_PER_READ * 2 * sizeof(BlkRec)}, {&ctx->packed, n * stride * 8}, {&ctx->slots[0], n * (size_t)ctx->smem_cap * sizeof(SlotRec)},
-        {&ctx->smem_off, (n + 1) * 8}, {&ctx->hit_off, (n + 1) * 8}, {&ctx->smems, n * 12 * sizeof(meme_mem_tl)}, {&ctx->hits, n * 24 * 8},
-        {&ctx->chain[0], n * 16 * 32}, {&ctx->chain[1], n * 16 * 8 * 16}, {&ctx->chain[2], n * 24}, {&ctx->chain[3], n * 4}, {&ctx->chain[8], n * 8},
-        {&ctx->chain[5], (n + 1) * 32 + n * 5 + 64}, {&ctx->chain[6], n * 3 * sizeof(meme_chain)}, {&ctx->chain[7], n * 6 * sizeof(meme_chain_seed)}};
+        {&B.reads, (size_t)total_bases + 16}, {&B.read_off, (n + 1) * 8}, {&S.slot_cnt, n * 4}, {&S.slot_hits, n * 8},
+        {&S.slot_loc, n * 8}, {&S.counters, 2 * SEED_CTRS * 8}, {&S.pend, n * 8}, {&S.blk, n * BLK_PER_READ * 2 * sizeof(BlkRec)}, {&B.packed, n * stride * 8}, {&S.slots[0], n * (size_t)ctx->smem_cap * sizeof(SlotRec)},
+        {&B.smem_off, (n + 1) * 8}, {&B.hit_off, (n + 1) * 8}, {&B.smems, n * 12 * sizeof(meme_mem_tl)}, {&B.hits, n * 24 * 8},
+        {&C.chains, n * 3 * sizeof(meme_chain)}, {&C.seeds, n * 6 * sizeof(meme_chain_seed)}};
     for (auto& d : dev) if ((rc = meme_buf_reserve(ctx, *d.b, d.bytes))) return rc;
-    struct { meme_ctx::HostBuf* b; size_t bytes; } host[] = {
-        {&ctx->h_smem_off, (n + 1) * 8}, {&ctx->h_hit_off, (n + 1) * 8}, {&ctx->h_smems, n * 12 * sizeof(meme_mem_tl)}, {&ctx->h_hits, n * 24 * 8},
-        {&ctx->h_chain[0], (n + 1) * 8}, {&ctx->h_chain[1], n * 3 * sizeof(meme_chain)}, {&ctx->h_chain[2], (n + 1) * 8},
-        {&ctx->h_chain[3], n * 6 * sizeof(meme_chain_seed)}, {&ctx->h_chain[4], n * 4}, {&ctx->h_chain[5], n * 4}, {&ctx->h_chain[6], n}};
+    if ((rc = meme_chain_reserve(ctx, nreads))) return rc;
+    struct { HostBuf* b; size_t bytes; } host[] = {
+        {&S.h_smem_off, (n + 1) * 8}, {&S.h_hit_off, (n + 1) * 8}, {&S.h_smems, n * 12 * sizeof(meme_mem_tl)}, {&S.h_hits, n * 24 * 8},
+        {&C.h_chain_off, (n + 1) * 8}, {&C.h_chains, n * 3 * sizeof(meme_chain)}, {&C.h_seed_off, (n + 1) * 8},
+        {&C.h_seeds, n * 6 * sizeof(meme_chain_seed)}, {&C.h_tree, n * 4}, {&C.h_frac, n * 4}, {&C.h_fallback, n}};
     for (auto& h : host) if ((rc = meme_hostbuf_reserve(ctx, *h.b, h.bytes))) return rc;
     // the stages behind seeding (meme_extend_last_batch_host, meme_global_batch_host) at their usual sizes for short reads: 4 alignment
     // records and 4 extension jobs of ~250 sequence bytes per read, one global alignment per 3 reads -- the first chunks of a run
     // otherwise pay for growing these (pinned memory: ~0.4 s per GB)
     struct { DevBuf* b; size_t bytes; } dev2[] = {
-        {&ctx->ext[0], n * 3 * 16}, {&ctx->ext[1], n * 4 * sizeof(meme_alnreg)}, {&ctx->ext[2], n * 4 * 4}, {&ctx->ext[3], (n + 1) * 48},
-        {&ctx->ext[4], n * 2 * sizeof(meme_seqpair)}, {&ctx->ext[5], n * 2 * sizeof(meme_seqpair)}, {&ctx->ext[6], n * 4 * sizeof(meme_seqpair)},
-        {&ctx->ext[7], n * 4 * 250}};
+        {&E.rmax, n * 3 * 16}, {&E.regs, n * 4 * sizeof(meme_alnreg)}, {&E.order, n * 4 * 4}, {&E.counts, ExtCounts(nullptr, nreads).bytes},
+        {&E.pairs_l, n * 2 * sizeof(meme_seqpair)}, {&E.pairs_r, n * 2 * sizeof(meme_seqpair)}, {&E.retry, n * 4 * sizeof(meme_seqpair)},
+        {&E.seq, n * 4 * 250}};
     for (auto& d : dev2) if ((rc = meme_buf_reserve(ctx, *d.b, d.bytes))) return rc;
-    if ((rc = meme_hostbuf_reserve(ctx, ctx->h_ext[0], (n + 1) * 8)) || (rc = meme_hostbuf_reserve(ctx, ctx->h_ext[1], n * 4 * sizeof(meme_alnreg))) ||
-        (rc = meme_hostbuf_reserve(ctx, ctx->h_gcig[0], n / 2 * sizeof(meme_gres))) || (rc = meme_hostbuf_reserve(ctx, ctx->h_gcig[1], n * 4))) return rc;
+    if ((rc = meme_hostbuf_reserve(ctx, E.h_reg_off, (n + 1) * 8)) || (rc = meme_hostbuf_reserve(ctx, E.h_regs, n * 4 * sizeof(meme_alnreg))) ||
+        (rc = meme_hostbuf_reserve(ctx, ctx->gcig.h_res, n / 2 * sizeof(meme_gres))) || (rc = meme_hostbuf_reserve(ctx, ctx->gcig.h_ops, n * 4))) return rc;
     return MEME_OK;
 }
 
@@ -628,49 +630,49 @@ static int seed_host_reads(meme_ctx* ctx, const uint8_t* reads, const int64_t* r
     HIP_TRY(hipSetDevice(ctx->device));
     if (out) {
         memset(out, 0, sizeof(*out));
-        if ((rc = meme_hostbuf_reserve(ctx, ctx->h_smem_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
-        if ((rc = meme_hostbuf_reserve(ctx, ctx->h_hit_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
-        out->smem_off = (const int64_t*)ctx->h_smem_off.p;
-        out->hit_off = (const int64_t*)ctx->h_hit_off.p;
+        if ((rc = meme_hostbuf_reserve(ctx, ctx->seed.h_smem_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
+        if ((rc = meme_hostbuf_reserve(ctx, ctx->seed.h_hit_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
+        out->smem_off = (const int64_t*)ctx->seed.h_smem_off.p;
+        out->hit_off = (const int64_t*)ctx->seed.h_hit_off.p;
     }
     if (totals) totals[0] = totals[1] = 0;
-    ctx->last_seed_reads = 0;
-    if (nreads == 0) { if (out) { ((i64*)ctx->h_smem_off.p)[0] = 0; ((i64*)ctx->h_hit_off.p)[0] = 0; } return MEME_OK; }
+    ctx->batch.last_seed_reads = 0;
+    if (nreads == 0) { if (out) { ((i64*)ctx->seed.h_smem_off.p)[0] = 0; ((i64*)ctx->seed.h_hit_off.p)[0] = 0; } return MEME_OK; }
     if (read_off[0] != 0) { meme_set_error("read_off[0] must be 0"); return MEME_E_ARG; }
     const i64 bases = read_off[nreads];
-    if ((rc = meme_buf_reserve(ctx, ctx->reads, (size_t)bases + 16))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->read_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->reads.p, reads, (size_t)bases, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->read_off.p, read_off, (size_t)(nreads + 1) * sizeof(i64), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = meme_buf_reserve(ctx, ctx->batch.reads, (size_t)bases + 16))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->batch.read_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->batch.reads.p, reads, (size_t)bases, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->batch.read_off.p, read_off, (size_t)(nreads + 1) * sizeof(i64), hipMemcpyHostToDevice, ctx->stream));
     if (ascii) {
         const i64 nvec = (bases + 15) / 16;
         i64 cb = (nvec + 255) / 256;
         if (cb > (i64)ctx->n_cus * 16) cb = (i64)ctx->n_cus * 16;
-        hipLaunchKernelGGL(k_ascii_to_codes, dim3((unsigned)(cb < 1 ? 1 : cb)), dim3(256), 0, ctx->stream, (uint4*)ctx->reads.p, nvec);
+        hipLaunchKernelGGL(k_ascii_to_codes, dim3((unsigned)(cb < 1 ? 1 : cb)), dim3(256), 0, ctx->stream, (uint4*)ctx->batch.reads.p, nvec);
         HIP_TRY(hipGetLastError());
     }
     i64 max_len = 0;
     for (i64 i = 0; i < nreads; ++i) max_len = read_off[i + 1] - read_off[i] > max_len ? read_off[i + 1] - read_off[i] : max_len;
     meme_seed_result res;
-    rc = launch_seed(ctx, (const uint8_t*)ctx->reads.p, (const i64*)ctx->read_off.p, nreads, max_len, bases, opt, &res);
+    rc = launch_seed(ctx, (const uint8_t*)ctx->batch.reads.p, (const i64*)ctx->batch.read_off.p, nreads, max_len, bases, opt, &res);
     if (rc) return rc;
     if (out) {
-        if ((rc = meme_hostbuf_reserve(ctx, ctx->h_smems, (size_t)(res.total_smems + 1) * sizeof(meme_mem_tl)))) return rc;
-        if ((rc = meme_hostbuf_reserve(ctx, ctx->h_hits, (size_t)(res.total_hits + 1) * sizeof(u64)))) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->h_smem_off.p, res.d_smem_off, (size_t)(nreads + 1) * sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->h_hit_off.p, res.d_hit_off, (size_t)(nreads + 1) * sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->h_smems.p, res.d_smems, (size_t)res.total_smems * sizeof(meme_mem_tl), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->h_hits.p, res.d_hits, (size_t)res.total_hits * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-        out->smems = (const meme_mem_tl*)ctx->h_smems.p;
-        out->hits = (const uint64_t*)ctx->h_hits.p;
+        if ((rc = meme_hostbuf_reserve(ctx, ctx->seed.h_smems, (size_t)(res.total_smems + 1) * sizeof(meme_mem_tl)))) return rc;
+        if ((rc = meme_hostbuf_reserve(ctx, ctx->seed.h_hits, (size_t)(res.total_hits + 1) * sizeof(u64)))) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->seed.h_smem_off.p, res.d_smem_off, (size_t)(nreads + 1) * sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->seed.h_hit_off.p, res.d_hit_off, (size_t)(nreads + 1) * sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->seed.h_smems.p, res.d_smems, (size_t)res.total_smems * sizeof(meme_mem_tl), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->seed.h_hits.p, res.d_hits, (size_t)res.total_hits * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+        out->smems = (const meme_mem_tl*)ctx->seed.h_smems.p;
+        out->hits = (const uint64_t*)ctx->seed.h_hits.p;
         out->total_smems = res.total_smems;
         out->total_hits = res.total_hits;
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));             // (the caller's read buffer is free again)
     if (totals) { totals[0] = res.total_smems; totals[1] = res.total_hits; }
-    ctx->last_seed_reads = nreads;
-    ctx->reads_resident = true;
-    ctx->last_seed_max_len = max_len;
+    ctx->batch.last_seed_reads = nreads;
+    ctx->batch.reads_resident = true;
+    ctx->batch.last_seed_max_len = max_len;
     return MEME_OK;
 }
 
