@@ -732,20 +732,17 @@ int launch_bsw(meme_ctx* ctx, meme_seqpair* d_pairs, const uint8_t* d_ref, const
                const meme_bsw_opt* opt, int host_maxq) {
     if (opt->e_ins <= 0 || opt->e_del <= 0) { meme_set_error("gap extension penalties must be positive"); return MEME_E_ARG; }
     int rc;
-    // counters (ints): [0..SORT_KEYS) histogram by query length, [SORT_KEYS..2*SORT_KEYS] exclusive offsets (+ total),
-    // then the scatter cursors, the longest query of the pairs the lane kernel cannot take, and the kernels' tickets
-    const size_t n_ints = 3 * (size_t)SORT_KEYS + 32;
-    if ((rc = meme_buf_reserve(ctx, ctx->bsw.hist, n_ints * sizeof(int)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->bsw.hist, BswSort(nullptr, SORT_KEYS).bytes))) return rc;
     if ((rc = meme_buf_reserve(ctx, ctx->bsw.order, (size_t)npairs * sizeof(int)))) return rc;
-    int* hist = (int*)ctx->bsw.hist.p;
-    int* offs = hist + SORT_KEYS;
-    int* cursor = offs + SORT_KEYS + 1;
-    int* maxq = cursor + SORT_KEYS;
-    unsigned int* tickets = (unsigned int*)(maxq + 1);
+    const BswSort bs(ctx->bsw.hist.p, SORT_KEYS);
+    int *hist = bs.hist, *offs = bs.offs, *cursor = bs.cursor, *maxq = bs.maxq;
+    unsigned int* tickets = bs.tickets;
     int* order = (int*)ctx->bsw.order.p;
     const i64 dev_cus = ctx->n_cus;
-    HIP_TRY(hipMemsetAsync(hist, 0, n_ints * sizeof(int), ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    Events<2>& ev = ctx->bsw.ev;
+    for (int i = 0; i < 2; ++i) if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
+    HIP_TRY(hipMemsetAsync(hist, 0, bs.bytes, ctx->stream));
+    HIP_TRY(hipEventRecord(ev[0], ctx->stream));
     // big batches: one pair per lane (throughput).  Small batches (the reference's 512-read call granularity): 16-64
     // lanes per pair, because a lone pair on one lane takes milliseconds.
     // (the lane kernel keeps a row's substitution scores as signed bytes)
@@ -829,7 +826,7 @@ int launch_bsw(meme_ctx* ctx, meme_seqpair* d_pairs, const uint8_t* d_ref, const
             if ((rc = launch_cls<64>(ctx, A, ((mq + 63) / 64) * 64, dev_cus))) return rc;
         }
     }
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
+    HIP_TRY(hipEventRecord(ev[1], ctx->stream));
     ctx->tm.bsw_launches = 1;
     return MEME_OK;
 }
@@ -837,12 +834,14 @@ int launch_bsw(meme_ctx* ctx, meme_seqpair* d_pairs, const uint8_t* d_ref, const
 int finish_bsw(meme_ctx* ctx) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
+    HIP_TRY(meme_bsw_last_ms(ctx, &ms));
     ctx->tm.bsw_kernel_ms = ms;
     return MEME_OK;
 }
 
 }  // namespace
+
+hipError_t meme_bsw_last_ms(meme_ctx* ctx, float* ms) { return hipEventElapsedTime(ms, ctx->bsw.ev[0], ctx->bsw.ev[1]); }
 
 int meme_bsw_launch(meme_ctx* ctx, meme_seqpair* d_pairs, const uint8_t* d_ref, const uint8_t* d_qer, int npairs, int w, const meme_bsw_opt* opt,
                     int host_maxq) {

@@ -1397,7 +1397,7 @@ int meme_chain_run(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs,
     if ((rc = meme_stage_contigs(ctx, C.contigs, tab, contigs, n_contigs, opt->l_pac, true, "", &ct))) return rc;
     // however this function is left (the error returns below included), the kernels on the side streams have finished: a caller that
     // retries with a smaller batch or destroys the ctx must not race them
-    struct SideGuard { meme_ctx* c; ~SideGuard() { for (auto st : c->stream_side) if (st) (void)hipStreamSynchronize(st); } } side_guard{ctx};
+    struct SideGuard { meme_ctx* c; ~SideGuard() { for (Stream& st : c->side.st) if (st.s) (void)hipStreamSynchronize(st); } } side_guard{ctx};
     if ((rc = meme_chain_reserve(ctx, n))) return rc;
     const ChainCounts cc(C.counts.p, n);
     HIP_TRY(hipMemsetAsync(cc.route, 0, 64, ctx->stream));
@@ -1416,11 +1416,7 @@ int meme_chain_run(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs,
     A.cls = L.cls;
     Events<5>& ev = C.ev;
     for (int i = 0; i < 5; ++i) if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
-    for (int i = 0; i < 3; ++i) {
-        { const int src = meme_side_stream(ctx, i); if (src) return src; }     // (tuning "chain_side_priority": the routed tiers' streams above the lane tier's in the hardware queues)
-        if (!ctx->ev_side[i]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_side[i], hipEventDisableTiming));
-    }
-    if (!ctx->ev_aux) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_aux, hipEventDisableTiming));
+    for (int i = 0; i < 3; ++i) if ((rc = meme_side_stream(ctx, i))) return rc;
     HIP_TRY(hipEventRecord(ev[0], ctx->stream));
     // ---- route by work
     const i64 never = (i64)1 << 60;
@@ -1437,15 +1433,15 @@ int meme_chain_run(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs,
     for (int k = 0; k < 3; ++k) if (nl[k] > 0) { if ((rc = meme_scan_exclusive(ctx, L.work[k], L.woff[k], nl[k]))) return rc; HIP_TRY(hipMemcpyAsync(&tw[k], L.woff[k] + nl[k], 8, hipMemcpyDeviceToHost, ctx->stream)); }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < 3; ++k) if (nl[k] > 0) { if ((rc = make_set(ctx, C.wave[k], L.list[k], L.woff[k], nl[k], tw[k], 1 + k, false, &W[k]))) return rc; used[k] = true; }
-    HIP_TRY(hipEventRecord(ctx->ev_aux, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->side.fork[0], ctx->stream));
     // ---- four launches at once (the longest-running first)
     for (int k = 2; k >= 0; --k) {
         if (nl[k] <= 0) continue;
-        HIP_TRY(hipStreamWaitEvent(ctx->stream_side[k], ctx->ev_aux, 0));
-        if (k == 2) hipLaunchKernelGGL((k_chain_lds<1024>), dim3((unsigned)nl[k]), dim3(64), 0, ctx->stream_side[k], A, W[k]);
-        else if (k == 1) hipLaunchKernelGGL((k_chain_lds<512>), dim3((unsigned)nl[k]), dim3(64), 0, ctx->stream_side[k], A, W[k]);
-        else hipLaunchKernelGGL((k_chain_lds<256>), dim3((unsigned)nl[k]), dim3(64), 0, ctx->stream_side[k], A, W[k]);
-        HIP_TRY(hipEventRecord(ctx->ev_side[k], ctx->stream_side[k]));
+        HIP_TRY(hipStreamWaitEvent(ctx->side.st[k], ctx->side.fork[0], 0));
+        if (k == 2) hipLaunchKernelGGL((k_chain_lds<1024>), dim3((unsigned)nl[k]), dim3(64), 0, ctx->side.st[k], A, W[k]);
+        else if (k == 1) hipLaunchKernelGGL((k_chain_lds<512>), dim3((unsigned)nl[k]), dim3(64), 0, ctx->side.st[k], A, W[k]);
+        else hipLaunchKernelGGL((k_chain_lds<256>), dim3((unsigned)nl[k]), dim3(64), 0, ctx->side.st[k], A, W[k]);
+        HIP_TRY(hipEventRecord(ctx->side.done[k], ctx->side.st[k]));
     }
     hipLaunchKernelGGL((k_chain<CHAIN_CAP, SEED_CAP>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, A);
     HIP_TRY(hipEventRecord(ev[1], ctx->stream));
@@ -1463,7 +1459,7 @@ int meme_chain_run(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs,
         if (wave_tiers) hipLaunchKernelGGL((k_chain_lds<256>), dim3((unsigned)nl[3]), dim3(64), 0, ctx->stream, A, W[3]);
         else hipLaunchKernelGGL((k_chain_wave<288, 2048>), dim3((unsigned)nl[3]), dim3(64), 0, ctx->stream, A, W[3], (i64)0);
     }
-    for (int k = 0; k < 3; ++k) if (nl[k] > 0) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_side[k], 0));
+    for (int k = 0; k < 3; ++k) if (nl[k] > 0) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->side.done[k], 0));
     HIP_TRY(hipEventRecord(ev[4], ctx->stream));
     // ---- the B-tree tier for what is left (fallback == 3)
     hipLaunchKernelGGL(k_chain_redo, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, (const ReadHdr*)C.hdr.p, n, 3, (const unsigned char*)nullptr, cc.route + 4, L.list[4], L.work[4]);

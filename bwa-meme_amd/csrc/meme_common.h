@@ -68,6 +68,13 @@ template <int N> struct Events {    // events of a stage, created on first use, 
     ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
     hipEvent_t& operator[](int i) { return e[i]; }
 };
+struct Stream {                     // a stream besides the caller's, created on first use, destroyed with its owner
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete; Stream& operator=(const Stream&) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
 
 // Packed layouts: typed arrays carved out of one allocation in order.  The same code gives the total bytes (base == nullptr) and the pointers.
 struct Carve {
@@ -99,10 +106,15 @@ struct ExtRounds {     // extension in rounds: per-read state, reads still activ
     ExtRounds(void* base, i64 n, i64 seeds) { Carve c(base); state = c.take<int4>(n + 1); act = c.take<uint8_t>(n + 1); sel = c.take<uint8_t>(seeds + 64); bytes = c.bytes; }
 };
 struct GcigCols {      // per CIGAR job: sizes, scans, the DP list and its classes; then the first bad job
-    i64 *zsz, *csz, *zoff, *coff, *ncig, *ooff, *msz, *moff, *psz, *poff, *isdp, *dpoff, *dplist, *is16, *o16, *is32, *o32, *is64, *o64, *is128, *o128, *bad; size_t bytes;
+    i64 *zsz, *csz, *zoff, *coff, *ncig, *ooff, *msz, *moff, *psz, *poff, *isdp, *dpoff, *dplist, *is16, *o16, *is32, *o32, *is64, *o64, *bad; size_t bytes;
     GcigCols(void* base, i64 n) { Carve c(base); zsz = c.col(n); csz = c.col(n); zoff = c.col(n); coff = c.col(n); ncig = c.col(n); ooff = c.col(n); msz = c.col(n); moff = c.col(n);
         psz = c.col(n); poff = c.col(n); isdp = c.col(n); dpoff = c.col(n); dplist = c.col(n); is16 = c.col(n); o16 = c.col(n); is32 = c.col(n); o32 = c.col(n); is64 = c.col(n);
-        o64 = c.col(n); is128 = c.col(n); o128 = c.col(n); bad = c.take<i64>(8); bytes = c.bytes; }
+        o64 = c.col(n); bad = c.take<i64>(8); bytes = c.bytes; }
+};
+struct BswSort {       // query-length sort of a banded-SW batch (ints, cleared as one block): histogram, exclusive offsets (+ total), scatter cursors, the longest query of the
+                       // pairs the lane kernel cannot take, the kernels' tickets
+    int *hist, *offs, *cursor, *maxq; unsigned int* tickets; size_t bytes;
+    BswSort(void* base, int keys) { Carve c(base); hist = c.take<int>(keys); offs = c.take<int>(keys + 1); cursor = c.take<int>(keys); maxq = c.take<int>(1); tickets = c.take<unsigned int>(30); bytes = c.bytes; }
 };
 struct MateCounts {    // gar entries, jobs, window bases and query bases per read, and their scans
     i64 *cntQ, *cntJ, *cntR, *cntY, *offQ, *offJ, *offR, *offY; size_t bytes;
@@ -122,12 +134,18 @@ struct ResidentBatch {
     i64 last_seed_max_len = 0;         // longest read of that batch
     bool reads_resident = false;       // reads holds the bases of that batch (false after meme_chain_batch_host: seeds brought by the caller)
 };
-enum { SEED_CTR_OVERFLOW = 2, SEED_CTR_BLK = 14, SEED_CTR_BLK_OUT = 15, SEED_CTRS = 16 };   // a seeding counter set (u64): reads left for the next tier, blocked-region cursors
+// a seeding counter set (u64): slot cursor of the tier, searches, reads left for the next tier (the length of its overflow list), window loads, eight SEED_PROF sums,
+// searches of the re-seeding kernels' lanes, length of the pending list, the two blocked-region cursors
+enum { SEED_CTR_SLOT = 0, SEED_CTR_SEARCHES = 1, SEED_CTR_OVERFLOW = 2, SEED_CTR_WINDOWS = 3, SEED_CTR_PROF = 4, SEED_CTR_LANE = 12, SEED_CTR_PEND = 13, SEED_CTR_BLK = 14, SEED_CTR_BLK_OUT = 15,
+       SEED_CTRS = 16 };
+enum { SEED_EV_PACK0, SEED_EV_PACK1, SEED_EV_SEARCH0, SEED_EV_SEARCH1, SEED_EV_RESEED0, SEED_EV_GATHER0, SEED_EV_GATHER1, SEED_EVS };   // SeedWs::ev: begin / end of packing, of a tier's search, begin of re-seeding, begin / end of offsets + gather
 struct SeedWs {
     DevBuf slots[3], ovf[2];           // SMEM slots of a tier; reads that overflow it (tier & 1)
     DevBuf slot_cnt, slot_hits, slot_loc, counters, pend, blk;
     HostBuf h_smems, h_hits, h_smem_off, h_hit_off;   // results of meme_seed_batch_host
     unsigned long long* counter_set(int cset) { return (unsigned long long*)counters.p + SEED_CTRS * cset; }   // two sets: an overflow tier may run beside the re-seeding kernels
+    Events<SEED_EVS> ev;
+    Stream emit; Events<2> emit_ev;    // k_reseed_emit runs beside the blocked regions' rounds: its stream, fork [0] and join [1]
 };
 struct ChainWs {
     DevBuf ch1, sd1, hdr, frac, contigs, counts, chains, seeds, lists;   // lane-tier chains / seeds, read headers, frac_rep, ContigTab, ChainCounts, packed chains / seeds, ChainLists
@@ -144,7 +162,7 @@ struct ExtWs {
     DevBuf live_cnt, live_regs, rounds, heavy;                                 // surviving records (counts + scan, packed), ExtRounds, the heavy reads
     HostBuf h_reg_off, h_regs; Events<2> ev;
 };
-struct BswWs { DevBuf pairs, refb, qerb, order, ws, hist; };   // hist: histogram, offsets, cursors, longest query and tickets of the query-length sort
+struct BswWs { DevBuf pairs, refb, qerb, order, ws, hist; Events<2> ev; };   // hist: BswSort; ev: begin / end of the last meme_bsw_launch
 struct GcigWs {        // cols: GcigCols; cig: CIGAR scratch, ops: packed; nm: nm + mdlen
     DevBuf jobs, cols, z, cig, res, ops, md, nm, md_packed, cjobs, cres; HostBuf h_res, h_ops, h_md; Events<2> ev;
 };
@@ -158,10 +176,15 @@ struct SamWs {         // cols: SamCols; contigs: contig name offsets + names + 
     DevBuf names, name_off, quals, recs, blob, cols, scratch, text, contigs; HostBuf h_text_off, h_text; Events<2> ev;
 };
 
+struct SideStreams {   // beside ctx->stream: the routed chaining tiers, the early overflow tier of seeding (meme_side_stream creates stream i with its event)
+    Stream st[3];
+    Events<3> done;    // done[i]: what was launched on st[i] has finished
+    Events<1> fork;    // recorded on ctx->stream where the side streams start
+};
+
 struct meme_ctx {
     int device = 0;
     int n_cus = 256;                   // compute units of the device (cached: hipGetDeviceProperties is slow)
-    hipStream_t stream = nullptr;
     DevIndex idx;
     bool owns_index = false;
     std::vector<std::pair<void*, size_t>> owned;   // device allocations of the index (pointer, bytes)
@@ -169,7 +192,12 @@ struct meme_ctx {
     // workspaces (scan_tmp: tiles of the prefix sums, meme_scan_exclusive and the seeding gather)
     ResidentBatch batch;
     DevBuf scan_tmp;
-    SeedWs seed; ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam;
+    ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam; SeedWs seed;
+    // Streams.  Order of destruction: meme_ctx_destroy synchronises every stream of the ctx; then the members go in reverse order of declaration, so the streams
+    // and their fork / join events -- these two and, last member of the last workspace, the seeding stage's -- are destroyed BEFORE any DevBuf / HostBuf above is
+    // freed.  A new stream holder goes below the buffers too: here, or last in SeedWs.  (A stage's timing events go with the stage; they are idle by then.)
+    Stream stream;
+    SideStreams side;
     // tuning
     i64 seed_blocks = 0;               // 0 = auto
     i64 smem_cap = 128;                // per-read SMEM slots in the search kernel's scratch (tier 0; 3 KB per read.  With 64 a handful of
@@ -181,41 +209,28 @@ struct meme_ctx {
     i64 ext_split = 1;                 // 1: the extension stage's read-walking kernels run eight lanes per read for reads with at most 8 chained seeds, a wavefront per read for the rest; 0: a wavefront per read
     i64 bsw_circ = 1;                  // 1: lane-per-pair banded SW of queries longer than 2w + 2 columns keeps its columns in a ring (k_bsw_lane_circ); 0: a word per query column
     i64 sam_max_batch = 0;             // > 0: meme_sam_format_batch_host refuses more record slots than this with MEME_E_CAPACITY (the caller then formats in pieces)
-    i64 seed_early_tier = 1;           // 1: the overflow tier of the reads known to have overflowed after k_reseed runs beside the re-seeding batches
     i64 ext_live_only = 0;             // 1: meme_extend_last_batch_host hands over the surviving records only (qe > qb: what src/bwamem.cpp:1680-1693 keeps)
     i64 ext_rounds = 1;                // with ext_live_only: rounds of one seed per read before everything still ahead is extended at once (0: the reference's batch, then compaction)
-    i64 gcig_groups = 1;               // 1: CIGAR jobs with bands of at most 16 / 32 / 64 columns run 4 / 2 / 1 to a wavefront as one chunk per row (k_gcig_grp); 0: a wavefront each, 64-column chunks; 2: also bands of 65-128 columns as one chunk, two columns per lane (measured slower: off by default)
+    i64 gcig_groups = 1;               // 1: CIGAR jobs with bands of at most 16 / 32 / 64 columns run 4 / 2 / 1 to a wavefront as one chunk per row (k_gcig_grp); 0: a wavefront each, 64-column chunks
     i64 gcig_zcap = -1;                // >= 0: bytes of LDS per CIGAR job for its backtrack matrix / window (default: 8192 where a typical matrix of the batch fits, else 2048)
     i64 ext_census = 0;                // 1: the extension stage counts its exact-prefix jobs (a measurement, profiles/r05_bsw.md)
     i64 seed_defer = 1;                // 1: re-seeding regions of unique SMEMs are verified on the plcp table (k_reseed) instead of searched
     i64 chain_light_hits = 32;         // reads with more hits to walk skip the lane-per-read tier: LDS tier at once, beside it
     i64 chain_lane_hits = 256;         // hits per read the lane-per-read chaining tier walks; reads with more go to the wavefront tiers at once
-    i64 chain_side_priority = 0;       // 1: the side streams of the routed chaining tiers are created with the highest stream priority (set before the first chaining call)
     i64 chain_wave_tiers = 1;          // 0: the chaining stage skips the LDS tier (everything beyond the lane tier through the B-tree tier; tests)
     i64 bsw_blocks = 0;
     i64 bsw_lane_min_pairs = 32768;   // batches at least this big use the lane-per-pair kernel (throughput); smaller ones the
                                        // lanes-per-pair kernel (latency: a lone pair takes ~6 ms on one lane, ~0.3 ms on 64)
     // timings
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     i64 sam_text_reads = 0;            // reads of the batch whose names / qualities meme_sam_stage_text staged (0: none)
     bool sam_has_quals = false;
-    hipStream_t stream_side[3] = {nullptr, nullptr, nullptr};   // the routed chaining tiers run beside the lane-per-read tier
-    hipEvent_t ev_side[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_aux = nullptr;
-    hipStream_t stream_emit = nullptr;                          // k_reseed_emit runs beside the blocked regions' rounds
-    hipEvent_t ev_emit[2] = {nullptr, nullptr};
     i64 chain_reads = 0, chain_tier2_reads = 0, chain_tier3_reads = 0;   // of the last meme_chain_run(): reads chained, of which by the wavefront-per-read tier
     meme_timings tm = {};
-    ~meme_ctx() {                      // the ctx's own events and streams; the stages release theirs, every workspace frees itself
-        for (hipEvent_t e : {ev[0], ev[1], ev[2], ev[3], ev[4], ev[5], ev[6], ev[7], ev_side[0], ev_side[1], ev_side[2], ev_aux, ev_emit[0], ev_emit[1]}) if (e) (void)hipEventDestroy(e);
-        for (hipStream_t st : {stream_side[0], stream_side[1], stream_side[2], stream_emit, stream}) if (st) (void)hipStreamDestroy(st);
-    }
 };
 
 void meme_set_error(const char* fmt, ...);
 int meme_buf_reserve(meme_ctx* ctx, DevBuf& b, size_t bytes);
-// side stream i of the ctx (the routed chaining tiers, the early overflow tier of seeding), created on first use -- ONE place, so that the tuning
-// "chain_side_priority" applies to all three whichever stage touches a stream first (advisor, round 5)
+// side stream i of the ctx with its "done" event, and the fork event, created on first use
 int meme_side_stream(meme_ctx* ctx, int i);
 int meme_hostbuf_reserve(meme_ctx* ctx, HostBuf& b, size_t bytes);
 // workgroups of a grid-stride launch over `items`, `per` to a workgroup: at least one, at most `cap` (256 x 64: 64 per CU of a 256-CU device)
@@ -229,6 +244,8 @@ int meme_scan_exclusive(meme_ctx* ctx, const i64* d_in, i64* d_out, i64 n);
 // the banded-SW kernels on device-resident pairs, no host synchronisation (meme_bsw.hip); host_maxq = an upper bound of the query lengths or -1
 int meme_bsw_launch(meme_ctx* ctx, meme_seqpair* d_pairs, const uint8_t* d_ref, const uint8_t* d_qer, int npairs, int w, const meme_bsw_opt* opt,
                     int host_maxq);
+// GPU time of the last meme_bsw_launch on the ctx, once ctx->stream has passed it
+hipError_t meme_bsw_last_ms(meme_ctx* ctx, float* ms);
 // local alignment scores of the jobs mem_flt_chained_seeds poses (meme_kswv.hip): window [rb, rb + tlen) of the text against the tlen x qlen
 // bases at reads[qoff]; sc[seed] = score.  The job count is read on the device; max_jobs sizes the launch.
 constexpr int MEME_SEEDSW_MAX = 200;    // MEM_SHORT_LEN, src/bwamem.cpp:250: windows are shorter

@@ -37,12 +37,10 @@ int meme_buf_reserve(meme_ctx* ctx, DevBuf& b, size_t bytes) {
 }
 
 int meme_side_stream(meme_ctx* ctx, int i) {
-    if (ctx->stream_side[i]) return MEME_OK;
-    int lo = 0, hi = 0;
-    if (ctx->chain_side_priority && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo)
-        HIP_TRY(hipStreamCreateWithPriority(&ctx->stream_side[i], hipStreamNonBlocking, hi));
-    else
-        HIP_TRY(hipStreamCreateWithFlags(&ctx->stream_side[i], hipStreamNonBlocking));
+    SideStreams& S = ctx->side;
+    if (!S.st[i].s) HIP_TRY(hipStreamCreateWithFlags(&S.st[i].s, hipStreamNonBlocking));
+    if (!S.done[i]) HIP_TRY(hipEventCreateWithFlags(&S.done[i], hipEventDisableTiming));
+    if (!S.fork[0]) HIP_TRY(hipEventCreateWithFlags(&S.fork[0], hipEventDisableTiming));
     return MEME_OK;
 }
 
@@ -85,13 +83,10 @@ extern "C" meme_ctx* meme_ctx_create(int device) {
     meme_ctx* ctx = new meme_ctx();
     ctx->device = device;
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ctx->n_cus = prop.multiProcessorCount; }
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
+    if (hipStreamCreateWithFlags(&ctx->stream.s, hipStreamNonBlocking) != hipSuccess) {
         meme_set_error("hipStreamCreate failed");
         delete ctx;
         return nullptr;
-    }
-    for (auto& e : ctx->ev) {
-        if (hipEventCreate(&e) != hipSuccess) { meme_set_error("hipEventCreate failed"); delete ctx; return nullptr; }
     }
     return ctx;
 }
@@ -99,7 +94,7 @@ extern "C" meme_ctx* meme_ctx_create(int device) {
 extern "C" void meme_ctx_destroy(meme_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    for (hipStream_t st : {ctx->stream, ctx->stream_side[0], ctx->stream_side[1], ctx->stream_side[2], ctx->stream_emit})
+    for (hipStream_t st : {ctx->stream.s, ctx->side.st[0].s, ctx->side.st[1].s, ctx->side.st[2].s, ctx->seed.emit.s})   // every stream of the ctx, before anything is freed
         if (st) (void)hipStreamSynchronize(st);
     if (ctx->owns_index) for (auto& o : ctx->owned) (void)hipFree(o.first);
     if (ctx->plcp_aux) (void)hipFree(ctx->plcp_aux);
@@ -150,14 +145,15 @@ extern "C" int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value) {
     else if (!strcmp(key, "ext_split")) ctx->ext_split = value;
     else if (!strcmp(key, "ext_census")) ctx->ext_census = value;
     else if (!strcmp(key, "gcig_zcap")) ctx->gcig_zcap = value;
-    else if (!strcmp(key, "gcig_groups")) ctx->gcig_groups = value;
+    else if (!strcmp(key, "gcig_groups")) {
+        if (value != 0 && value != 1) { meme_set_error("gcig_groups must be 0 or 1"); return MEME_E_ARG; }
+        ctx->gcig_groups = value;
+    }
     else if (!strcmp(key, "ext_live_only")) ctx->ext_live_only = value;
     else if (!strcmp(key, "ext_rounds")) ctx->ext_rounds = value < 0 ? 0 : value;
-    else if (!strcmp(key, "seed_early_tier")) ctx->seed_early_tier = value;
     else if (!strcmp(key, "bsw_blocks")) ctx->bsw_blocks = value;
     else if (!strcmp(key, "bsw_lane_min_pairs")) ctx->bsw_lane_min_pairs = value;
     else if (!strcmp(key, "chain_wave_tiers")) ctx->chain_wave_tiers = value;
-    else if (!strcmp(key, "chain_side_priority")) ctx->chain_side_priority = value;
     else if (!strcmp(key, "chain_lane_hits")) ctx->chain_lane_hits = value;
     else if (!strcmp(key, "chain_light_hits")) ctx->chain_light_hits = value;
     else if (!strcmp(key, "group_lanes")) {

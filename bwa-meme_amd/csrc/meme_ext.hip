@@ -850,7 +850,7 @@ extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* con
                     unsigned long long h_retry = 0;
                     HIP_TRY(hipMemcpyAsync(&h_retry, d_nretry, 8, hipMemcpyDeviceToHost, ctx->stream));
                     HIP_TRY(hipStreamSynchronize(ctx->stream));
-                    { float ms = 0.f; if (hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]) == hipSuccess) bsw_ms += ms; }
+                    { float ms = 0.f; if (meme_bsw_last_ms(ctx, &ms) == hipSuccess) bsw_ms += ms; }
                     n_pairs += np; ++n_calls;
                     if (attempt > 0) n_retried += np;
                     P = F.retry;

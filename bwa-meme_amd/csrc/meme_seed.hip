@@ -184,285 +184,326 @@ int launch_k_seed(hipStream_t stream, const SeedArgs& A, size_t lds, i64 blocks)
     return MEME_OK;
 }
 
-int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i64 nreads, i64 max_len, i64 total_bytes,
-                const meme_seed_opt* opt, meme_seed_result* out) {
-    unsigned long long h_counters[SEED_CTRS];
-    int rc;
-    ctx->batch.last_seed_reads = 0;          // whatever batch meme_chain_last_batch_host could have chained is being overwritten
-    ctx->sam_text_reads = 0;           // ... and the names / qualities staged for it belong to the previous batch
-    if ((rc = meme_buf_reserve(ctx, ctx->seed.slot_cnt, (size_t)nreads * sizeof(int)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->seed.slot_hits, (size_t)nreads * sizeof(i64)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->seed.slot_loc, (size_t)nreads * sizeof(i64)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->seed.counters, 2 * SEED_CTRS * sizeof(unsigned long long)))) return rc;
-    const int dev_cus = ctx->n_cus;
-    // ---- pack the reads: 2 bits/base, both strands, N masks (k_pack_reads) ---------------------------------
+// ---- one seeding call, in phases ----------------------------------------------------------------------------
+// What the phases share.
+struct SeedRun {
+    meme_ctx* ctx;
+    const i64* d_read_off; i64 nreads;
+    const meme_seed_opt* opt;
+    PackGeom geo;
+    TierTable tiers = {};              // where every tier that ran keeps its slots (k_gather)
+    bool defer = false;                // tier 0 leaves the re-seeding regions of unique SMEMs to k_reseed
+    i64 n_early = -1;                  // reads of the tier-1 launch that ran beside the re-seeding kernels (-1: none did)
+    i64 n_todo = 0;                    // reads the last tier left to the next one
+    float ms_total = 0.f, ms_reseed = 0.f;
+    i64 launches = 0, searches = 0, windows = 0, lane_searches = 0;
+};
+
+// pack the reads: 2 bits/base, both strands, N masks (k_pack_reads)
+int seed_pack(SeedRun& R, const uint8_t* d_reads, i64 max_len, i64 total_bytes) {
+    meme_ctx* ctx = R.ctx;
     // the reference exits on reads longer than LEARNED_MAX_READ_LEN (src/bwamem.cpp:1259-1262): fail loudly, never seed part of a batch
     if (max_len > MAX_READ_LEN) {
         meme_set_error("read of %lld bases exceeds the learned-index limit of %d (LEARNED_MAX_READ_LEN)", (long long)max_len, MAX_READ_LEN);
         return MEME_E_ARG;
     }
-    if (max_len < 1) max_len = 1;
-    const i64 stage_len = max_len;                                // longest read as staged by the packing kernel
-    PackGeom geo;
+    if (max_len < 1) max_len = 1;                                 // longest read as staged by the packing kernel
+    PackGeom& geo = R.geo;
     geo.W = (int)((max_len + 31) / 32) + 2;
     geo.MW = (int)((max_len + 63) / 64);
     geo.stride = 2 * geo.W + 2 * geo.MW + 1;
-    if ((rc = meme_buf_reserve(ctx, ctx->batch.packed, (size_t)nreads * geo.stride * 8))) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev[6], ctx->stream));
-    {
-        int rb = (int)((48 * 1024) / stage_len);                    // reads per workgroup: <= 48 KB of staged bytes
-        if (rb > 32) rb = 32;
-        if (rb < 1) rb = 1;
-        i64 pblocks = (nreads + rb - 1) / rb;
-        if (pblocks > (i64)dev_cus * 16) pblocks = (i64)dev_cus * 16;   // grid-stride beyond that
-        size_t plds = ((size_t)rb * (size_t)stage_len + 16 + 48 + 3) & ~(size_t)3;   // + the packer's 9-dword reads past a read's last word
-        hipLaunchKernelGGL(k_pack_reads, dim3((unsigned)pblocks), dim3(256), plds, ctx->stream, d_reads,
-                           d_read_off, nreads, total_bytes, geo, rb, (u64*)ctx->batch.packed.p);
-        HIP_TRY(hipGetLastError());
+    int rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->batch.packed, (size_t)R.nreads * geo.stride * 8))) return rc;
+    HIP_TRY(hipEventRecord(ctx->seed.ev[SEED_EV_PACK0], ctx->stream));
+    int rb = (int)((48 * 1024) / max_len);                        // reads per workgroup: <= 48 KB of staged bytes
+    if (rb > 32) rb = 32;
+    if (rb < 1) rb = 1;
+    i64 pblocks = (R.nreads + rb - 1) / rb;
+    if (pblocks > (i64)ctx->n_cus * 16) pblocks = (i64)ctx->n_cus * 16;   // grid-stride beyond that
+    size_t plds = ((size_t)rb * (size_t)max_len + 16 + 48 + 3) & ~(size_t)3;   // + the packer's 9-dword reads past a read's last word
+    hipLaunchKernelGGL(k_pack_reads, dim3((unsigned)pblocks), dim3(256), plds, ctx->stream, d_reads,
+                       R.d_read_off, R.nreads, total_bytes, geo, rb, (u64*)ctx->batch.packed.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->seed.ev[SEED_EV_PACK1], ctx->stream));
+    return MEME_OK;
+}
+
+// One k_seed launch of a tier: `n_todo` reads (tier 0: the batch; overflow tiers: the reads named in `pending`), SMEM slots in
+// ctx->seed.slots[tier], the reads that overflow THIS tier appended to ctx->seed.ovf[tier & 1], counters in set `cset`.
+int launch_tier(SeedRun& R, int tier, i64 n_todo, const i64* pending, int cset, hipStream_t stream, bool defer) {
+    meme_ctx* ctx = R.ctx;
+    // overflow tiers hold a 512-entry SMEM ring per read in LDS: run them 32 lanes per read (8 reads per block)
+    int G = tier == 0 ? (int)ctx->group_lanes : 32;
+    const int cap = tier == 0 ? (int)ctx->smem_cap : TIER_CAP[tier];
+    const int lcap = cap < TIER_LCAP[tier] ? cap : TIER_LCAP[tier];
+    DevBuf& sb = ctx->seed.slots[tier];
+    DevBuf& ob = ctx->seed.ovf[tier & 1];
+    const size_t need = (size_t)n_todo * cap * sizeof(SlotRec);
+    if (tier > 0 && need > sb.cap) {
+        // overflow tiers re-run the reads that emitted more SMEMs than their slots hold, with 32 x more slots each:
+        // refuse instead of exhausting the HBM the index lives in
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b / 2) {
+            meme_set_error("%lld reads emitted more than %d SMEMs each: re-running them needs %.1f GB of slots, more than half of the "
+                           "free HBM (%.1f GB); seed this batch in smaller pieces", (long long)n_todo, R.tiers.cap[tier - 1],
+                           need / 1e9, free_b / 1e9);
+            return MEME_E_CAPACITY;
+        }
     }
-    HIP_TRY(hipEventRecord(ctx->ev[7], ctx->stream));
-    float ms_total = 0.f, ms_reseed = 0.f;
-    i64 launches = 0, searches = 0, windows = 0, lane_searches = 0;
-    TierTable tiers;
-    for (int t = 0; t < N_TIERS; ++t) { tiers.base[t] = nullptr; tiers.cap[t] = 0; }
-    // One k_seed launch of a tier: `n_todo` reads (tier 0: the batch; overflow tiers: the reads named in `pending`), SMEM slots in
-    // ctx->seed.slots[tier], the reads that overflow THIS tier appended to ctx->seed.ovf[tier & 1], counters in set `cset`.
-    auto launch_tier = [&](int tier, i64 n_todo, const i64* pending, int cset, hipStream_t stream, bool defer) -> int {
-        // overflow tiers hold a 512-entry SMEM ring per read in LDS: run them 32 lanes per read (8 reads per block)
-        int G = tier == 0 ? (int)ctx->group_lanes : 32;
-        const int cap = tier == 0 ? (int)ctx->smem_cap : TIER_CAP[tier];
-        const int lcap = cap < TIER_LCAP[tier] ? cap : TIER_LCAP[tier];
-        DevBuf& sb = ctx->seed.slots[tier];
-        DevBuf& ob = ctx->seed.ovf[tier & 1];
-        const size_t need = (size_t)n_todo * cap * sizeof(SlotRec);
-        if (tier > 0 && need > sb.cap) {
-            // overflow tiers re-run the reads that emitted more SMEMs than their slots hold, with 32 x more slots each:
-            // refuse instead of exhausting the HBM the index lives in
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b / 2) {
-                meme_set_error("%lld reads emitted more than %d SMEMs each: re-running them needs %.1f GB of slots, more than half of the "
-                               "free HBM (%.1f GB); seed this batch in smaller pieces", (long long)n_todo, tiers.cap[tier - 1],
-                               need / 1e9, free_b / 1e9);
-                return MEME_E_CAPACITY;
-            }
-        }
-        int rc2;
-        if ((rc2 = meme_buf_reserve(ctx, sb, need))) return rc2;
-        if ((rc2 = meme_buf_reserve(ctx, ob, (size_t)n_todo * sizeof(i64)))) return rc2;
-        unsigned long long* counters = ctx->seed.counter_set(cset);
-        HIP_TRY(hipMemsetAsync(counters, 0, SEED_CTRS * sizeof(unsigned long long), stream));
-        SeedArgs A;
-        A.I = ctx->idx;
-        A.packed = (const u64*)ctx->batch.packed.p;
-        A.read_off = d_read_off;
-        A.nreads = n_todo;
-        A.geo = geo;
-        A.opt = *opt;
-        A.slots = (SlotRec*)sb.p;
-        A.slot_cnt = (int*)ctx->seed.slot_cnt.p;
-        A.slot_hits = (i64*)ctx->seed.slot_hits.p;
-        A.slot_loc = (i64*)ctx->seed.slot_loc.p;
-        A.pending = pending;
-        A.ovf_list = (i64*)ob.p;
-        A.cap = cap;
-        A.lcap = lcap;
-        A.tier = tier;
-        A.counters = counters;
-        A.defer = defer ? 1 : 0;
-        tiers.base[tier] = (const SlotRec*)sb.p;
-        tiers.cap[tier] = cap;
-        while (G < 32 && seed_lds_bytes(G, geo, lcap) > (size_t)160 * 1024) G *= 2;   // long reads: fewer reads per workgroup
-        const int groups = BLOCK / G;
-        size_t lds = seed_lds_bytes(G, geo, lcap);
-        i64 want = (n_todo + groups - 1) / groups;
-        i64 blocks = ctx->seed_blocks > 0 ? ctx->seed_blocks : (i64)dev_cus * ctx->seed_blocks_per_cu;
-        if (blocks > want) blocks = want;
-        if (blocks < 1) blocks = 1;
-        if (tier == 0) HIP_TRY(hipEventRecord(ctx->ev[0], stream));
-        switch (G) {
-        case 1: return launch_k_seed<1>(stream, A, lds, blocks);
-        case 2: return launch_k_seed<2>(stream, A, lds, blocks);
-        case 4: return launch_k_seed<4>(stream, A, lds, blocks);
-        case 8: return launch_k_seed<8>(stream, A, lds, blocks);
-        case 16: return launch_k_seed<16>(stream, A, lds, blocks);
-        case 32: return launch_k_seed<32>(stream, A, lds, blocks);
-        default: meme_set_error("group_lanes must be 1, 2, 4, 8, 16 or 32"); return MEME_E_ARG;
-        }
-    };
-    auto tally = [&](const unsigned long long* h) {
-        ++launches;
-        searches += (i64)h[1];
-        windows += (i64)h[3];
+    int rc;
+    if ((rc = meme_buf_reserve(ctx, sb, need))) return rc;
+    if ((rc = meme_buf_reserve(ctx, ob, (size_t)n_todo * sizeof(i64)))) return rc;
+    unsigned long long* counters = ctx->seed.counter_set(cset);
+    HIP_TRY(hipMemsetAsync(counters, 0, SEED_CTRS * sizeof(unsigned long long), stream));
+    SeedArgs A;
+    A.I = ctx->idx;
+    A.packed = (const u64*)ctx->batch.packed.p;
+    A.read_off = R.d_read_off;
+    A.nreads = n_todo;
+    A.geo = R.geo;
+    A.opt = *R.opt;
+    A.slots = (SlotRec*)sb.p;
+    A.slot_cnt = (int*)ctx->seed.slot_cnt.p;
+    A.slot_hits = (i64*)ctx->seed.slot_hits.p;
+    A.slot_loc = (i64*)ctx->seed.slot_loc.p;
+    A.pending = pending;
+    A.ovf_list = (i64*)ob.p;
+    A.cap = cap;
+    A.lcap = lcap;
+    A.tier = tier;
+    A.counters = counters;
+    A.defer = defer ? 1 : 0;
+    R.tiers.base[tier] = (const SlotRec*)sb.p;
+    R.tiers.cap[tier] = cap;
+    while (G < 32 && seed_lds_bytes(G, R.geo, lcap) > (size_t)160 * 1024) G *= 2;   // long reads: fewer reads per workgroup
+    const int groups = BLOCK / G;
+    size_t lds = seed_lds_bytes(G, R.geo, lcap);
+    i64 want = (n_todo + groups - 1) / groups;
+    i64 blocks = ctx->seed_blocks > 0 ? ctx->seed_blocks : (i64)ctx->n_cus * ctx->seed_blocks_per_cu;
+    if (blocks > want) blocks = want;
+    if (blocks < 1) blocks = 1;
+    if (tier == 0) HIP_TRY(hipEventRecord(ctx->seed.ev[SEED_EV_SEARCH0], stream));
+    switch (G) {
+    case 1: return launch_k_seed<1>(stream, A, lds, blocks);
+    case 2: return launch_k_seed<2>(stream, A, lds, blocks);
+    case 4: return launch_k_seed<4>(stream, A, lds, blocks);
+    case 8: return launch_k_seed<8>(stream, A, lds, blocks);
+    case 16: return launch_k_seed<16>(stream, A, lds, blocks);
+    case 32: return launch_k_seed<32>(stream, A, lds, blocks);
+    default: meme_set_error("group_lanes must be 1, 2, 4, 8, 16 or 32"); return MEME_E_ARG;
+    }
+}
+
+// the counters a tier's launch left, on the host (waits for ctx->stream); then its share of the call's tallies
+int fetch_counters(SeedRun& R, int cset, unsigned long long* h) {
+    HIP_TRY(hipMemcpyAsync(h, R.ctx->seed.counter_set(cset), SEED_CTRS * sizeof(unsigned long long), hipMemcpyDeviceToHost, R.ctx->stream));
+    HIP_TRY(hipStreamSynchronize(R.ctx->stream));
+    return MEME_OK;
+}
+void tally(SeedRun& R, const unsigned long long* h) {
+    ++R.launches;
+    R.searches += (i64)h[SEED_CTR_SEARCHES];
+    R.windows += (i64)h[SEED_CTR_WINDOWS];
+    R.n_todo = (i64)h[SEED_CTR_OVERFLOW];
 #ifdef SEED_PROF
-        {
-            double tot = 0; for (int k = 0; k < 8; ++k) tot += (double)h[4 + k];
-            fprintf(stderr, "[seed prof]:");
-            const char* nm[6] = {"control", "request+rmi", "window+compare", "resolve", "level", "apply"};
-            for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %.1f%%", nm[k], 100.0 * (double)h[4 + k] / (tot > 0 ? tot : 1));
-            fprintf(stderr, "\n");
-        }
-#endif
-    };
-    // ---- tier 0: the whole batch.  It leaves the re-seeding regions of unique SMEMs to k_reseed (a walk on the plcp table, one lane per
-    // read) and the batches of searches behind it; the overflow tiers search everything themselves.
-    const bool defer = ctx->seed_defer != 0 && ctx->idx.plcp != nullptr && opt->rounds >= 2;
-    if (defer && (rc = meme_buf_reserve(ctx, ctx->seed.pend, (size_t)nreads * sizeof(i64)))) return rc;
-    if (defer && (rc = meme_buf_reserve(ctx, ctx->seed.blk, (size_t)nreads * BLK_PER_READ * 2 * sizeof(BlkRec)))) return rc;
-    if ((rc = launch_tier(0, nreads, nullptr, 0, ctx->stream, defer))) return rc;
-    i64 n_early = -1;                  // reads of the tier-1 launch that ran beside the re-seeding kernels (-1: none did)
-    { const int src = meme_side_stream(ctx, 0); if (src) return src; }
-    if (!ctx->ev_side[0]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_side[0], hipEventDisableTiming));
-    if (!ctx->ev_aux) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_aux, hipEventDisableTiming));
-    if (defer) {
-        const int cap = (int)ctx->smem_cap;
-        HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
-        ReseedArgs R;
-        R.I = ctx->idx; R.packed = (const u64*)ctx->batch.packed.p; R.geo = geo; R.nreads = nreads; R.opt = *opt;
-        R.slots = (SlotRec*)ctx->seed.slots[0].p; R.cap = cap; R.slot_cnt = (int*)ctx->seed.slot_cnt.p; R.slot_hits = (i64*)ctx->seed.slot_hits.p;
-        R.ovf_list = (i64*)ctx->seed.ovf[0].p; R.counters = ctx->seed.counter_set(0); R.pend_list = (i64*)ctx->seed.pend.p;
-        R.blk = (BlkRec*)ctx->seed.blk.p; R.blk_out = R.blk + nreads * BLK_PER_READ; R.blk_cap = nreads * BLK_PER_READ;
-        R.blk_ctr = SEED_CTR_BLK; R.blk_out_ctr = SEED_CTR_BLK_OUT;
-        i64 rblocks = (nreads + 255) / 256;
-        if (rblocks > (i64)dev_cus * 32) rblocks = (i64)dev_cus * 32;
-        hipLaunchKernelGGL(k_reseed, dim3((unsigned)rblocks), dim3(256), 0, ctx->stream, R);
-        HIP_TRY(hipEventRecord(ctx->ev_aux, ctx->stream));
-        // the batch searches (list sizes stay on the device: fixed grids, grid-stride loops), then the blocked regions' passes
-        const unsigned sblocks = (unsigned)(rblocks < (i64)dev_cus * 4 ? rblocks : (i64)dev_cus * 4);
-        // the pending intervals on a stream of their own, beside the blocked regions' rounds (both are latency-bound lane-per-item
-        // kernels; they touch different slots of the reads they share)
-        if (!ctx->stream_emit) { HIP_TRY(hipStreamCreateWithFlags(&ctx->stream_emit, hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&ctx->ev_emit[0], hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&ctx->ev_emit[1], hipEventDisableTiming)); }
-        HIP_TRY(hipEventRecord(ctx->ev_emit[0], ctx->stream));
-        HIP_TRY(hipStreamWaitEvent(ctx->stream_emit, ctx->ev_emit[0], 0));
-        hipLaunchKernelGGL(k_reseed_emit, dim3(sblocks), dim3(256), 0, ctx->stream_emit, R);
-        HIP_TRY(hipEventRecord(ctx->ev_emit[1], ctx->stream_emit));
-        constexpr int ROUNDS = 4;                           // (named configuration: 3 rounds leave 2.2 ms of one-by-one searches to the last pass)
-        for (int round = 0; round < ROUNDS; ++round) {     // blocked regions ping-pong between two lists; the last pass searches for itself
-            hipLaunchKernelGGL(k_reseed_search, dim3(sblocks), dim3(256), 0, ctx->stream, R);
-            if (round < ROUNDS - 1) {
-                hipLaunchKernelGGL(k_reseed_resume<false>, dim3(sblocks), dim3(256), 0, ctx->stream, R);
-                HIP_TRY(hipMemsetAsync(ctx->seed.counter_set(0) + R.blk_ctr, 0, sizeof(unsigned long long), ctx->stream));
-                std::swap(R.blk, R.blk_out); std::swap(R.blk_ctr, R.blk_out_ctr);
-            } else hipLaunchKernelGGL(k_reseed_resume<true>, dim3(sblocks), dim3(256), 0, ctx->stream, R);
-        }
-        HIP_TRY(hipGetLastError());
-        // The reads that overflowed their slots in k_seed or in k_reseed's pass are known once k_reseed has finished -- the only re-seeding
-        // kernel that looks at every read; the ones behind it work from lists of reads that did NOT overflow.  Their tier-1 launch (a few
-        // homopolymer reads of thousands of SMEMs each: 2.5 ms at the named configuration however few they are) runs beside the batches
-        // of searches instead of behind them.  Reads that overflow later (appended by a resume pass: rare) get a second launch below.
-        if (ctx->seed_early_tier != 0) {
-            unsigned long long h_ovf = 0;
-            HIP_TRY(hipStreamWaitEvent(ctx->stream_side[0], ctx->ev_aux, 0));
-            HIP_TRY(hipMemcpyAsync(&h_ovf, ctx->seed.counter_set(0) + SEED_CTR_OVERFLOW, 8, hipMemcpyDeviceToHost, ctx->stream_side[0]));
-            HIP_TRY(hipStreamSynchronize(ctx->stream_side[0]));
-            if (h_ovf > 0) {
-                n_early = (i64)h_ovf;
-                if ((rc = launch_tier(1, n_early, (const i64*)ctx->seed.ovf[0].p, 1, ctx->stream_side[0], false))) return rc;
-                HIP_TRY(hipEventRecord(ctx->ev_side[0], ctx->stream_side[0]));
-                HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_side[0], 0));
-            }
-        }
-        HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_emit[1], 0));
-    }
-    HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    HIP_TRY(hipMemcpyAsync(h_counters, ctx->seed.counter_set(0), sizeof(h_counters), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        ms_total += ms;
-        if (defer) {
-            float a = 0.f;
-            HIP_TRY(hipEventElapsedTime(&a, ctx->ev[4], ctx->ev[1]));
-            ms_reseed += a;
-            lane_searches += (i64)h_counters[12];
-#ifdef RESEED_PROF
-            fprintf(stderr, "[reseed prof] (wave-time in 10 ns ticks, executions) stage windows %llu / %llu, table walk %llu / %llu, lane search %llu / %llu\n", h_counters[4], h_counters[5],
-                    h_counters[6], h_counters[7], h_counters[8], h_counters[9]);
-#endif
-            if (getenv("MEME_SEED_TRACE")) fprintf(stderr, "[meme] seed tier 0: search kernel + re-seeding kernels %.2f ms, of which behind k_seed %.2f ms (%lld lane searches; %lld reads of the "
-                                                   "overflow tier beside them)\n", ms, a, (long long)h_counters[12], (long long)(n_early < 0 ? 0 : n_early));
-        }
+        double tot = 0; for (int k = 0; k < 8; ++k) tot += (double)h[SEED_CTR_PROF + k];
+        fprintf(stderr, "[seed prof]:");
+        const char* nm[6] = {"control", "request+rmi", "window+compare", "resolve", "level", "apply"};
+        for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %.1f%%", nm[k], 100.0 * (double)h[SEED_CTR_PROF + k] / (tot > 0 ? tot : 1));
+        fprintf(stderr, "\n");
     }
-    tally(h_counters);
-    // ---- overflow tiers: reads that produced more SMEMs than their slots hold (pathological repeats) are re-run alone
-    i64 n_todo = (i64)h_counters[SEED_CTR_OVERFLOW];
-    const i64* pending = (const i64*)ctx->seed.ovf[0].p;
-    for (int tier = 1; n_todo > 0; ++tier) {
+#endif
+}
+
+// The re-seeding kernels behind tier 0's k_seed: k_reseed (a walk on the plcp table, one lane per read), then the pending intervals on a stream of
+// their own beside the rounds over the blocked regions.
+int launch_reseed(SeedRun& R) {
+    meme_ctx* ctx = R.ctx;
+    SeedWs& S = ctx->seed;
+    const i64 nreads = R.nreads;
+    HIP_TRY(hipEventRecord(S.ev[SEED_EV_RESEED0], ctx->stream));
+    ReseedArgs A;
+    A.I = ctx->idx; A.packed = (const u64*)ctx->batch.packed.p; A.geo = R.geo; A.nreads = nreads; A.opt = *R.opt;
+    A.slots = (SlotRec*)S.slots[0].p; A.cap = (int)ctx->smem_cap; A.slot_cnt = (int*)S.slot_cnt.p; A.slot_hits = (i64*)S.slot_hits.p;
+    A.ovf_list = (i64*)S.ovf[0].p; A.counters = S.counter_set(0); A.pend_list = (i64*)S.pend.p;
+    A.blk = (BlkRec*)S.blk.p; A.blk_out = A.blk + nreads * BLK_PER_READ; A.blk_cap = nreads * BLK_PER_READ;
+    A.blk_ctr = SEED_CTR_BLK; A.blk_out_ctr = SEED_CTR_BLK_OUT;
+    i64 rblocks = (nreads + 255) / 256;
+    if (rblocks > (i64)ctx->n_cus * 32) rblocks = (i64)ctx->n_cus * 32;
+    hipLaunchKernelGGL(k_reseed, dim3((unsigned)rblocks), dim3(256), 0, ctx->stream, A);
+    HIP_TRY(hipEventRecord(ctx->side.fork[0], ctx->stream));     // (the early overflow launch starts here)
+    // the batch searches (list sizes stay on the device: fixed grids, grid-stride loops), then the blocked regions' passes
+    const unsigned sblocks = (unsigned)(rblocks < (i64)ctx->n_cus * 4 ? rblocks : (i64)ctx->n_cus * 4);
+    // the pending intervals on a stream of their own, beside the blocked regions' rounds (both are latency-bound lane-per-item
+    // kernels; they touch different slots of the reads they share)
+    if (!S.emit.s) HIP_TRY(hipStreamCreateWithFlags(&S.emit.s, hipStreamNonBlocking));
+    for (int i = 0; i < 2; ++i) if (!S.emit_ev[i]) HIP_TRY(hipEventCreateWithFlags(&S.emit_ev[i], hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(S.emit_ev[0], ctx->stream));
+    HIP_TRY(hipStreamWaitEvent(S.emit, S.emit_ev[0], 0));
+    hipLaunchKernelGGL(k_reseed_emit, dim3(sblocks), dim3(256), 0, S.emit, A);
+    HIP_TRY(hipEventRecord(S.emit_ev[1], S.emit));
+    constexpr int ROUNDS = 4;                           // (named configuration: 3 rounds leave 2.2 ms of one-by-one searches to the last pass)
+    for (int round = 0; round < ROUNDS; ++round) {     // blocked regions ping-pong between two lists; the last pass searches for itself
+        hipLaunchKernelGGL(k_reseed_search, dim3(sblocks), dim3(256), 0, ctx->stream, A);
+        if (round < ROUNDS - 1) {
+            hipLaunchKernelGGL(k_reseed_resume<false>, dim3(sblocks), dim3(256), 0, ctx->stream, A);
+            HIP_TRY(hipMemsetAsync(S.counter_set(0) + A.blk_ctr, 0, sizeof(unsigned long long), ctx->stream));
+            std::swap(A.blk, A.blk_out); std::swap(A.blk_ctr, A.blk_out_ctr);
+        } else hipLaunchKernelGGL(k_reseed_resume<true>, dim3(sblocks), dim3(256), 0, ctx->stream, A);
+    }
+    HIP_TRY(hipGetLastError());
+    return MEME_OK;
+}
+
+// The reads that overflowed their slots in k_seed or in k_reseed's pass are known once k_reseed has finished -- the only re-seeding
+// kernel that looks at every read; the ones behind it work from lists of reads that did NOT overflow.  Their tier-1 launch (a few
+// homopolymer reads of thousands of SMEMs each: 2.5 ms at the named configuration however few they are) runs beside the batches
+// of searches instead of behind them.  Reads that overflow later (appended by a resume pass: rare) get a second launch in seed_overflow_tiers.
+int launch_early_overflow(SeedRun& R) {
+    meme_ctx* ctx = R.ctx;
+    Stream& side = ctx->side.st[0];
+    unsigned long long h_ovf = 0;
+    HIP_TRY(hipStreamWaitEvent(side, ctx->side.fork[0], 0));
+    HIP_TRY(hipMemcpyAsync(&h_ovf, ctx->seed.counter_set(0) + SEED_CTR_OVERFLOW, 8, hipMemcpyDeviceToHost, side));
+    HIP_TRY(hipStreamSynchronize(side));
+    if (h_ovf == 0) return MEME_OK;
+    R.n_early = (i64)h_ovf;
+    int rc;
+    if ((rc = launch_tier(R, 1, R.n_early, (const i64*)ctx->seed.ovf[0].p, 1, side, false))) return rc;
+    HIP_TRY(hipEventRecord(ctx->side.done[0], side));
+    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->side.done[0], 0));
+    return MEME_OK;
+}
+
+// tier 0: the whole batch.  It leaves the re-seeding regions of unique SMEMs to k_reseed and the batches of searches behind it; the overflow
+// tiers search everything themselves.
+int seed_tier0(SeedRun& R) {
+    meme_ctx* ctx = R.ctx;
+    SeedWs& S = ctx->seed;
+    int rc;
+    R.defer = ctx->seed_defer != 0 && ctx->idx.plcp != nullptr && R.opt->rounds >= 2;
+    if (R.defer && (rc = meme_buf_reserve(ctx, S.pend, (size_t)R.nreads * sizeof(i64)))) return rc;
+    if (R.defer && (rc = meme_buf_reserve(ctx, S.blk, (size_t)R.nreads * BLK_PER_READ * 2 * sizeof(BlkRec)))) return rc;
+    if ((rc = launch_tier(R, 0, R.nreads, nullptr, 0, ctx->stream, R.defer))) return rc;
+    if (R.defer) {
+        if ((rc = meme_side_stream(ctx, 0)) || (rc = launch_reseed(R)) || (rc = launch_early_overflow(R))) return rc;
+        HIP_TRY(hipStreamWaitEvent(ctx->stream, S.emit_ev[1], 0));
+    }
+    HIP_TRY(hipEventRecord(S.ev[SEED_EV_SEARCH1], ctx->stream));
+    unsigned long long h[SEED_CTRS];
+    if ((rc = fetch_counters(R, 0, h))) return rc;
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev[SEED_EV_SEARCH0], S.ev[SEED_EV_SEARCH1]));
+    R.ms_total += ms;
+    if (R.defer) {
+        float a = 0.f;
+        HIP_TRY(hipEventElapsedTime(&a, S.ev[SEED_EV_RESEED0], S.ev[SEED_EV_SEARCH1]));
+        R.ms_reseed += a;
+        R.lane_searches += (i64)h[SEED_CTR_LANE];
+        if (getenv("MEME_SEED_TRACE")) fprintf(stderr, "[meme] seed tier 0: search kernel + re-seeding kernels %.2f ms, of which behind k_seed %.2f ms (%lld lane searches; %lld reads of the "
+                                               "overflow tier beside them)\n", ms, a, (long long)h[SEED_CTR_LANE], (long long)(R.n_early < 0 ? 0 : R.n_early));
+    }
+    tally(R, h);
+    return MEME_OK;
+}
+
+// overflow tiers: reads that produced more SMEMs than their slots hold (pathological repeats) are re-run alone
+int seed_overflow_tiers(SeedRun& R) {
+    meme_ctx* ctx = R.ctx;
+    SeedWs& S = ctx->seed;
+    int rc;
+    unsigned long long h[SEED_CTRS];
+    for (int tier = 1; R.n_todo > 0; ++tier) {
         if (tier >= N_TIERS) {
             meme_set_error("a read produced more than %d SMEMs", TIER_CAP[N_TIERS - 1]);
             return MEME_E_CAPACITY;
         }
         const int cset = tier & 1;
-        if (tier == 1 && n_early == n_todo) {
+        if (tier == 1 && R.n_early == R.n_todo) {
             // the launch beside the re-seeding kernels took them all: only its counters are left to read
-            HIP_TRY(hipMemcpyAsync(h_counters, ctx->seed.counter_set(cset), sizeof(h_counters), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            if ((rc = fetch_counters(R, cset, h))) return rc;
         } else {
             // (tier 1 after an early launch that did not see every overflowed read: all of them again -- rare, and simple)
-            HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-            if ((rc = launch_tier(tier, n_todo, pending, cset, ctx->stream, false))) return rc;
-            HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-            HIP_TRY(hipMemcpyAsync(h_counters, ctx->seed.counter_set(cset), sizeof(h_counters), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            HIP_TRY(hipEventRecord(S.ev[SEED_EV_SEARCH0], ctx->stream));
+            if ((rc = launch_tier(R, tier, R.n_todo, (const i64*)S.ovf[(tier - 1) & 1].p, cset, ctx->stream, false))) return rc;
+            HIP_TRY(hipEventRecord(S.ev[SEED_EV_SEARCH1], ctx->stream));
+            if ((rc = fetch_counters(R, cset, h))) return rc;
             float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-            ms_total += ms;
+            HIP_TRY(hipEventElapsedTime(&ms, S.ev[SEED_EV_SEARCH0], S.ev[SEED_EV_SEARCH1]));
+            R.ms_total += ms;
         }
-        tally(h_counters);
-        n_todo = (i64)h_counters[SEED_CTR_OVERFLOW];
-        pending = (const i64*)ctx->seed.ovf[tier & 1].p;
+        tally(R, h);
     }
-    {
-        float pms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&pms, ctx->ev[6], ctx->ev[7]));
-        ctx->tm.seed_pack_ms = pms;
-    }
-    ctx->tm.seed_kernel_ms = ms_total;
-    ctx->tm.seed_launches = launches;
-    ctx->tm.seed_windows = windows;
-    ctx->tm.seed_reseed_ms = ms_reseed;
-    ctx->tm.seed_lane_searches = lane_searches;
-    // offsets
+    return MEME_OK;
+}
+
+// per-read offsets of the SMEMs and hits (a two-level scan), then the gather of every tier's slots into the batch's packed arrays
+int seed_gather(SeedRun& R, meme_seed_result* out) {
+    meme_ctx* ctx = R.ctx;
+    SeedWs& S = ctx->seed;
+    ResidentBatch& B = ctx->batch;
+    const i64 nreads = R.nreads;
+    int rc;
     i64 ntiles = (nreads + SCAN_TILE - 1) / SCAN_TILE;
     if ((rc = meme_buf_reserve(ctx, ctx->scan_tmp, (size_t)(2 * ntiles + 2) * sizeof(i64)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->batch.smem_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->batch.hit_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, B.smem_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, B.hit_off, (size_t)(nreads + 1) * sizeof(i64)))) return rc;
     i64* tiles = (i64*)ctx->scan_tmp.p;
     i64* totals = tiles + 2 * ntiles;
-    HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
-    hipLaunchKernelGGL(k_tile_sums, dim3((unsigned)ntiles), dim3(SCAN_BLOCK), 0, ctx->stream, (const int*)ctx->seed.slot_cnt.p,
-                       (const i64*)ctx->seed.slot_hits.p, nreads, tiles);
+    HIP_TRY(hipEventRecord(S.ev[SEED_EV_GATHER0], ctx->stream));
+    hipLaunchKernelGGL(k_tile_sums, dim3((unsigned)ntiles), dim3(SCAN_BLOCK), 0, ctx->stream, (const int*)S.slot_cnt.p,
+                       (const i64*)S.slot_hits.p, nreads, tiles);
     hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(SCAN_BLOCK), 0, ctx->stream, tiles, ntiles, totals);
-    hipLaunchKernelGGL(k_offsets, dim3((unsigned)ntiles), dim3(SCAN_BLOCK), 0, ctx->stream, (const int*)ctx->seed.slot_cnt.p,
-                       (const i64*)ctx->seed.slot_hits.p, nreads, (const i64*)tiles, (i64*)ctx->batch.smem_off.p,
-                       (i64*)ctx->batch.hit_off.p);
+    hipLaunchKernelGGL(k_offsets, dim3((unsigned)ntiles), dim3(SCAN_BLOCK), 0, ctx->stream, (const int*)S.slot_cnt.p,
+                       (const i64*)S.slot_hits.p, nreads, (const i64*)tiles, (i64*)B.smem_off.p, (i64*)B.hit_off.p);
     HIP_TRY(hipGetLastError());
     i64 h_tot[2];
     HIP_TRY(hipMemcpyAsync(h_tot, totals, sizeof(h_tot), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if ((rc = meme_buf_reserve(ctx, ctx->batch.smems, (size_t)(h_tot[0] + 1) * sizeof(meme_mem_tl)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ctx->batch.hits, (size_t)(h_tot[1] + 1) * sizeof(u64)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, B.smems, (size_t)(h_tot[0] + 1) * sizeof(meme_mem_tl)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, B.hits, (size_t)(h_tot[1] + 1) * sizeof(u64)))) return rc;
     i64 gblocks = (nreads + 15) / 16;
-    if (gblocks > (i64)dev_cus * 8) gblocks = (i64)dev_cus * 8;
+    if (gblocks > (i64)ctx->n_cus * 8) gblocks = (i64)ctx->n_cus * 8;
     if (gblocks < 1) gblocks = 1;
-    hipLaunchKernelGGL(k_gather, dim3((unsigned)gblocks), dim3(BLOCK), 0, ctx->stream, ctx->idx.sa, tiers,
-                       (const i64*)ctx->seed.slot_loc.p, (const int*)ctx->seed.slot_cnt.p, nreads, opt->hits_per_smem,
-                       (const i64*)ctx->batch.smem_off.p, (const i64*)ctx->batch.hit_off.p, (meme_mem_tl*)ctx->batch.smems.p,
-                       (u64*)ctx->batch.hits.p);
+    hipLaunchKernelGGL(k_gather, dim3((unsigned)gblocks), dim3(BLOCK), 0, ctx->stream, ctx->idx.sa, R.tiers,
+                       (const i64*)S.slot_loc.p, (const int*)S.slot_cnt.p, nreads, R.opt->hits_per_smem,
+                       (const i64*)B.smem_off.p, (const i64*)B.hit_off.p, (meme_mem_tl*)B.smems.p, (u64*)B.hits.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
+    HIP_TRY(hipEventRecord(S.ev[SEED_EV_GATHER1], ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    float gms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&gms, ctx->ev[2], ctx->ev[3]));
-    ctx->tm.seed_gather_ms = gms;
-    out->d_smems = (const meme_mem_tl*)ctx->batch.smems.p;
-    out->d_smem_off = (const i64*)ctx->batch.smem_off.p;
-    out->d_hits = (const u64*)ctx->batch.hits.p;
-    out->d_hit_off = (const i64*)ctx->batch.hit_off.p;
+    HIP_TRY(hipEventElapsedTime(&ctx->tm.seed_gather_ms, S.ev[SEED_EV_GATHER0], S.ev[SEED_EV_GATHER1]));
+    out->d_smems = (const meme_mem_tl*)B.smems.p;
+    out->d_smem_off = (const i64*)B.smem_off.p;
+    out->d_hits = (const u64*)B.hits.p;
+    out->d_hit_off = (const i64*)B.hit_off.p;
     out->total_smems = h_tot[0];
     out->total_hits = h_tot[1];
-    out->searches = searches;
+    out->searches = R.searches;
     return MEME_OK;
+}
+
+int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i64 nreads, i64 max_len, i64 total_bytes,
+                const meme_seed_opt* opt, meme_seed_result* out) {
+    int rc;
+    SeedWs& S = ctx->seed;
+    ctx->batch.last_seed_reads = 0;          // whatever batch meme_chain_last_batch_host could have chained is being overwritten
+    ctx->sam_text_reads = 0;           // ... and the names / qualities staged for it belong to the previous batch
+    if ((rc = meme_buf_reserve(ctx, S.slot_cnt, (size_t)nreads * sizeof(int)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, S.slot_hits, (size_t)nreads * sizeof(i64)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, S.slot_loc, (size_t)nreads * sizeof(i64)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, S.counters, 2 * SEED_CTRS * sizeof(unsigned long long)))) return rc;
+    for (int i = 0; i < SEED_EVS; ++i) if (!S.ev[i]) HIP_TRY(hipEventCreate(&S.ev[i]));
+    SeedRun R;
+    R.ctx = ctx; R.d_read_off = d_read_off; R.nreads = nreads; R.opt = opt;
+    if ((rc = seed_pack(R, d_reads, max_len, total_bytes)) || (rc = seed_tier0(R)) || (rc = seed_overflow_tiers(R))) return rc;
+    HIP_TRY(hipEventElapsedTime(&ctx->tm.seed_pack_ms, S.ev[SEED_EV_PACK0], S.ev[SEED_EV_PACK1]));
+    ctx->tm.seed_kernel_ms = R.ms_total;
+    ctx->tm.seed_launches = R.launches;
+    ctx->tm.seed_windows = R.windows;
+    ctx->tm.seed_reseed_ms = R.ms_reseed;
+    ctx->tm.seed_lane_searches = R.lane_searches;
+    return seed_gather(R, out);
 }
 
 // longest read of the batch (sizes the packed layout and the LDS tile)

@@ -81,7 +81,7 @@ struct SeedArgs {
     const i64* pending;    // read ids to re-process in an overflow tier, else nullptr
     i64* ovf_list;
     int cap, lcap, tier;
-    unsigned long long* counters;   // [0] ticket, [1] searches, [2] overflowed reads, [3] window loads, [4..11] SEED_PROF, [12] lane searches of k_reseed
+    unsigned long long* counters;   // one counter set (SEED_CTR_*, meme_common.h)
     int defer;                      // 1: re-seeding regions of unique SMEMs are left to k_reseed (tier 0 only)
 };
 
@@ -519,7 +519,7 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
 
 #ifdef SEED_PROF
     // diagnostic build: wall-clock ticks (100 MHz) a wavefront spends in each section of the loop body, summed over
-    // groups into counters[4..]; marks sit at points every lane still in the loop passes
+    // groups into counters[SEED_CTR_PROF..]; marks sit at points every lane still in the loop passes
     unsigned prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long prof_t = wall_clock64();
 #define PROF_MARK(i_) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long now__ = wall_clock64(); prof[i_] += (unsigned)(now__ - prof_t); prof_t = now__; } while (0)
@@ -625,7 +625,7 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                         A.slot_cnt[rid] = ovf ? 0 : st[ST_N_SMEMS];
                         A.slot_hits[rid] = ovf ? 0 : LD64(ST_HITS_LO);
                         A.slot_loc[rid] = ((i64)A.tier << 40) | (i64)ticket;
-                        if (ovf) A.ovf_list[atomicAdd(&A.counters[2], 1ull)] = rid;
+                        if (ovf) A.ovf_list[atomicAdd(&A.counters[SEED_CTR_OVERFLOW], 1ull)] = rid;
                     }
                     if (!ovf) { acc_searches += (unsigned)st[ST_SEARCHES]; acc_windows += (unsigned)st[ST_WINDOWS]; }
                     pc = PC_FETCH;
@@ -647,7 +647,7 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                         const int kreq = __popcll(mo), alloc = kreq > TICKET_CHUNK ? kreq : TICKET_CHUNK;
                         unsigned long long nb = 0;
                         if (lane == first) {
-                            nb = atomicAdd(&A.counters[0], (unsigned long long)alloc);
+                            nb = atomicAdd(&A.counters[SEED_CTR_SLOT], (unsigned long long)alloc);
                             const unsigned long long wb = nb + (unsigned)(alloc - TICKET_CHUNK);
                             wv[0] = kreq - (alloc - TICKET_CHUNK); wv[2] = (int)(unsigned)(wb & 0xffffffffull); wv[3] = (int)(wb >> 32);
                         }
@@ -700,9 +700,9 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
 #undef AT
             if (pc == PC_EXIT) {
                 if (t == 0) {
-                    atomicAdd(&A.counters[1], (unsigned long long)acc_searches); atomicAdd(&A.counters[3], (unsigned long long)acc_windows);
+                    atomicAdd(&A.counters[SEED_CTR_SEARCHES], (unsigned long long)acc_searches); atomicAdd(&A.counters[SEED_CTR_WINDOWS], (unsigned long long)acc_windows);
 #ifdef SEED_PROF
-                    for (int k = 0; k < 8; ++k) atomicAdd(&A.counters[4 + k], (unsigned long long)prof[k]);
+                    for (int k = 0; k < 8; ++k) atomicAdd(&A.counters[SEED_CTR_PROF + k], (unsigned long long)prof[k]);
 #endif
                 }
                 break;
@@ -1215,7 +1215,7 @@ struct ReseedArgs {
     int* slot_cnt;
     i64* slot_hits;
     i64* ovf_list;
-    unsigned long long* counters;   // [1] searches, [2] overflowed reads, [12] searches inside the walk kernels, [13] reads with pending SMEMs, [14] blocked regions
+    unsigned long long* counters;   // the counter set of tier 0 (SEED_CTR_*: searches, overflowed reads, lane searches, reads with pending SMEMs, blocked regions)
     i64* pend_list;         // reads that hold SLOT_PEND records
     BlkRec* blk;            // blocked regions: the list this launch reads (k_reseed: writes), capacity blk_cap, its length in counters[blk_ctr]
     BlkRec* blk_out;        // k_reseed_resume<false>: the regions that block again, length in counters[blk_out_ctr]
@@ -1237,7 +1237,7 @@ struct SmemAppender {
         } else {
             const int at = atomicAdd(cnt, 1);
             if (at < cap) { SlotRec sr; sr.start = start; sr.end = end; sr.sa_start = sa_start; sr.count = count; sl[at] = sr; }
-            else if (at == cap) ovf_list[atomicAdd(&counters[2], 1ull)] = rid;     // the first one over: the read goes to the next tier (which rewrites its counters)
+            else if (at == cap) ovf_list[atomicAdd(&counters[SEED_CTR_OVERFLOW], 1ull)] = rid;     // the first one over: the read goes to the next tier (which rewrites its counters)
             atomicAdd(reinterpret_cast<unsigned long long*>(hits), (unsigned long long)h);
         }
     }
@@ -1374,7 +1374,7 @@ __global__ void __launch_bounds__(256) k_reseed(ReseedArgs A) {
             if (ap.ns != c0) {
                 if (ap.ns > cap) {            // more SMEMs than the read's slots hold: the whole read goes to the next tier, as in k_seed
                     A.slot_cnt[r] = 0; A.slot_hits[r] = 0;
-                    A.ovf_list[atomicAdd(&A.counters[2], 1ull)] = r;
+                    A.ovf_list[atomicAdd(&A.counters[SEED_CTR_OVERFLOW], 1ull)] = r;
                     n_pend = 0; n_blk = 0;
                 } else { A.slot_cnt[r] = ap.ns; A.slot_hits[r] = A.slot_hits[r] + ap.hits_add; pend_ns = ap.ns; }
             }
@@ -1386,9 +1386,9 @@ __global__ void __launch_bounds__(256) k_reseed(ReseedArgs A) {
         if (hops | lsearches) { atomicAdd(&blk_hops, (unsigned long long)(hops + lsearches)); if (lsearches) atomicAdd(&blk_lane, (unsigned long long)lsearches); }
         __syncthreads();
         if (threadIdx.x == 0) {
-            if (blk_hops) atomicAdd(&A.counters[1], blk_hops);
-            if (blk_lane) atomicAdd(&A.counters[12], blk_lane);
-            if (blk_pend) blk_pend_base = (unsigned)atomicAdd(&A.counters[13], (unsigned long long)blk_pend);
+            if (blk_hops) atomicAdd(&A.counters[SEED_CTR_SEARCHES], blk_hops);
+            if (blk_lane) atomicAdd(&A.counters[SEED_CTR_LANE], blk_lane);
+            if (blk_pend) blk_pend_base = (unsigned)atomicAdd(&A.counters[SEED_CTR_PEND], (unsigned long long)blk_pend);
             if (blk_blk) blk_blk_base = atomicAdd(&A.counters[A.blk_ctr], (unsigned long long)blk_blk);
         }
         __syncthreads();
@@ -1408,7 +1408,7 @@ __global__ void __launch_bounds__(256) k_reseed(ReseedArgs A) {
 // of a wavefront in step.
 __global__ void __launch_bounds__(256) k_reseed_emit(ReseedArgs A) {
     __shared__ uint32_t lwin[(LANE_W / 2) * 256];
-    const i64 n_list = (i64)A.counters[13];
+    const i64 n_list = (i64)A.counters[SEED_CTR_PEND];
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n_list; i += (i64)gridDim.x * blockDim.x) {
         // (runs beside the blocked regions' passes, which append to the same reads: only the slots the first pass filled are looked
         // at, and the hit count is bumped atomically)
@@ -1535,8 +1535,8 @@ __global__ void __launch_bounds__(256) k_reseed_resume(ReseedArgs A) {
     if (lsearches) atomicAdd(&acc_lane, (unsigned long long)lsearches);
     __syncthreads();
     if (threadIdx.x == 0) {
-        if (acc_total) atomicAdd(&A.counters[1], acc_total);
-        if (acc_lane) atomicAdd(&A.counters[12], acc_lane);
+        if (acc_total) atomicAdd(&A.counters[SEED_CTR_SEARCHES], acc_total);
+        if (acc_lane) atomicAdd(&A.counters[SEED_CTR_LANE], acc_lane);
     }
 }
 

@@ -27,7 +27,6 @@ contigs = [(l_pac * k // 8, l_pac * (k + 1) // 8 - l_pac * k // 8, 0) for k in r
 opt = hipapi.default_chain_opt(l_pac)
 if os.environ.get("CHAIN_LIGHT_HITS"): ctx.set_tuning("chain_light_hits", int(os.environ["CHAIN_LIGHT_HITS"]))
 if os.environ.get("CHAIN_WAVE_TIERS"): ctx.set_tuning("chain_wave_tiers", int(os.environ["CHAIN_WAVE_TIERS"]))
-if os.environ.get("CHAIN_SIDE_PRIORITY"): ctx.set_tuning("chain_side_priority", int(os.environ["CHAIN_SIDE_PRIORITY"]))
 for it in range(3 if not os.environ.get("CHAIN_LANE_HITS") else 1):
     t0 = time.time(); smems, so, hits, ho = ctx.seed_batch_host(reads.reshape(-1), off); t1 = time.time()
     res = ctx.chain_last_batch_host(contigs, opt); t2 = time.time()
