@@ -740,7 +740,7 @@ int launch_bsw(meme_ctx* ctx, meme_seqpair* d_pairs, const uint8_t* d_ref, const
     int* order = (int*)ctx->bsw.order.p;
     const i64 dev_cus = ctx->n_cus;
     Events<2>& ev = ctx->bsw.ev;
-    for (int i = 0; i < 2; ++i) if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
+    HIP_TRY(ev.ensure());
     HIP_TRY(hipMemsetAsync(hist, 0, bs.bytes, ctx->stream));
     HIP_TRY(hipEventRecord(ev[0], ctx->stream));
     // big batches: one pair per lane (throughput).  Small batches (the reference's 512-read call granularity): 16-64

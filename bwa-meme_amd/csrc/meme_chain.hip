@@ -1351,29 +1351,86 @@ __global__ void __launch_bounds__(256) k_chain_counts(const ReadHdr* __restrict_
 // fallback = 3 (two chains on one position; more than 1 024 chains) goes to the B-tree tier.  Each of the five wavefront launches has a
 // scratch set of its own.
 namespace {
-struct ScratchSet { DevBuf* buf; WaveArgs W; };
-int make_set(meme_ctx* ctx, DevBuf& buf, const i64* d_list, const i64* d_woff, i64 nlist, i64 total_work, int set, bool with_tree, WaveArgs* out) {
-    const size_t units = (size_t)total_work + 8, nodes = with_tree ? (size_t)total_work / 3 + 4 * (size_t)nlist + 8 : 1;
-    const size_t sz[7] = {units * sizeof(C2), units * sizeof(S2), units * sizeof(FRec), with_tree ? units * 8 : 8, units * 4, with_tree ? units * 4 : 8, nodes * sizeof(TNode)};
-    size_t need = 0, at[7];
-    for (int k = 0; k < 7; ++k) { at[k] = need; need += (sz[k] + 255) / 256 * 256; }
-    if (need > buf.cap) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b / 2 + buf.cap) {
+// One wavefront launch: ChainLists column k (its reads, their work, the scan of it), scratch set k + 1 in ChainWs::wave[k].  k = 0 / 1 / 2: LDS tier of 256 / 512 /
+// 1 024 chains (routed, on side stream k), 3: LDS tier of 256 chains for what the lane tier left, 4: B-tree tier.
+enum ChainKernel { CK_LDS1024, CK_LDS512, CK_LDS256, CK_LANE, CK_TREE };
+struct ChainTier {
+    int k; ChainKernel kernel; bool tree; // tree: the scratch set has sort keys, a second index array and tree nodes (what k_chain_wave needs)
+    hipStream_t st;
+    i64 n = 0, total = 0;                 // reads of the list, hits they walk
+    WaveArgs W;
+};
+// the chaining kernels: a wavefront per listed read (LDS tiers of 1 024 / 512 / 256 chains, B-tree tier) or, CK_LANE, a lane per read of the batch (W unused)
+void launch_chain(ChainKernel kernel, unsigned grid, hipStream_t st, const ChainArgs& A, const WaveArgs& W) {
+    if (kernel == CK_LDS1024) hipLaunchKernelGGL((k_chain_lds<1024>), dim3(grid), dim3(64), 0, st, A, W);
+    else if (kernel == CK_LDS512) hipLaunchKernelGGL((k_chain_lds<512>), dim3(grid), dim3(64), 0, st, A, W);
+    else if (kernel == CK_LDS256) hipLaunchKernelGGL((k_chain_lds<256>), dim3(grid), dim3(64), 0, st, A, W);
+    else if (kernel == CK_LANE) hipLaunchKernelGGL((k_chain<CHAIN_CAP, SEED_CAP>), dim3(grid), dim3(64), 0, st, A);
+    else hipLaunchKernelGGL((k_chain_wave<288, 2048>), dim3(grid), dim3(64), 0, st, A, W, (i64)0);
+}
+// the scratch set of a tier, every array 256-byte aligned: chains, seeds, records, sort keys, two index arrays, tree nodes -- sized, reserved, then carved
+int make_set(meme_ctx* ctx, const ChainLists& L, ChainTier& T) {
+    DevBuf& buf = ctx->chain.wave[T.k];
+    const size_t units = (size_t)T.total + 8, n_nodes = T.tree ? (size_t)T.total / 3 + 4 * (size_t)T.n + 8 : 1;
+    WaveArgs& W = T.W;
+    W.list = L.list[T.k]; W.woff = L.woff[T.k]; W.nlist = T.n; W.sub = nullptr; W.nsub = 0; W.set = T.k + 1;
+    for (int carve = 0; carve < 2; ++carve) {
+        Carve c(carve ? buf.p : nullptr);
+        W.C = c.take<C2>(units, 256); W.S = c.take<S2>(units, 256); W.F = c.take<FRec>(units, 256); W.srt = c.take<u64>(T.tree ? units : 1, 256); W.ia = c.take<int>(units, 256);
+        W.ib = c.take<int>(T.tree ? units : 2, 256); W.nodes = c.take<TNode>(n_nodes, 256); c.take<char>(0, 256);
+        size_t free_b = 0;
+        if (!carve && !meme_fits_free_hbm(c.bytes, buf.cap, &free_b)) {
             meme_set_error("chaining %lld repeat-rich reads of this batch (%lld hits to walk) needs %.1f GB of scratch, more than half of the free HBM "
-                           "(%.1f GB): chain this batch in smaller pieces", (long long)nlist, (long long)total_work, need / 1e9, free_b / 1e9);
+                           "(%.1f GB): chain this batch in smaller pieces", (long long)T.n, (long long)T.total, c.bytes / 1e9, free_b / 1e9);
             return MEME_E_CAPACITY;
         }
+        const int rc = carve ? MEME_OK : meme_buf_reserve(ctx, buf, c.bytes);
+        if (rc) return rc;
     }
-    int rc = meme_buf_reserve(ctx, buf, need);
-    if (rc) return rc;
-    unsigned char* p = (unsigned char*)buf.p;
-    WaveArgs W;
-    memset(&W, 0, sizeof(W));
-    W.list = d_list; W.woff = d_woff; W.nlist = nlist; W.sub = nullptr; W.nsub = 0; W.set = set;
-    W.C = (C2*)(p + at[0]); W.S = (S2*)(p + at[1]); W.F = (FRec*)(p + at[2]); W.srt = (u64*)(p + at[3]); W.ia = (int*)(p + at[4]);
-    W.ib = (int*)(p + at[5]); W.nodes = (TNode*)(p + at[6]);
-    *out = W;
+    return MEME_OK;
+}
+// The tiers of a group, their read counts known: scan of the work -> total -> (one synchronisation for the group) -> scratch set -> launch, the longest-running
+// first.  routed: each on its side stream behind the fork event, its "done" event recorded.
+int run_tiers(meme_ctx* ctx, const ChainArgs& A, const ChainLists& L, ChainTier* T, int nt, bool routed) {
+    int rc;
+    for (int i = 0; i < nt; ++i) if (T[i].n > 0 && (rc = meme_scan_total(ctx, L.work[T[i].k], L.woff[T[i].k], T[i].n, &T[i].total))) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < nt; ++i) if (T[i].n > 0 && (rc = make_set(ctx, L, T[i]))) return rc;
+    if (routed) HIP_TRY(hipEventRecord(ctx->side.fork[0], ctx->stream));
+    for (int i = nt - 1; i >= 0; --i) {
+        const ChainTier& t = T[i];
+        if (t.n <= 0) continue;
+        if (routed) HIP_TRY(hipStreamWaitEvent(t.st, ctx->side.fork[0], 0));
+        launch_chain(t.kernel, (unsigned)t.n, t.st, A, t.W);
+        if (routed) HIP_TRY(hipEventRecord(ctx->side.done[t.k], t.st));
+    }
+    return MEME_OK;
+}
+// the reads left with fallback == want (skip: classes of the routed reads -- their tiers may still be writing) listed for tier T; then the group of one
+int redo_tier(meme_ctx* ctx, const ChainArgs& A, const ChainLists& L, unsigned long long* route, ChainTier& T, int want, const unsigned char* skip) {
+    hipLaunchKernelGGL(k_chain_redo, dim3(grid_blocks(A.nreads, 256)), dim3(256), 0, ctx->stream, (const ReadHdr*)A.hdr, A.nreads, want, skip, route + T.k, L.list[T.k], L.work[T.k]);
+    unsigned long long h = 0;
+    HIP_TRY(hipMemcpyAsync(&h, route + T.k, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    T.n = (i64)h;
+    return T.n > 0 ? run_tiers(ctx, A, L, &T, 1, false) : MEME_OK;
+}
+// chains and seeds counted per read, scanned, packed from the lane tier's rows and the scratch sets of the tiers that ran; totals[0..1] = chains, seeds
+int chain_pack(meme_ctx* ctx, const ChainCounts& cc, const ChainTier* T, i64* totals) {
+    ChainWs& C = ctx->chain;
+    const i64 n = ctx->batch.last_seed_reads;
+    int rc;
+    hipLaunchKernelGGL(k_chain_counts, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, C.hdr.as<const ReadHdr>(), n, cc.nch, cc.nsd, cc.tree, cc.fb);
+    if ((rc = meme_scan_total(ctx, cc.nch, cc.chain_off, n, &totals[0])) || (rc = meme_scan_total(ctx, cc.nsd, cc.seed_off, n, &totals[1]))) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if ((rc = meme_buf_reserve(ctx, C.chains, (size_t)(totals[0] + 1) * sizeof(meme_chain)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, C.seeds, (size_t)(totals[1] + 1) * sizeof(meme_chain_seed)))) return rc;
+    PackSets PS;
+    memset(&PS, 0, sizeof(PS));
+    for (int k = 0; k < 5; ++k) if (T[k].n > 0) { PS.woff[k + 1] = T[k].W.woff; PS.C[k + 1] = T[k].W.C; PS.S[k + 1] = T[k].W.S; PS.F[k + 1] = T[k].W.F; }
+    hipLaunchKernelGGL(k_chain_pack, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, C.ch1.as<const DChain>(), C.sd1.as<const DSeed>(), PS,
+                       C.hdr.as<const ReadHdr>(), (const i64*)cc.chain_off, (const i64*)cc.seed_off, n, C.chains.as<meme_chain>(), C.seeds.as<meme_chain_seed>());
+    HIP_TRY(hipGetLastError());
     return MEME_OK;
 }
 }  // namespace
@@ -1401,112 +1458,56 @@ int meme_chain_run(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs,
     if ((rc = meme_chain_reserve(ctx, n))) return rc;
     const ChainCounts cc(C.counts.p, n);
     HIP_TRY(hipMemsetAsync(cc.route, 0, 64, ctx->stream));
+    const ChainLists L(C.lists.p, n);
     ChainArgs A;
-    A.smems = (const meme_mem_tl*)ctx->batch.smems.p; A.smem_off = (const i64*)ctx->batch.smem_off.p;
-    A.hits = (const u64*)ctx->batch.hits.p; A.hit_off = (const i64*)ctx->batch.hit_off.p; A.read_off = (const i64*)ctx->batch.read_off.p;
+    A.smems = ctx->batch.smems.as<const meme_mem_tl>(); A.smem_off = ctx->batch.smem_off.as<const i64>();
+    A.hits = ctx->batch.hits.as<const u64>(); A.hit_off = ctx->batch.hit_off.as<const i64>(); A.read_off = ctx->batch.read_off.as<const i64>();
     A.nreads = n;
     A.contig_off = ct.off; A.contig_len = ct.len; A.contig_alt = ct.alt; A.n_contigs = n_contigs;
     A.o = *opt;
     A.hit_cap1 = (int)ctx->chain_lane_hits;
-    A.ch = (DChain*)C.ch1.p; A.sd = (DSeed*)C.sd1.p; A.hdr = (ReadHdr*)C.hdr.p; A.frac_rep = (float*)C.frac.p;
-    // lists: [k] list, work, offsets for k = 0 / 1 / 2 LDS tier of 256 / 512 / 1 024 chains (routed), 3 LDS tier of 256 chains (left by the
-    // lane tier), 4 B-tree tier; scratch set k + 1 in C.wave[k]
-    const ChainLists L(C.lists.p, n);
-    const bool wave_tiers = ctx->chain_wave_tiers != 0;     // (0: tests drive everything the lane tier leaves through the B-tree tier)
+    A.ch = C.ch1.as<DChain>(); A.sd = C.sd1.as<DSeed>(); A.hdr = C.hdr.as<ReadHdr>(); A.frac_rep = C.frac.as<float>();
     A.cls = L.cls;
+    const bool wave_tiers = ctx->chain_wave_tiers != 0;     // (0: tests drive everything the lane tier leaves through the B-tree tier)
     Events<5>& ev = C.ev;
-    for (int i = 0; i < 5; ++i) if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
+    HIP_TRY(ev.ensure());
     for (int i = 0; i < 3; ++i) if ((rc = meme_side_stream(ctx, i))) return rc;
+    ChainTier T[5] = {{0, CK_LDS256, false, ctx->side.st[0]}, {1, CK_LDS512, false, ctx->side.st[1]}, {2, CK_LDS1024, false, ctx->side.st[2]},
+                      {3, wave_tiers ? CK_LDS256 : CK_TREE, !wave_tiers, ctx->stream}, {4, CK_TREE, true, ctx->stream}};
+    for (ChainTier& t : T) memset(&t.W, 0, sizeof(t.W));
     HIP_TRY(hipEventRecord(ev[0], ctx->stream));
     // ---- route by work
     const i64 never = (i64)1 << 60;
     const i64 light = wave_tiers ? ctx->chain_light_hits : never, heavy = wave_tiers ? 256 : never, huge = wave_tiers ? 512 : never;
     hipLaunchKernelGGL(k_chain_route, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, A.smems, A.smem_off, A.read_off, n, opt->max_occ, opt->min_seed_len, light, heavy, huge,
                        L.cls, cc.route, L.list[0], L.work[0], L.list[1], L.work[1], L.list[2], L.work[2]);
-    unsigned long long h_cnt[5] = {0, 0, 0, 0, 0};
+    unsigned long long h_cnt[3] = {0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h_cnt, cc.route, 24, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));                           // (also: `tab` is a local)
-    i64 nl[5] = {(i64)h_cnt[0], (i64)h_cnt[1], (i64)h_cnt[2], 0, 0}, tw[5] = {0, 0, 0, 0, 0};
-    WaveArgs W[5];
-    memset(W, 0, sizeof(W));
-    bool used[5] = {false, false, false, false, false};
-    for (int k = 0; k < 3; ++k) if (nl[k] > 0) { if ((rc = meme_scan_exclusive(ctx, L.work[k], L.woff[k], nl[k]))) return rc; HIP_TRY(hipMemcpyAsync(&tw[k], L.woff[k] + nl[k], 8, hipMemcpyDeviceToHost, ctx->stream)); }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 3; ++k) if (nl[k] > 0) { if ((rc = make_set(ctx, C.wave[k], L.list[k], L.woff[k], nl[k], tw[k], 1 + k, false, &W[k]))) return rc; used[k] = true; }
-    HIP_TRY(hipEventRecord(ctx->side.fork[0], ctx->stream));
-    // ---- four launches at once (the longest-running first)
-    for (int k = 2; k >= 0; --k) {
-        if (nl[k] <= 0) continue;
-        HIP_TRY(hipStreamWaitEvent(ctx->side.st[k], ctx->side.fork[0], 0));
-        if (k == 2) hipLaunchKernelGGL((k_chain_lds<1024>), dim3((unsigned)nl[k]), dim3(64), 0, ctx->side.st[k], A, W[k]);
-        else if (k == 1) hipLaunchKernelGGL((k_chain_lds<512>), dim3((unsigned)nl[k]), dim3(64), 0, ctx->side.st[k], A, W[k]);
-        else hipLaunchKernelGGL((k_chain_lds<256>), dim3((unsigned)nl[k]), dim3(64), 0, ctx->side.st[k], A, W[k]);
-        HIP_TRY(hipEventRecord(ctx->side.done[k], ctx->side.st[k]));
-    }
-    hipLaunchKernelGGL((k_chain<CHAIN_CAP, SEED_CAP>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, A);
+    for (int k = 0; k < 3; ++k) T[k].n = (i64)h_cnt[k];
+    // ---- four launches at once: the routed tiers, then the lane tier
+    if ((rc = run_tiers(ctx, A, L, T, 3, true))) return rc;
+    launch_chain(CK_LANE, (unsigned)((n + 63) / 64), ctx->stream, A, T[0].W);
     HIP_TRY(hipEventRecord(ev[1], ctx->stream));
     // ---- what the lane tier left: LDS tier of 256 chains (or, with that switched off, the B-tree tier)
-    hipLaunchKernelGGL(k_chain_redo, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, (const ReadHdr*)C.hdr.p, n, 1, (const unsigned char*)L.cls, cc.route + 3, L.list[3], L.work[3]);   // (routed reads: their tiers may still be writing)
-    HIP_TRY(hipMemcpyAsync(&h_cnt[3], cc.route + 3, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    nl[3] = (i64)h_cnt[3];
-    if (nl[3] > 0) {
-        if ((rc = meme_scan_exclusive(ctx, L.work[3], L.woff[3], nl[3]))) return rc;
-        HIP_TRY(hipMemcpyAsync(&tw[3], L.woff[3] + nl[3], 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if ((rc = make_set(ctx, C.wave[3], L.list[3], L.woff[3], nl[3], tw[3], 4, !wave_tiers, &W[3]))) return rc;
-        used[3] = true;
-        if (wave_tiers) hipLaunchKernelGGL((k_chain_lds<256>), dim3((unsigned)nl[3]), dim3(64), 0, ctx->stream, A, W[3]);
-        else hipLaunchKernelGGL((k_chain_wave<288, 2048>), dim3((unsigned)nl[3]), dim3(64), 0, ctx->stream, A, W[3], (i64)0);
-    }
-    for (int k = 0; k < 3; ++k) if (nl[k] > 0) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->side.done[k], 0));
+    if ((rc = redo_tier(ctx, A, L, cc.route, T[3], 1, L.cls))) return rc;
+    for (int k = 0; k < 3; ++k) if (T[k].n > 0) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->side.done[k], 0));
     HIP_TRY(hipEventRecord(ev[4], ctx->stream));
     // ---- the B-tree tier for what is left (fallback == 3)
-    hipLaunchKernelGGL(k_chain_redo, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, (const ReadHdr*)C.hdr.p, n, 3, (const unsigned char*)nullptr, cc.route + 4, L.list[4], L.work[4]);
-    HIP_TRY(hipMemcpyAsync(&h_cnt[4], cc.route + 4, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    nl[4] = (i64)h_cnt[4];
-    if (nl[4] > 0) {
-        if ((rc = meme_scan_exclusive(ctx, L.work[4], L.woff[4], nl[4]))) return rc;
-        HIP_TRY(hipMemcpyAsync(&tw[4], L.woff[4] + nl[4], 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if ((rc = make_set(ctx, C.wave[4], L.list[4], L.woff[4], nl[4], tw[4], 5, true, &W[4]))) return rc;
-        used[4] = true;
-        hipLaunchKernelGGL((k_chain_wave<288, 2048>), dim3((unsigned)nl[4]), dim3(64), 0, ctx->stream, A, W[4], (i64)0);
-    }
+    if ((rc = redo_tier(ctx, A, L, cc.route, T[4], 3, nullptr))) return rc;
     HIP_TRY(hipEventRecord(ev[2], ctx->stream));
-    hipLaunchKernelGGL(k_chain_counts, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, (const ReadHdr*)C.hdr.p, n, cc.nch, cc.nsd, cc.tree, cc.fb);
-    if ((rc = meme_scan_exclusive(ctx, cc.nch, cc.chain_off, n))) return rc;
-    i64 tot[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(&tot[0], cc.chain_off + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = meme_scan_exclusive(ctx, cc.nsd, cc.seed_off, n))) return rc;
-    HIP_TRY(hipMemcpyAsync(&tot[1], cc.seed_off + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if ((rc = meme_buf_reserve(ctx, C.chains, (size_t)(tot[0] + 1) * sizeof(meme_chain)))) return rc;
-    if ((rc = meme_buf_reserve(ctx, C.seeds, (size_t)(tot[1] + 1) * sizeof(meme_chain_seed)))) return rc;
-    PackSets PS;
-    memset(&PS, 0, sizeof(PS));
-    for (int k = 0; k < 5; ++k) if (used[k]) { PS.woff[k + 1] = W[k].woff; PS.C[k + 1] = W[k].C; PS.S[k + 1] = W[k].S; PS.F[k + 1] = W[k].F; }
-    hipLaunchKernelGGL(k_chain_pack, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, (const DChain*)C.ch1.p, (const DSeed*)C.sd1.p, PS,
-                       (const ReadHdr*)C.hdr.p, (const i64*)cc.chain_off, (const i64*)cc.seed_off, n, (meme_chain*)C.chains.p, (meme_chain_seed*)C.seeds.p);
-    HIP_TRY(hipGetLastError());
+    if ((rc = chain_pack(ctx, cc, T, totals))) return rc;
     HIP_TRY(hipEventRecord(ev[3], ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    {
-        float ms = 0.f, ms1 = 0.f, ms3 = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[3]));
-        HIP_TRY(hipEventElapsedTime(&ms1, ev[0], ev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms3, ev[4], ev[2]));
-        ctx->tm.chain_kernel_ms = ms;          // (includes the small host round trips between the tiers)
-        ctx->tm.chain_pass2_ms = ms - ms1;     // everything after the lane-per-read tier has finished (the routed tiers run beside it)
-        ctx->tm.chain_tier3_ms = ms3;
-        ctx->tm.chain_tier2_reads = nl[0] + nl[1] + nl[2] + nl[3];
-        ctx->tm.chain_tier3_reads = nl[4];
-    }
-    ctx->chain_reads = n;
-    ctx->chain_tier2_reads = nl[0] + nl[1] + nl[2] + nl[3];
-    ctx->chain_tier3_reads = nl[4];
-    totals[0] = tot[0]; totals[1] = tot[1];
+    float ms = 0.f, ms1 = 0.f, ms3 = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[3]));
+    HIP_TRY(hipEventElapsedTime(&ms1, ev[0], ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms3, ev[4], ev[2]));
+    ctx->tm.chain_kernel_ms = ms;          // (includes the small host round trips between the tiers)
+    ctx->tm.chain_pass2_ms = ms - ms1;     // everything after the lane-per-read tier has finished (the routed tiers run beside it)
+    ctx->tm.chain_tier3_ms = ms3;
+    ctx->tm.chain_tier2_reads = T[0].n + T[1].n + T[2].n + T[3].n;
+    ctx->tm.chain_tier3_reads = T[4].n;
     return MEME_OK;
 }
 
@@ -1551,7 +1552,7 @@ extern "C" int meme_chain_last_batch_host(meme_ctx* ctx, const meme_contig* cont
     i64 nfb = 0;
     for (i64 i = 0; i < n; ++i) nfb += out->fallback[i] ? 1 : 0;
     out->n_fallback = nfb;                 // always 0: both tiers run on the device
-    out->n_tier2 = ctx->chain_tier2_reads;
+    out->n_tier2 = ctx->tm.chain_tier2_reads;
     return MEME_OK;
 }
 

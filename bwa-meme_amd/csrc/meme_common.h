@@ -56,6 +56,7 @@ template <bool HOST> struct Buf {   // growable device workspace (meme_buf_reser
     Buf() = default;
     Buf(const Buf&) = delete; Buf& operator=(const Buf&) = delete;
     ~Buf() { if (p) (void)(HOST ? hipHostFree(p) : hipFree(p)); }
+    template <class T> T* as() const { return (T*)p; }
 };
 typedef Buf<false> DevBuf;
 typedef Buf<true> HostBuf;
@@ -67,6 +68,7 @@ template <int N> struct Events {    // events of a stage, created on first use, 
     Events(const Events&) = delete; Events& operator=(const Events&) = delete;
     ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
     hipEvent_t& operator[](int i) { return e[i]; }
+    hipError_t ensure() { for (hipEvent_t& x : e) if (!x) { const hipError_t r = hipEventCreate(&x); if (r != hipSuccess) return r; } return hipSuccess; }   // whichever are missing
 };
 struct Stream {                     // a stream besides the caller's, created on first use, destroyed with its owner
     hipStream_t s = nullptr;
@@ -97,9 +99,19 @@ struct ChainLists {    // list, work and work offsets of the five wavefront laun
     i64 *list[5], *work[5], *woff[5]; unsigned char* cls; size_t bytes;
     ChainLists(void* base, i64 n) { Carve c(base); for (int k = 0; k < 5; ++k) { list[k] = c.col(n); work[k] = c.col(n); woff[k] = c.col(n); } cls = c.take<unsigned char>(n + 64); bytes = c.bytes; }
 };
-struct ExtCounts {     // jobs left / right and sequence bytes per read, their scans, seeds selected per round and its scan
-    i64 *cntL, *cntR, *cntB, *offL, *offR, *offB, *cntS, *offS; size_t bytes;
-    ExtCounts(void* base, i64 n) { Carve c(base); cntL = c.col(n); cntR = c.col(n); cntB = c.col(n); offL = c.col(n); offR = c.col(n); offB = c.col(n); cntS = c.col(n); offS = c.col(n); bytes = c.bytes; }
+enum { EXT_L = 0, EXT_R = 1, EXT_B = 2 };   // ExtCounts columns: left jobs, right jobs, sequence bytes
+struct ExtCounts {     // per read cnt[k], their scans off[k], seeds selected per round and its scan.  The multi-slab path copies the three off columns as one block: adjacent(), checked there
+    i64 *cnt[3], *off[3], *cntS, *offS; size_t bytes;
+    ExtCounts(void* base, i64 n) { Carve c(base); for (i64*& q : cnt) q = c.col(n); for (i64*& q : off) q = c.col(n); cntS = c.col(n); offS = c.col(n); bytes = c.bytes; }
+    bool adjacent(i64 n) const { return off[1] == off[0] + (n + 1) && off[2] == off[1] + (n + 1); }
+};
+struct CountScan {     // ExtWs::flt_cnt (seeds the filter keeps per read; the scan is the new seed_off) and ExtWs::live_cnt (surviving records per read): counts, their scan
+    i64 *cnt, *off; size_t bytes;
+    CountScan(void* base, i64 n) { Carve c(base); cnt = c.col(n); off = c.col(n); bytes = c.bytes; }
+};
+struct ExtRetry {      // ExtWs::retry: the jobs a fold sends to the next band width, attempts alternating between the halves (nmax: the larger side's jobs)
+    meme_seqpair* half[2]; size_t bytes;
+    ExtRetry(void* base, i64 nmax) { Carve c(base); for (meme_seqpair*& q : half) q = c.take<meme_seqpair>((size_t)nmax + 1); bytes = c.bytes; }
 };
 struct ExtRounds {     // extension in rounds: per-read state, reads still active, seeds selected
     int4* state; uint8_t* act; uint8_t* sel; size_t bytes;
@@ -157,9 +169,9 @@ struct ChainWs {
 };
 enum { EXT_CTR_RETRY = 0, EXT_CTR_FLT_JOBS = 2, EXT_CTR_CENSUS = 8, EXT_CTR_HEAVY = 24, EXT_CTR_BYTES = 256 };   // ExtWs::counters (u64); the census takes 11
 struct ExtWs {
-    DevBuf rmax, regs, order, counts, pairs_l, pairs_r, retry, seq, counters;   // counts: ExtCounts; retry: two halves
-    DevBuf flt_sc, flt_jobs, flt_cnt, flt_seeds, flt_score, flt_hsp;           // the seed filter's: scores, jobs, counts + new seed offsets, kept seeds, their scores, thresholds
-    DevBuf live_cnt, live_regs, rounds, heavy;                                 // surviving records (counts + scan, packed), ExtRounds, the heavy reads
+    DevBuf rmax, regs, order, counts, pairs_l, pairs_r, retry, seq, counters;   // counts: ExtCounts; retry: ExtRetry
+    DevBuf flt_sc, flt_jobs, flt_cnt, flt_seeds, flt_score, flt_hsp;           // the seed filter's: scores, jobs, CountScan (the scan = new seed offsets), kept seeds, their scores, thresholds
+    DevBuf live_cnt, live_regs, rounds, heavy;                                 // surviving records (CountScan, packed), ExtRounds, the heavy reads
     HostBuf h_reg_off, h_regs; Events<2> ev;
 };
 struct BswWs { DevBuf pairs, refb, qerb, order, ws, hist; Events<2> ev; };   // hist: BswSort; ev: begin / end of the last meme_bsw_launch
@@ -206,6 +218,8 @@ struct meme_ctx {
     i64 seed_blocks_per_cu = 5;
     i64 max_batch = 0;                 // > 0: the batch calls behind seeding (extension, global alignment) refuse more reads / jobs than this with
                                        // MEME_E_CAPACITY, as they do when their scratch would not fit: a caller's memory bound, and how the tests reach that path
+    i64 ext_slab_jobs = 8 << 20;       // the extension stage poses and aligns its jobs in slabs of whole reads: at most this many jobs per side and ext_slab_bytes of job sequence each, and at
+    i64 ext_slab_bytes = (i64)3 << 29; // least one read (SeqPair offsets are 32-bit).  ext_slab_jobs has a tuning key: a bound, and how the tests reach the multi-slab path
     i64 ext_split = 1;                 // 1: the extension stage's read-walking kernels run eight lanes per read for reads with at most 8 chained seeds, a wavefront per read for the rest; 0: a wavefront per read
     i64 bsw_circ = 1;                  // 1: lane-per-pair banded SW of queries longer than 2w + 2 columns keeps its columns in a ring (k_bsw_lane_circ); 0: a word per query column
     i64 sam_max_batch = 0;             // > 0: meme_sam_format_batch_host refuses more record slots than this with MEME_E_CAPACITY (the caller then formats in pieces)
@@ -224,7 +238,6 @@ struct meme_ctx {
     // timings
     i64 sam_text_reads = 0;            // reads of the batch whose names / qualities meme_sam_stage_text staged (0: none)
     bool sam_has_quals = false;
-    i64 chain_reads = 0, chain_tier2_reads = 0, chain_tier3_reads = 0;   // of the last meme_chain_run(): reads chained, of which by the wavefront-per-read tier
     meme_timings tm = {};
 };
 
@@ -241,6 +254,10 @@ int meme_stage_contigs(meme_ctx* ctx, DevBuf& buf, std::vector<unsigned char>& h
                        const char* prefix, ContigTab* out);
 // exclusive prefix sum of n 64-bit counts into out[0..n] (out[n] = total), asynchronous on ctx->stream (meme_scan.hip)
 int meme_scan_exclusive(meme_ctx* ctx, const i64* d_in, i64* d_out, i64 n);
+// the same, and the total on its way to *h_total (an asynchronous 8-byte copy: the caller synchronises ctx->stream before reading it)
+int meme_scan_total(meme_ctx* ctx, const i64* d_in, i64* d_out, i64 n, i64* h_total);
+// false: growing a workspace that holds `have` bytes to `need` would take more than half of the free HBM (*free_b, for the message); the caller refuses with MEME_E_CAPACITY
+inline bool meme_fits_free_hbm(size_t need, size_t have, size_t* free_b) { size_t total_b = 0; return need <= have || hipMemGetInfo(free_b, &total_b) != hipSuccess || need <= *free_b / 2 + have; }
 // the banded-SW kernels on device-resident pairs, no host synchronisation (meme_bsw.hip); host_maxq = an upper bound of the query lengths or -1
 int meme_bsw_launch(meme_ctx* ctx, meme_seqpair* d_pairs, const uint8_t* d_ref, const uint8_t* d_qer, int npairs, int w, const meme_bsw_opt* opt,
                     int host_maxq);

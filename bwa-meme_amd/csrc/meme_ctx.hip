@@ -136,32 +136,19 @@ extern "C" int meme_get_timings(meme_ctx* ctx, meme_timings* out) {
 
 extern "C" int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value) {
     if (!ctx || !key) return MEME_E_ARG;
-    if (!strcmp(key, "seed_blocks")) ctx->seed_blocks = value;
-    else if (!strcmp(key, "smem_cap")) ctx->smem_cap = value < 8 ? 8 : value;
-    else if (!strcmp(key, "seed_defer")) ctx->seed_defer = value;
-    else if (!strcmp(key, "max_batch")) ctx->max_batch = value;
-    else if (!strcmp(key, "sam_max_batch")) ctx->sam_max_batch = value;
-    else if (!strcmp(key, "bsw_circ")) ctx->bsw_circ = value;
-    else if (!strcmp(key, "ext_split")) ctx->ext_split = value;
-    else if (!strcmp(key, "ext_census")) ctx->ext_census = value;
-    else if (!strcmp(key, "gcig_zcap")) ctx->gcig_zcap = value;
-    else if (!strcmp(key, "gcig_groups")) {
-        if (value != 0 && value != 1) { meme_set_error("gcig_groups must be 0 or 1"); return MEME_E_ARG; }
-        ctx->gcig_groups = value;
-    }
-    else if (!strcmp(key, "ext_live_only")) ctx->ext_live_only = value;
-    else if (!strcmp(key, "ext_rounds")) ctx->ext_rounds = value < 0 ? 0 : value;
-    else if (!strcmp(key, "bsw_blocks")) ctx->bsw_blocks = value;
-    else if (!strcmp(key, "bsw_lane_min_pairs")) ctx->bsw_lane_min_pairs = value;
-    else if (!strcmp(key, "chain_wave_tiers")) ctx->chain_wave_tiers = value;
-    else if (!strcmp(key, "chain_lane_hits")) ctx->chain_lane_hits = value;
-    else if (!strcmp(key, "chain_light_hits")) ctx->chain_light_hits = value;
-    else if (!strcmp(key, "group_lanes")) {
-        if (value != 1 && value != 2 && value != 4 && value != 8 && value != 16 && value != 32) { meme_set_error("group_lanes must be 1, 2, 4, 8, 16 or 32"); return MEME_E_ARG; }
-        ctx->group_lanes = value;
-    } else if (!strcmp(key, "seed_blocks_per_cu")) ctx->seed_blocks_per_cu = value < 1 ? 1 : value;
-    else { meme_set_error("unknown tuning key %s", key); return MEME_E_ARG; }
-    return MEME_OK;
+    if (!strcmp(key, "gcig_groups") && value != 0 && value != 1) { meme_set_error("gcig_groups must be 0 or 1"); return MEME_E_ARG; }
+    if (!strcmp(key, "group_lanes") && value != 1 && value != 2 && value != 4 && value != 8 && value != 16 && value != 32) { meme_set_error("group_lanes must be 1, 2, 4, 8, 16 or 32"); return MEME_E_ARG; }
+    const i64 any = INT64_MIN;   // no lower clamp
+    static const struct { const char* key; i64 meme_ctx::*member; i64 at_least; } keys[] = {
+        {"seed_blocks", &meme_ctx::seed_blocks, any}, {"smem_cap", &meme_ctx::smem_cap, 8}, {"seed_defer", &meme_ctx::seed_defer, any}, {"max_batch", &meme_ctx::max_batch, any},
+        {"sam_max_batch", &meme_ctx::sam_max_batch, any}, {"bsw_circ", &meme_ctx::bsw_circ, any}, {"ext_split", &meme_ctx::ext_split, any}, {"ext_slab_jobs", &meme_ctx::ext_slab_jobs, 1},
+        {"ext_census", &meme_ctx::ext_census, any}, {"gcig_zcap", &meme_ctx::gcig_zcap, any}, {"gcig_groups", &meme_ctx::gcig_groups, any}, {"ext_live_only", &meme_ctx::ext_live_only, any},
+        {"ext_rounds", &meme_ctx::ext_rounds, 0}, {"bsw_blocks", &meme_ctx::bsw_blocks, any}, {"bsw_lane_min_pairs", &meme_ctx::bsw_lane_min_pairs, any},
+        {"chain_wave_tiers", &meme_ctx::chain_wave_tiers, any}, {"chain_lane_hits", &meme_ctx::chain_lane_hits, any}, {"chain_light_hits", &meme_ctx::chain_light_hits, any},
+        {"group_lanes", &meme_ctx::group_lanes, any}, {"seed_blocks_per_cu", &meme_ctx::seed_blocks_per_cu, 1}};
+    for (const auto& k : keys) if (!strcmp(key, k.key)) { ctx->*k.member = value < k.at_least ? k.at_least : value; return MEME_OK; }
+    meme_set_error("unknown tuning key %s", key);
+    return MEME_E_ARG;
 }
 
 extern "C" int meme_index_share(meme_ctx* ctx, meme_ctx* owner);

@@ -645,10 +645,25 @@ __global__ void __launch_bounds__(256) k_ext_census(const meme_seqpair* __restri
     if (threadIdx.x < 11 && acc[threadIdx.x]) atomicAdd(&cnt[threadIdx.x], acc[threadIdx.x]);
 }
 
-}  // namespace
+// ---- the host side: meme_extend_last_batch_host in phases around one ExtRun ----------------------------------------------------------
+struct ExtRun {
+    meme_ctx* ctx; const meme_chain_opt* copt; const meme_ext_opt* eopt; int32_t n_contigs;
+    i64 n, n_chains, n_seeds;                       // reads, chains, chained seeds (before the filter) of the batch
+    ExtCounts ec = ExtCounts(nullptr, 0);
+    ExtArgs A;                                      // what every launch of k_ext_jobs starts from: the batch, the records, the counts
+    meme_bsw_opt bsw[2];                            // left / right (bswLeft / bswRight, src/bwamem.cpp:2953-2959)
+    unsigned long long* ctr = nullptr;              // ExtWs::counters
+    bool flt_read = true;                           // false: the seed filter ran and its two totals have yet to cross to the host
+    i64 h_flt[2] = {0, 0};                          // chained seeds after the filter, alignments it ran
+    i64 n_heavy = 0; const i64* d_heavy = nullptr;  // reads with more than EXT_LIGHT chained seeds (tuning "ext_split")
+    i64 tot[3] = {0, 0, 0};                         // the plan's totals: left jobs, right jobs, sequence bytes
+    std::vector<i64> h_off;                         // the plan's three offset columns on the host (more than one slab only)
+    i64 n_pairs = 0, n_retried = 0, n_calls = 0, n_seeds_ext = 0;   // n_seeds_ext: chained seeds whose extension jobs ran
+    float bsw_ms = 0.f;
+};
+struct Slab { i64 g0, g1, n[3], first[3]; };        // reads [g0, g1): its left jobs, right jobs and sequence bytes, and the batch's before it
 
-extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs, const meme_chain_opt* copt,
-                                           const meme_ext_opt* eopt, meme_ext_host_result* out) {
+int ext_check(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs, const meme_chain_opt* copt, const meme_ext_opt* eopt, meme_ext_host_result* out) {
     if (!ctx || !contigs || n_contigs < 1 || !copt || !eopt || !out) { meme_set_error("meme_extend_last_batch_host: null argument"); return MEME_E_ARG; }
     if (copt->max_occ < 1 || copt->l_pac < 1 || eopt->e_del < 1 || eopt->e_ins < 1 || eopt->w < 1) { meme_set_error("meme_extend_last_batch_host: bad options"); return MEME_E_ARG; }
     HIP_TRY(hipSetDevice(ctx->device));
@@ -660,284 +675,321 @@ extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* con
     }
     if (copt->l_pac * 2 != ctx->idx.n) { meme_set_error("meme_extend_last_batch_host: l_pac does not match the loaded index"); return MEME_E_ARG; }
     if (ctx->max_batch > 0 && n > ctx->max_batch) { meme_set_error("meme_extend_last_batch_host: %lld reads exceed the ctx's max_batch of %lld", (long long)n, (long long)ctx->max_batch); return MEME_E_CAPACITY; }
-    int rc;
-    i64 tot[2];
-    if ((rc = meme_chain_run(ctx, contigs, n_contigs, copt, tot))) return rc;
+    return MEME_OK;
+}
+// the stage's events and counters; what every launch starts from (chaining's seeds until the filter has had its say)
+int ext_begin(ExtRun& R) {
+    meme_ctx* ctx = R.ctx;
     ExtWs& E = ctx->ext;
     const ChainWs& C = ctx->chain;
-    Events<2>& ev = E.ev;
-    for (int i = 0; i < 2; ++i) if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
-    HIP_TRY(hipEventRecord(ev[0], ctx->stream));
-    const i64* d_choff = C.chain_off();
-    const i64* d_sdoff = C.seed_off(n);
-    const ContigTab ct(C.contigs.p, n_contigs, true);
-    const i64 n_chains = tot[0];
-    i64 n_seeds = tot[1];
+    HIP_TRY(E.ev.ensure());
+    HIP_TRY(hipEventRecord(E.ev[0], ctx->stream));
+    int rc;
     if ((rc = meme_buf_reserve(ctx, E.counters, EXT_CTR_BYTES))) return rc;
-    unsigned long long* const ctr = (unsigned long long*)E.counters.p;
-    // ---- mem_flt_chained_seeds: the read lengths it runs for and their thresholds, evaluated the way the reference's host code does
-    // (:579-583: float coefficients, double min_l, libm's log).  Never with reads below ~760 bases unless -W is given.
-    const meme_chain_seed* d_seeds = (const meme_chain_seed*)C.seeds.p;
-    const int* d_score = nullptr;
-    unsigned long long* d_fltcnt = ctr + EXT_CTR_FLT_JOBS;
-    bool flt = false;
-    {
-        const i64 max_len = ctx->batch.last_seed_max_len;
-        std::vector<int> hsp((size_t)max_len + 2, -1);
-        for (i64 l = 2; l <= max_len; ++l) {
-            const int l_query = (int)l;
-            const double min_l = copt->min_chain_weight ? 1.1f * copt->min_chain_weight : 5.5f * log(l_query);     // MEM_HSP_COEF, MEM_MINSC_COEF (:252-253)
-            if (min_l > 0.05f * l_query) continue;                                                                  // MEM_SEEDSW_COEF (:254)
-            hsp[(size_t)l] = (int)(eopt->a * min_l + .499);
-            if (hsp[(size_t)l] < 0) hsp[(size_t)l] = 0;
-            flt = true;
-        }
-        if (flt && n_seeds > 0) {
-            if (n_seeds >= 0x7fffffff) { meme_set_error("meme_extend_last_batch_host: %lld chained seeds in one batch", (long long)n_seeds); return MEME_E_CAPACITY; }
-            if ((rc = meme_buf_reserve(ctx, E.flt_sc, (size_t)(n_seeds + 1) * 4)) || (rc = meme_buf_reserve(ctx, E.flt_jobs, (size_t)(n_seeds + 1) * sizeof(meme_seedsw_job))) ||
-                (rc = meme_buf_reserve(ctx, E.flt_cnt, (size_t)(n + 1) * 16)) || (rc = meme_buf_reserve(ctx, E.flt_seeds, (size_t)(n_seeds + 1) * sizeof(meme_chain_seed))) ||
-                (rc = meme_buf_reserve(ctx, E.flt_score, (size_t)(n_seeds + 1) * 4)) || (rc = meme_buf_reserve(ctx, E.flt_hsp, hsp.size() * 4))) return rc;
-            HIP_TRY(hipMemcpyAsync(E.flt_hsp.p, hsp.data(), hsp.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(hipMemsetAsync(d_fltcnt, 0, 8, ctx->stream));
-            FltArgs F;
-            memset(&F, 0, sizeof(F));
-            F.read_off = (const i64*)ctx->batch.read_off.p; F.n = n; F.chain_off = d_choff; F.chains = (meme_chain*)C.chains.p; F.seed_off = d_sdoff; F.seeds = d_seeds;
-            F.l_pac = copt->l_pac; F.contig_off = ct.off; F.contig_len = ct.len; F.n_contigs = n_contigs;
-            F.hsp = (const int*)E.flt_hsp.p; F.a = eopt->a; F.sc = (int*)E.flt_sc.p; F.jobs = (meme_seedsw_job*)E.flt_jobs.p; F.n_jobs = d_fltcnt;
-            F.cnt = (i64*)E.flt_cnt.p; F.off2 = F.cnt + (n + 1); F.seeds2 = (meme_chain_seed*)E.flt_seeds.p; F.score2 = (int*)E.flt_score.p;
-            hipLaunchKernelGGL(k_flt_pose, dim3((unsigned)n), dim3(64), 0, ctx->stream, F);
-            if ((rc = meme_seedsw_launch(ctx, F.jobs, d_fltcnt, n_seeds, F.sc, eopt))) return rc;
-            hipLaunchKernelGGL((k_flt_apply<false>), dim3((unsigned)n), dim3(64), 0, ctx->stream, F);
-            if ((rc = meme_scan_exclusive(ctx, F.cnt, (i64*)F.off2, n))) return rc;
-            hipLaunchKernelGGL((k_flt_apply<true>), dim3((unsigned)n), dim3(64), 0, ctx->stream, F);
-            HIP_TRY(hipGetLastError());
-            d_sdoff = F.off2; d_seeds = F.seeds2; d_score = F.score2;
-        } else flt = false;
-    }
-    if ((rc = meme_buf_reserve(ctx, E.rmax, (size_t)(n_chains + 1) * 16)) || (rc = meme_buf_reserve(ctx, E.regs, (size_t)(n_seeds + 1) * sizeof(meme_alnreg))) ||
-        (rc = meme_buf_reserve(ctx, E.order, (size_t)(n_seeds + 1) * 4)) || (rc = meme_buf_reserve(ctx, E.counts, ExtCounts(nullptr, n).bytes))) return rc;
-    ExtArgs A;
+    R.ctr = E.counters.as<unsigned long long>();
+    R.h_flt[0] = R.n_seeds;
+    const ContigTab ct(C.contigs.p, R.n_contigs, true);
+    ExtArgs& A = R.A;
     memset(&A, 0, sizeof(A));
-    A.reads = (const uint8_t*)ctx->batch.reads.p; A.read_off = (const i64*)ctx->batch.read_off.p; A.g0 = 0; A.ns = n;
-    A.chain_off = d_choff; A.chains = (const meme_chain*)C.chains.p; A.seed_off = d_sdoff; A.seeds = d_seeds; A.seed_score = d_score; A.frac_rep = (const float*)C.frac.p;
-    A.pac = ctx->idx.pac; A.l_pac = copt->l_pac;
+    A.reads = ctx->batch.reads.as<const uint8_t>(); A.read_off = ctx->batch.read_off.as<const i64>(); A.g0 = 0; A.ns = R.n;
+    A.chain_off = C.chain_off(); A.chains = C.chains.as<const meme_chain>(); A.seed_off = C.seed_off(R.n); A.seeds = C.seeds.as<const meme_chain_seed>(); A.frac_rep = C.frac.as<const float>();
+    A.pac = ctx->idx.pac; A.l_pac = R.copt->l_pac;
     A.contig_off = ct.off; A.contig_len = ct.len;
-    A.o = *eopt;
-    A.rmax = (i64*)E.rmax.p; A.regs = (meme_alnreg*)E.regs.p; A.order = (int*)E.order.p;
-    const ExtCounts ec(E.counts.p, n);
-    A.cntL = ec.cntL; A.cntR = ec.cntR; A.cntB = ec.cntB;
-    meme_bsw_opt bl, br;
+    A.o = *R.eopt;
+    return MEME_OK;
+}
+// behind the filter: the records, the extension order and the per-read counts; the banded-SW options of the two sides
+int ext_workspace(ExtRun& R) {
+    meme_ctx* ctx = R.ctx;
+    ExtWs& E = ctx->ext;
+    const meme_ext_opt* eopt = R.eopt;
+    ExtArgs& A = R.A;
+    int rc;
+    if ((rc = meme_buf_reserve(ctx, E.rmax, (size_t)(R.n_chains + 1) * 16)) || (rc = meme_buf_reserve(ctx, E.regs, (size_t)(R.n_seeds + 1) * sizeof(meme_alnreg))) ||
+        (rc = meme_buf_reserve(ctx, E.order, (size_t)(R.n_seeds + 1) * 4)) || (rc = meme_buf_reserve(ctx, E.counts, ExtCounts(nullptr, R.n).bytes))) return rc;
+    R.ec = ExtCounts(E.counts.p, R.n);
+    A.rmax = E.rmax.as<i64>(); A.regs = E.regs.as<meme_alnreg>(); A.order = E.order.as<int>();
+    A.cntL = R.ec.cnt[EXT_L]; A.cntR = R.ec.cnt[EXT_R]; A.cntB = R.ec.cnt[EXT_B];
+    meme_bsw_opt& bl = R.bsw[0];
     memset(&bl, 0, sizeof(bl));
     bl.o_del = eopt->o_del; bl.e_del = eopt->e_del; bl.o_ins = eopt->o_ins; bl.e_ins = eopt->e_ins; bl.zdrop = eopt->zdrop; bl.a = eopt->a; bl.b = eopt->b;
-    br = bl;
-    bl.end_bonus = eopt->pen_clip5;                   // bswLeft / bswRight, src/bwamem.cpp:2953-2959
-    br.end_bonus = eopt->pen_clip3;
-    unsigned long long* d_nretry = ctr + EXT_CTR_RETRY;
-    i64* d_cntS = ec.cntS;                          // seeds selected per read in a round, and its scan
-    i64* d_offS = ec.offS;
-    unsigned long long* d_census = ctr + EXT_CTR_CENSUS;
-    if (ctx->ext_census) HIP_TRY(hipMemsetAsync(d_census, 0, 11 * 8, ctx->stream));
-    // ---- light and heavy reads (round 6): the list of reads with more than EXT_LIGHT chained seeds; everything else runs eight lanes per read
-    i64 n_heavy = 0;
-    const i64* d_heavy = nullptr;
-    const bool split = ctx->ext_split != 0;
-    if (split) {
-        if ((rc = meme_buf_reserve(ctx, E.heavy, (size_t)(n + 1) * 8))) return rc;
-        unsigned long long* d_nheavy = ctr + EXT_CTR_HEAVY;
-        HIP_TRY(hipMemsetAsync(d_nheavy, 0, 8, ctx->stream));
-        hipLaunchKernelGGL(k_ext_split, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, d_sdoff, n, (i64*)E.heavy.p, d_nheavy);
-        unsigned long long h = 0;
-        HIP_TRY(hipMemcpyAsync(&h, d_nheavy, 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        n_heavy = (i64)h; d_heavy = (const i64*)E.heavy.p;
-    }
-    // a kernel that walks the reads of [X.g0, X.g0 + X.ns): one launch of wavefronts, or -- split, and the range is the whole batch -- eight lanes per light read + a wavefront per listed read
-    auto launch_jobs = [&](ExtArgs X, bool write) {
-        const bool two = split && X.g0 == 0 && X.ns == n;
-        X.list = nullptr; X.nlist = 0; X.light = 0;
-        if (!two) {
-            if (write) hipLaunchKernelGGL((k_ext_jobs<true, 64>), dim3((unsigned)((X.ns + 3) / 4)), dim3(256), 0, ctx->stream, X);
-            else hipLaunchKernelGGL((k_ext_jobs<false, 64>), dim3((unsigned)((X.ns + 3) / 4)), dim3(256), 0, ctx->stream, X);
-            return;
-        }
-        X.light = 1;
-        if (write) hipLaunchKernelGGL((k_ext_jobs<true, 8>), dim3((unsigned)((X.ns + 31) / 32)), dim3(256), 0, ctx->stream, X);
-        else hipLaunchKernelGGL((k_ext_jobs<false, 8>), dim3((unsigned)((X.ns + 31) / 32)), dim3(256), 0, ctx->stream, X);
-        if (n_heavy > 0) {
-            X.light = 0; X.list = d_heavy; X.nlist = n_heavy;
-            if (write) hipLaunchKernelGGL((k_ext_jobs<true, 64>), dim3((unsigned)((n_heavy + 3) / 4)), dim3(256), 0, ctx->stream, X);
-            else hipLaunchKernelGGL((k_ext_jobs<false, 64>), dim3((unsigned)((n_heavy + 3) / 4)), dim3(256), 0, ctx->stream, X);
-        }
-    };
-    i64 n_pairs = 0, n_retried = 0, n_calls = 0;
-    float bsw_ms = 0.f;
-    i64 h_flt[2] = {n_seeds, 0};                    // chained seeds after the filter, alignments it ran
-    bool flt_read = !flt;
-    std::vector<i64> h_off;
-    // ---- the jobs of the seeds `A.mode` / `A.sel` name: plan (job and byte counts of every read, their scans), sequences, banded SW left then right
-    // with the band doubled once where the reference doubles it, results folded into the records.  *n_sel_out: what k_ext_advance selected for this round.
-    auto run_jobs = [&](i64* n_sel_out) -> int {
-        int rc;
-        if (A.mode != 2) launch_jobs(A, false);      // (in rounds k_ext_advance has counted)
-        for (int k = 0; k < 3; ++k) if ((rc = meme_scan_exclusive(ctx, ec.cntL + k * (n + 1), ec.offL + k * (n + 1), n))) return rc;
-        i64 tot3[3] = {0, 0, 0};
-        for (int k = 0; k < 3; ++k) HIP_TRY(hipMemcpyAsync(&tot3[k], ec.offL + k * (n + 1) + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (n_sel_out) {
-            if ((rc = meme_scan_exclusive(ctx, d_cntS, d_offS, n))) return rc;
-            HIP_TRY(hipMemcpyAsync(n_sel_out, d_offS + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (!flt_read) {
-            HIP_TRY(hipMemcpyAsync(&h_flt[0], d_sdoff + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipMemcpyAsync(&h_flt[1], d_fltcnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        flt_read = true;
-        // ---- slabs of reads whose jobs' sequences fit 32-bit offsets (SeqPair::idr / idq); the per-read offsets cross to the host only when one slab is not enough
-        const i64 SLAB_BYTES = (i64)3 << 29, SLAB_JOBS = 8 << 20;
-        const bool one_slab = tot3[2] <= SLAB_BYTES && tot3[0] <= SLAB_JOBS && tot3[1] <= SLAB_JOBS;
-        if (tot3[0] + tot3[1] == 0) return MEME_OK;
-        if (!one_slab) {
-            h_off.resize((size_t)(3 * (n + 1)));
-            HIP_TRY(hipMemcpyAsync(h_off.data(), ec.offL, h_off.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-        }
-        const i64* oL = one_slab ? nullptr : h_off.data();
-        const i64* oR = one_slab ? nullptr : oL + (n + 1);
-        const i64* oB = one_slab ? nullptr : oR + (n + 1);
-        for (i64 g0 = 0; g0 < n;) {
-            i64 g1 = n, nL = tot3[0], nR = tot3[1], nB = tot3[2], j0L = 0, j0R = 0, b0 = 0;
-            if (!one_slab) {
-                g1 = g0 + 1;
-                while (g1 < n && oB[g1 + 1] - oB[g0] <= SLAB_BYTES && oL[g1 + 1] - oL[g0] <= SLAB_JOBS && oR[g1 + 1] - oR[g0] <= SLAB_JOBS) {
-                    i64 step = 1;                               // gallop to the slab's end
-                    while (g1 + 2 * step < n && oB[g1 + 2 * step + 1] - oB[g0] <= SLAB_BYTES && oL[g1 + 2 * step + 1] - oL[g0] <= SLAB_JOBS &&
-                           oR[g1 + 2 * step + 1] - oR[g0] <= SLAB_JOBS) step *= 2;
-                    g1 += step;
-                }
-                if (oB[g1] - oB[g0] >= ((i64)1 << 31)) { meme_set_error("a read's extension jobs need more than 2 GiB of sequence"); return MEME_E_CAPACITY; }
-                nL = oL[g1] - oL[g0]; nR = oR[g1] - oR[g0]; nB = oB[g1] - oB[g0];
-                j0L = oL[g0]; j0R = oR[g0]; b0 = oB[g0];
-            }
-            const i64 nmax = nL > nR ? nL : nR;
-            if ((rc = meme_buf_reserve(ctx, E.pairs_l, (size_t)(nL + 1) * sizeof(meme_seqpair))) || (rc = meme_buf_reserve(ctx, E.pairs_r, (size_t)(nR + 1) * sizeof(meme_seqpair))) ||
-                (rc = meme_buf_reserve(ctx, E.retry, (size_t)(2 * nmax + 2) * sizeof(meme_seqpair))) || (rc = meme_buf_reserve(ctx, E.seq, (size_t)nB + 256))) return rc;
-            ExtArgs S = A;
-            S.g0 = g0; S.ns = g1 - g0;
-            // (the scans cover the whole batch: a slab's first read has its own offsets to subtract)
-            S.offL = ec.offL + g0; S.offR = ec.offR + g0; S.offB = ec.offB + g0;
-            S.job0L = j0L; S.job0R = j0R; S.byte0 = b0;
-            S.L = (meme_seqpair*)E.pairs_l.p; S.R = (meme_seqpair*)E.pairs_r.p; S.seq = (uint8_t*)E.seq.p;
-            launch_jobs(S, true);
-            HIP_TRY(hipGetLastError());
-            if (ctx->ext_census) {
-                if (nL) hipLaunchKernelGGL(k_ext_census, dim3(grid_blocks(nL, 256)), dim3(256), 0, ctx->stream, (const meme_seqpair*)S.L, nL, (const uint8_t*)S.seq, eopt->w, d_census);
-                if (nR) hipLaunchKernelGGL(k_ext_census, dim3(grid_blocks(nR, 256)), dim3(256), 0, ctx->stream, (const meme_seqpair*)S.R, nR, (const uint8_t*)S.seq, eopt->w, d_census);
-            }
-            for (int dir = 0; dir < 2; ++dir) {
-                meme_seqpair* P = dir == 0 ? S.L : S.R;
-                i64 np = dir == 0 ? nL : nR;
-                if (dir == 1 && np > 0) hipLaunchKernelGGL(k_ext_h0, dim3(grid_blocks(np, 256)), dim3(256), 0, ctx->stream, P, np, (const meme_alnreg*)A.regs);
-                for (int attempt = 0; attempt < EXT_BAND_TRIES && np > 0; ++attempt) {
-                    const int w = eopt->w << attempt;
-                    if ((rc = meme_bsw_launch(ctx, P, S.seq, S.seq, (int)np, w, dir == 0 ? &bl : &br, (int)ctx->batch.last_seed_max_len))) return rc;
-                    HIP_TRY(hipMemsetAsync(d_nretry, 0, 8, ctx->stream));
-                    FoldArgs F;
-                    F.pairs = P; F.n = np; F.regs = A.regs; F.chains = A.chains; F.seed_off = A.seed_off; F.seeds = A.seeds; F.read_off = A.read_off;
-                    F.o = *eopt; F.w = w; F.last = attempt + 1 == EXT_BAND_TRIES;
-                    F.retry = (meme_seqpair*)E.retry.p + (size_t)(attempt & 1) * (size_t)(nmax + 1); F.n_retry = d_nretry;
-                    if (dir == 0) hipLaunchKernelGGL((k_ext_fold<true>), dim3(grid_blocks(np, 256)), dim3(256), 0, ctx->stream, F);
-                    else hipLaunchKernelGGL((k_ext_fold<false>), dim3(grid_blocks(np, 256)), dim3(256), 0, ctx->stream, F);
-                    unsigned long long h_retry = 0;
-                    HIP_TRY(hipMemcpyAsync(&h_retry, d_nretry, 8, hipMemcpyDeviceToHost, ctx->stream));
-                    HIP_TRY(hipStreamSynchronize(ctx->stream));
-                    { float ms = 0.f; if (meme_bsw_last_ms(ctx, &ms) == hipSuccess) bsw_ms += ms; }
-                    n_pairs += np; ++n_calls;
-                    if (attempt > 0) n_retried += np;
-                    P = F.retry;
-                    np = (i64)h_retry;
-                }
-            }
-            g0 = g1;
-        }
-        return MEME_OK;
-    };
+    R.bsw[1] = bl;
+    R.bsw[0].end_bonus = eopt->pen_clip5;
+    R.bsw[1].end_bonus = eopt->pen_clip3;
+    if (ctx->ext_census) HIP_TRY(hipMemsetAsync(R.ctr + EXT_CTR_CENSUS, 0, 11 * 8, ctx->stream));
+    return MEME_OK;
+}
+PurgeArgs purge_args(const ExtRun& R) {      // the purge's view of the same arrays
+    const ExtArgs& A = R.A;
     PurgeArgs P;
-    P.read_off = A.read_off; P.nreads = n; P.chain_off = A.chain_off; P.chains = A.chains; P.seed_off = A.seed_off; P.seeds = A.seeds;
-    P.regs = A.regs; P.order = A.order; P.o = *eopt;
-    const i64 rounds = ctx->ext_live_only ? ctx->ext_rounds : 0;
-    i64 n_seeds_ext = 0;                                // chained seeds whose extension jobs ran
-    if (rounds <= 0) {
-        // ---- the reference's batch: every chained seed extended, then the purge
-        A.mode = 0;
-        if ((rc = run_jobs(nullptr))) return rc;
-        hipLaunchKernelGGL(k_ext_purge, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, P);
-        HIP_TRY(hipGetLastError());
-        n_seeds_ext = h_flt[0];
-    } else {
-        // ---- in rounds (see k_ext_advance): records + extension order first, then `rounds` rounds of one seed per read, one round with everything still ahead
-        if ((rc = meme_buf_reserve(ctx, E.rounds, ExtRounds(nullptr, n, n_seeds).bytes))) return rc;
-        const ExtRounds er(E.rounds.p, n, n_seeds);
-        AdvArgs V;
-        V.P = P; V.state = er.state; V.act = er.act; V.sel = er.sel; V.cntS = d_cntS;
-        V.rmax = A.rmax; V.cntL = A.cntL; V.cntR = A.cntR; V.cntB = A.cntB;
-        A.mode = 1; A.state = V.state;
-        launch_jobs(A, true);
-        A.sel = V.sel; A.act = V.act;
-        auto launch_advance = [&](AdvArgs X) {
-            X.list = nullptr; X.nlist = 0; X.light = 0;
-            if (!split) { hipLaunchKernelGGL((k_ext_advance<64>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, X); return; }
-            X.light = 1;
-            hipLaunchKernelGGL((k_ext_advance<8>), dim3((unsigned)((n + 31) / 32)), dim3(256), 0, ctx->stream, X);
-            if (n_heavy > 0) { X.light = 0; X.list = d_heavy; X.nlist = n_heavy; hipLaunchKernelGGL((k_ext_advance<64>), dim3((unsigned)((n_heavy + 3) / 4)), dim3(256), 0, ctx->stream, X); }
-        };
-        for (i64 t = 0; t <= rounds; ++t) {
-            HIP_TRY(hipMemsetAsync(V.sel, 0, (size_t)n_seeds, ctx->stream));
-            V.mode = t < rounds ? ADV_ONE : ADV_REST;
-            launch_advance(V);
-            A.mode = 2;
-            i64 h_sel = 0;
-            if ((rc = run_jobs(&h_sel))) return rc;
-            n_seeds_ext += h_sel;
-            if (h_sel == 0) break;                      // every read has been walked to its end
-        }
-        V.mode = ADV_FINISH;
-        launch_advance(V);
-        HIP_TRY(hipGetLastError());
+    P.read_off = A.read_off; P.nreads = R.n; P.chain_off = A.chain_off; P.chains = A.chains; P.seed_off = A.seed_off; P.seeds = A.seeds; P.regs = A.regs; P.order = A.order; P.o = *R.eopt;
+    return P;
+}
+// mem_flt_chained_seeds: the read lengths it runs for and their thresholds, evaluated the way the reference's host code does (:579-583: float coefficients, double min_l,
+// libm's log; never with reads below ~760 bases unless -W is given); the windows posed, aligned (seed SW), the seeds below their bar taken out of their chains: the stage goes
+// on with the seeds, offsets and scores the filter made
+int ext_filter(ExtRun& R) {
+    meme_ctx* ctx = R.ctx;
+    ExtWs& E = ctx->ext;
+    const i64 n = R.n, n_seeds = R.n_seeds, max_len = ctx->batch.last_seed_max_len;
+    bool flt = false;
+    std::vector<int> hsp((size_t)max_len + 2, -1);
+    for (i64 l = 2; l <= max_len; ++l) {
+        const int l_query = (int)l;
+        const double min_l = R.copt->min_chain_weight ? 1.1f * R.copt->min_chain_weight : 5.5f * log(l_query);     // MEM_HSP_COEF, MEM_MINSC_COEF (:252-253)
+        if (min_l > 0.05f * l_query) continue;                                                                        // MEM_SEEDSW_COEF (:254)
+        hsp[(size_t)l] = (int)(R.eopt->a * min_l + .499);
+        if (hsp[(size_t)l] < 0) hsp[(size_t)l] = 0;
+        flt = true;
     }
-    const i64 n_flt_dropped = n_seeds - h_flt[0];
-    n_seeds = h_flt[0];
-    HIP_TRY(hipEventRecord(ev[1], ctx->stream));
+    if (!flt || n_seeds <= 0) return MEME_OK;
+    if (n_seeds >= 0x7fffffff) { meme_set_error("meme_extend_last_batch_host: %lld chained seeds in one batch", (long long)n_seeds); return MEME_E_CAPACITY; }
+    int rc;
+    if ((rc = meme_buf_reserve(ctx, E.flt_sc, (size_t)(n_seeds + 1) * 4)) || (rc = meme_buf_reserve(ctx, E.flt_jobs, (size_t)(n_seeds + 1) * sizeof(meme_seedsw_job))) ||
+        (rc = meme_buf_reserve(ctx, E.flt_cnt, CountScan(nullptr, n).bytes)) || (rc = meme_buf_reserve(ctx, E.flt_seeds, (size_t)(n_seeds + 1) * sizeof(meme_chain_seed))) ||
+        (rc = meme_buf_reserve(ctx, E.flt_score, (size_t)(n_seeds + 1) * 4)) || (rc = meme_buf_reserve(ctx, E.flt_hsp, hsp.size() * 4))) return rc;
+    HIP_TRY(hipMemcpyAsync(E.flt_hsp.p, hsp.data(), hsp.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(R.ctr + EXT_CTR_FLT_JOBS, 0, 8, ctx->stream));
+    const CountScan fc(E.flt_cnt.p, n);
+    FltArgs F;
+    memset(&F, 0, sizeof(F));
+    F.read_off = R.A.read_off; F.n = n; F.chain_off = R.A.chain_off; F.chains = ctx->chain.chains.as<meme_chain>(); F.seed_off = R.A.seed_off; F.seeds = R.A.seeds;
+    F.l_pac = R.A.l_pac; F.contig_off = R.A.contig_off; F.contig_len = R.A.contig_len; F.n_contigs = R.n_contigs;
+    F.hsp = E.flt_hsp.as<const int>(); F.a = R.eopt->a; F.sc = E.flt_sc.as<int>(); F.jobs = E.flt_jobs.as<meme_seedsw_job>(); F.n_jobs = R.ctr + EXT_CTR_FLT_JOBS;
+    F.cnt = fc.cnt; F.off2 = fc.off; F.seeds2 = E.flt_seeds.as<meme_chain_seed>(); F.score2 = E.flt_score.as<int>();
+    hipLaunchKernelGGL(k_flt_pose, dim3((unsigned)n), dim3(64), 0, ctx->stream, F);
+    if ((rc = meme_seedsw_launch(ctx, F.jobs, F.n_jobs, n_seeds, F.sc, R.eopt))) return rc;
+    hipLaunchKernelGGL((k_flt_apply<false>), dim3((unsigned)n), dim3(64), 0, ctx->stream, F);
+    if ((rc = meme_scan_exclusive(ctx, fc.cnt, fc.off, n))) return rc;
+    hipLaunchKernelGGL((k_flt_apply<true>), dim3((unsigned)n), dim3(64), 0, ctx->stream, F);
+    HIP_TRY(hipGetLastError());
+    R.A.seed_off = F.off2; R.A.seeds = F.seeds2; R.A.seed_score = F.score2;
+    R.flt_read = false;
+    return MEME_OK;
+}
+// light and heavy reads (tuning "ext_split"): the list of reads with more than EXT_LIGHT chained seeds; everything else runs eight lanes per read
+int ext_split(ExtRun& R) {
+    meme_ctx* ctx = R.ctx;
+    if (!ctx->ext_split) return MEME_OK;
+    int rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->ext.heavy, (size_t)(R.n + 1) * 8))) return rc;
+    unsigned long long* d_nheavy = R.ctr + EXT_CTR_HEAVY;
+    HIP_TRY(hipMemsetAsync(d_nheavy, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(k_ext_split, dim3(grid_blocks(R.n, 256)), dim3(256), 0, ctx->stream, R.A.seed_off, R.n, ctx->ext.heavy.as<i64>(), d_nheavy);
+    unsigned long long h = 0;
+    HIP_TRY(hipMemcpyAsync(&h, d_nheavy, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    R.n_heavy = (i64)h; R.d_heavy = ctx->ext.heavy.as<const i64>();
+    return MEME_OK;
+}
+// A kernel that walks reads (k_ext_jobs, k_ext_advance; k64 / k8: its G = 64 and G = 8 instances) over `ns` reads: one launch of a wavefront per read, or -- tuning
+// "ext_split", and the reads are the whole batch -- eight lanes per light read + a wavefront per read of the heavy list
+template <class Args> void launch_walk(const ExtRun& R, void (*k64)(Args), void (*k8)(Args), Args X, i64 ns, bool whole_batch) {
+    const hipStream_t st = R.ctx->stream;
+    X.list = nullptr; X.nlist = 0; X.light = 0;
+    if (!(R.ctx->ext_split && whole_batch)) { hipLaunchKernelGGL(k64, dim3((unsigned)((ns + 3) / 4)), dim3(256), 0, st, X); return; }
+    X.light = 1;
+    hipLaunchKernelGGL(k8, dim3((unsigned)((ns + 31) / 32)), dim3(256), 0, st, X);
+    if (R.n_heavy > 0) { X.light = 0; X.list = R.d_heavy; X.nlist = R.n_heavy; hipLaunchKernelGGL(k64, dim3((unsigned)((R.n_heavy + 3) / 4)), dim3(256), 0, st, X); }
+}
+void launch_jobs(const ExtRun& R, const ExtArgs& X, bool write) {      // the reads [X.g0, X.g0 + X.ns)
+    void (*const k64)(ExtArgs) = write ? k_ext_jobs<true, 64> : k_ext_jobs<false, 64>;
+    void (*const k8)(ExtArgs) = write ? k_ext_jobs<true, 8> : k_ext_jobs<false, 8>;
+    launch_walk(R, k64, k8, X, X.ns, X.g0 == 0 && X.ns == R.n);
+}
+// the plan of the seeds `A.mode` / `A.sel` name: job and byte counts of every read (in rounds k_ext_advance has counted), their scans and totals.
+// *n_sel: what k_ext_advance selected for this round.  The filter's two totals ride along with the first plan's.
+int ext_plan(ExtRun& R, i64* n_sel) {
+    meme_ctx* ctx = R.ctx;
+    int rc;
+    if (R.A.mode != 2) launch_jobs(R, R.A, false);
+    for (int k = 0; k < 3; ++k) if ((rc = meme_scan_exclusive(ctx, R.ec.cnt[k], R.ec.off[k], R.n))) return rc;      // (all three queued before the first total is fetched)
+    for (int k = 0; k < 3; ++k) HIP_TRY(hipMemcpyAsync(&R.tot[k], R.ec.off[k] + R.n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_sel && (rc = meme_scan_total(ctx, R.ec.cntS, R.ec.offS, R.n, n_sel))) return rc;
+    if (!R.flt_read) {
+        HIP_TRY(hipMemcpyAsync(&R.h_flt[0], R.A.seed_off + R.n, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(&R.h_flt[1], R.ctr + EXT_CTR_FLT_JOBS, 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    R.flt_read = true;
+    return MEME_OK;
+}
+// Slabs: runs of whole reads whose jobs stay within lim[k] per column, at least one read each.  off[k][0..n]: the plan's scans, so reads [g0, g) hold off[k][g] - off[k][g0].
+bool slab_fits(const i64* const off[3], const i64 lim[3], i64 g0, i64 g) { return off[0][g] - off[0][g0] <= lim[0] && off[1][g] - off[1][g0] <= lim[1] && off[2][g] - off[2][g0] <= lim[2]; }
+i64 next_slab(const i64* const off[3], i64 n, i64 g0, const i64 lim[3]) {      // the end of the slab that starts at read g0
+    i64 g1 = g0 + 1;
+    while (g1 < n && slab_fits(off, lim, g0, g1 + 1)) {
+        i64 step = 1;                               // gallop to the slab's end
+        while (g1 + 2 * step < n && slab_fits(off, lim, g0, g1 + 2 * step + 1)) step *= 2;
+        g1 += step;
+    }
+    return g1;
+}
+// one slab: its jobs and their sequences written (SeqPair offsets are 32-bit: they count from the slab's first job and byte), the census, then banded SW left and right with
+// the band doubled once where the reference doubles it, results folded into the records
+int ext_slab(ExtRun& R, const Slab& S) {
+    meme_ctx* ctx = R.ctx;
+    ExtWs& E = ctx->ext;
+    const i64 nL = S.n[EXT_L], nR = S.n[EXT_R], nmax = nL > nR ? nL : nR;
+    int rc;
+    if ((rc = meme_buf_reserve(ctx, E.pairs_l, (size_t)(nL + 1) * sizeof(meme_seqpair))) || (rc = meme_buf_reserve(ctx, E.pairs_r, (size_t)(nR + 1) * sizeof(meme_seqpair))) ||
+        (rc = meme_buf_reserve(ctx, E.retry, ExtRetry(nullptr, nmax).bytes)) || (rc = meme_buf_reserve(ctx, E.seq, (size_t)S.n[EXT_B] + 256))) return rc;
+    const ExtRetry retry(E.retry.p, nmax);
+    ExtArgs X = R.A;
+    X.g0 = S.g0; X.ns = S.g1 - S.g0;
+    // (the scans cover the whole batch: a slab's first read has its own offsets to subtract)
+    X.offL = R.ec.off[EXT_L] + S.g0; X.offR = R.ec.off[EXT_R] + S.g0; X.offB = R.ec.off[EXT_B] + S.g0;
+    X.job0L = S.first[EXT_L]; X.job0R = S.first[EXT_R]; X.byte0 = S.first[EXT_B];
+    X.L = E.pairs_l.as<meme_seqpair>(); X.R = E.pairs_r.as<meme_seqpair>(); X.seq = E.seq.as<uint8_t>();
+    launch_jobs(R, X, true);
+    HIP_TRY(hipGetLastError());
+    unsigned long long *d_census = R.ctr + EXT_CTR_CENSUS, *d_nretry = R.ctr + EXT_CTR_RETRY;
+    if (ctx->ext_census) {
+        if (nL) hipLaunchKernelGGL(k_ext_census, dim3(grid_blocks(nL, 256)), dim3(256), 0, ctx->stream, (const meme_seqpair*)X.L, nL, (const uint8_t*)X.seq, R.eopt->w, d_census);
+        if (nR) hipLaunchKernelGGL(k_ext_census, dim3(grid_blocks(nR, 256)), dim3(256), 0, ctx->stream, (const meme_seqpair*)X.R, nR, (const uint8_t*)X.seq, R.eopt->w, d_census);
+    }
+    for (int dir = 0; dir < 2; ++dir) {
+        meme_seqpair* P = dir == 0 ? X.L : X.R;
+        i64 np = dir == 0 ? nL : nR;
+        if (dir == 1 && np > 0) hipLaunchKernelGGL(k_ext_h0, dim3(grid_blocks(np, 256)), dim3(256), 0, ctx->stream, P, np, (const meme_alnreg*)X.regs);
+        for (int attempt = 0; attempt < EXT_BAND_TRIES && np > 0; ++attempt) {
+            const int w = R.eopt->w << attempt;
+            if ((rc = meme_bsw_launch(ctx, P, X.seq, X.seq, (int)np, w, &R.bsw[dir], (int)ctx->batch.last_seed_max_len))) return rc;
+            HIP_TRY(hipMemsetAsync(d_nretry, 0, 8, ctx->stream));
+            FoldArgs F;
+            F.pairs = P; F.n = np; F.regs = X.regs; F.chains = X.chains; F.seed_off = X.seed_off; F.seeds = X.seeds; F.read_off = X.read_off;
+            F.o = *R.eopt; F.w = w; F.last = attempt + 1 == EXT_BAND_TRIES;
+            F.retry = retry.half[attempt & 1]; F.n_retry = d_nretry;
+            if (dir == 0) hipLaunchKernelGGL((k_ext_fold<true>), dim3(grid_blocks(np, 256)), dim3(256), 0, ctx->stream, F);
+            else hipLaunchKernelGGL((k_ext_fold<false>), dim3(grid_blocks(np, 256)), dim3(256), 0, ctx->stream, F);
+            unsigned long long h_retry = 0;
+            HIP_TRY(hipMemcpyAsync(&h_retry, d_nretry, 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            { float ms = 0.f; if (meme_bsw_last_ms(ctx, &ms) == hipSuccess) R.bsw_ms += ms; }
+            R.n_pairs += np; ++R.n_calls;
+            if (attempt > 0) R.n_retried += np;
+            P = F.retry;
+            np = (i64)h_retry;
+        }
+    }
+    return MEME_OK;
+}
+// the planned jobs, slab after slab.  One slab takes the whole batch unless its jobs exceed the ctx's ext_slab_jobs per side or ext_slab_bytes of sequence;
+// only then do the per-read offsets cross to the host.
+int ext_slabs(ExtRun& R) {
+    meme_ctx* ctx = R.ctx;
+    const i64 n = R.n, lim[3] = {ctx->ext_slab_jobs, ctx->ext_slab_jobs, ctx->ext_slab_bytes};
+    if (R.tot[EXT_L] + R.tot[EXT_R] == 0) return MEME_OK;
+    int rc;
+    if (R.tot[EXT_L] <= lim[EXT_L] && R.tot[EXT_R] <= lim[EXT_R] && R.tot[EXT_B] <= lim[EXT_B]) return ext_slab(R, Slab{0, n, {R.tot[0], R.tot[1], R.tot[2]}, {0, 0, 0}});
+    if (!R.ec.adjacent(n)) { meme_set_error("meme_extend_last_batch_host: the offset columns of ExtCounts are not adjacent"); return MEME_E_STATE; }
+    R.h_off.resize((size_t)(3 * (n + 1)));
+    HIP_TRY(hipMemcpyAsync(R.h_off.data(), R.ec.off[0], R.h_off.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const i64* const off[3] = {R.h_off.data(), R.h_off.data() + (n + 1), R.h_off.data() + 2 * (n + 1)};
+    for (i64 g0 = 0; g0 < n;) {
+        Slab S;
+        S.g0 = g0; S.g1 = next_slab(off, n, g0, lim);
+        for (int k = 0; k < 3; ++k) { S.n[k] = off[k][S.g1] - off[k][g0]; S.first[k] = off[k][g0]; }
+        if (S.n[EXT_B] >= ((i64)1 << 31)) { meme_set_error("a read's extension jobs need more than 2 GiB of sequence"); return MEME_E_CAPACITY; }
+        if ((rc = ext_slab(R, S))) return rc;
+        g0 = S.g1;
+    }
+    return MEME_OK;
+}
+// the reference's batch: every chained seed extended, then the purge
+int ext_batch(ExtRun& R) {
+    int rc;
+    R.A.mode = 0;
+    if ((rc = ext_plan(R, nullptr)) || (rc = ext_slabs(R))) return rc;
+    hipLaunchKernelGGL(k_ext_purge, dim3((unsigned)((R.n + 3) / 4)), dim3(256), 0, R.ctx->stream, purge_args(R));
+    HIP_TRY(hipGetLastError());
+    R.n_seeds_ext = R.h_flt[0];
+    return MEME_OK;
+}
+// in rounds (see k_ext_advance): records + extension order first, then `rounds` rounds of one seed per read, one round with everything still ahead
+int ext_rounds(ExtRun& R, i64 rounds) {
+    meme_ctx* ctx = R.ctx;
+    ExtArgs& A = R.A;
+    int rc;
+    if ((rc = meme_buf_reserve(ctx, ctx->ext.rounds, ExtRounds(nullptr, R.n, R.n_seeds).bytes))) return rc;
+    const ExtRounds er(ctx->ext.rounds.p, R.n, R.n_seeds);
+    AdvArgs V;
+    V.P = purge_args(R); V.state = er.state; V.act = er.act; V.sel = er.sel; V.cntS = R.ec.cntS;
+    V.rmax = A.rmax; V.cntL = A.cntL; V.cntR = A.cntR; V.cntB = A.cntB;
+    A.mode = 1; A.state = V.state;
+    launch_jobs(R, A, true);
+    A.sel = V.sel; A.act = V.act;
+    for (i64 t = 0; t <= rounds; ++t) {
+        HIP_TRY(hipMemsetAsync(V.sel, 0, (size_t)R.n_seeds, ctx->stream));
+        V.mode = t < rounds ? ADV_ONE : ADV_REST;
+        launch_walk(R, k_ext_advance<64>, k_ext_advance<8>, V, R.n, true);
+        A.mode = 2;
+        i64 h_sel = 0;
+        if ((rc = ext_plan(R, &h_sel)) || (rc = ext_slabs(R))) return rc;
+        R.n_seeds_ext += h_sel;
+        if (h_sel == 0) break;                      // every read has been walked to its end
+    }
+    V.mode = ADV_FINISH;
+    launch_walk(R, k_ext_advance<64>, k_ext_advance<8>, V, R.n, true);
+    HIP_TRY(hipGetLastError());
+    return MEME_OK;
+}
+// hand-over: one record per chained seed, or (tuning "ext_live_only") the surviving ones counted, packed and copied; then the result
+int ext_hand_over(ExtRun& R, meme_ext_host_result* out) {
+    meme_ctx* ctx = R.ctx;
+    ExtWs& E = ctx->ext;
+    const i64 n = R.n, n_seeds = R.h_flt[0];        // chained seeds behind the filter
+    const meme_alnreg* regs = R.A.regs;
+    int rc;
     if ((rc = meme_hostbuf_reserve(ctx, E.h_reg_off, (size_t)(n + 1) * 8))) return rc;
-    i64 n_out = n_seeds;                                // records that cross to the host
+    i64 n_out = n_seeds;                            // records that cross to the host
     if (ctx->ext_live_only) {
-        if ((rc = meme_buf_reserve(ctx, E.live_cnt, (size_t)(n + 1) * 16))) return rc;
-        i64* d_lcnt = (i64*)E.live_cnt.p;
-        i64* d_loff = d_lcnt + (n + 1);
-        hipLaunchKernelGGL(k_ext_live_count, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, d_sdoff, (const meme_alnreg*)A.regs, n, d_lcnt);
-        if ((rc = meme_scan_exclusive(ctx, d_lcnt, d_loff, n))) return rc;
-        HIP_TRY(hipMemcpyAsync(E.h_reg_off.p, d_loff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = meme_buf_reserve(ctx, E.live_cnt, CountScan(nullptr, n).bytes))) return rc;
+        const CountScan lc(E.live_cnt.p, n);
+        hipLaunchKernelGGL(k_ext_live_count, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, R.A.seed_off, regs, n, lc.cnt);
+        if ((rc = meme_scan_exclusive(ctx, lc.cnt, lc.off, n))) return rc;
+        HIP_TRY(hipMemcpyAsync(E.h_reg_off.p, lc.off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        n_out = ((const i64*)E.h_reg_off.p)[n];
+        n_out = E.h_reg_off.as<const i64>()[n];
         if ((rc = meme_buf_reserve(ctx, E.live_regs, (size_t)(n_out + 1) * sizeof(meme_alnreg))) || (rc = meme_hostbuf_reserve(ctx, E.h_regs, (size_t)(n_out + 1) * sizeof(meme_alnreg)))) return rc;
-        hipLaunchKernelGGL(k_ext_live_pack, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, d_sdoff, (const meme_alnreg*)A.regs, n, (const i64*)d_loff, (meme_alnreg*)E.live_regs.p);
+        hipLaunchKernelGGL(k_ext_live_pack, dim3(grid_blocks(n, 256)), dim3(256), 0, ctx->stream, R.A.seed_off, regs, n, (const i64*)lc.off, E.live_regs.as<meme_alnreg>());
         HIP_TRY(hipGetLastError());
         if (n_out) HIP_TRY(hipMemcpyAsync(E.h_regs.p, E.live_regs.p, (size_t)n_out * sizeof(meme_alnreg), hipMemcpyDeviceToHost, ctx->stream));
     } else {
         if ((rc = meme_hostbuf_reserve(ctx, E.h_regs, (size_t)(n_seeds + 1) * sizeof(meme_alnreg)))) return rc;
-        HIP_TRY(hipMemcpyAsync(E.h_reg_off.p, d_sdoff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (n_seeds) HIP_TRY(hipMemcpyAsync(E.h_regs.p, A.regs, (size_t)n_seeds * sizeof(meme_alnreg), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(E.h_reg_off.p, R.A.seed_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (n_seeds) HIP_TRY(hipMemcpyAsync(E.h_regs.p, regs, (size_t)n_seeds * sizeof(meme_alnreg), hipMemcpyDeviceToHost, ctx->stream));
     }
     unsigned long long h_census[11] = {0};
-    if (ctx->ext_census) HIP_TRY(hipMemcpyAsync(h_census, d_census, 11 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->ext_census) HIP_TRY(hipMemcpyAsync(h_census, R.ctr + EXT_CTR_CENSUS, 11 * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     out->n_exact_prefix = ctx->ext_census ? (int64_t)h_census[0] : -1;
     out->census_band_cells = ctx->ext_census ? (int64_t)h_census[1] : -1;
     for (int c = 0; c < 9; ++c) out->census_class[c] = ctx->ext_census ? (int64_t)h_census[2 + c] : -1;
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    out->nreads = n; out->reg_off = (const int64_t*)E.h_reg_off.p; out->regs = (const meme_alnreg*)E.h_regs.p; out->total_regs = n_out; out->total_seeds = n_seeds; out->n_ext_seeds = n_seeds_ext;
-    out->total_chains = n_chains; out->n_pairs = n_pairs; out->n_retried = n_retried; out->n_bsw_calls = n_calls;
-    out->n_flt_jobs = h_flt[1]; out->n_flt_dropped = n_flt_dropped;
-    out->n_tier2 = ctx->chain_tier2_reads; out->chain_ms = ctx->tm.chain_kernel_ms; out->ext_ms = ms; out->bsw_ms = bsw_ms;
+    HIP_TRY(hipEventElapsedTime(&ms, E.ev[0], E.ev[1]));
+    out->nreads = n; out->reg_off = E.h_reg_off.as<const int64_t>(); out->regs = E.h_regs.as<const meme_alnreg>(); out->total_regs = n_out; out->total_seeds = n_seeds; out->n_ext_seeds = R.n_seeds_ext;
+    out->total_chains = R.n_chains; out->n_pairs = R.n_pairs; out->n_retried = R.n_retried; out->n_bsw_calls = R.n_calls;
+    out->n_flt_jobs = R.h_flt[1]; out->n_flt_dropped = R.n_seeds - n_seeds;
+    out->n_tier2 = ctx->tm.chain_tier2_reads; out->chain_ms = ctx->tm.chain_kernel_ms; out->ext_ms = ms; out->bsw_ms = R.bsw_ms;
     return MEME_OK;
+}
+
+}  // namespace
+
+extern "C" int meme_extend_last_batch_host(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs, const meme_chain_opt* copt,
+                                           const meme_ext_opt* eopt, meme_ext_host_result* out) {
+    int rc;
+    if ((rc = ext_check(ctx, contigs, n_contigs, copt, eopt, out))) return rc;
+    i64 tot[2];
+    if ((rc = meme_chain_run(ctx, contigs, n_contigs, copt, tot))) return rc;
+    ExtRun R;
+    R.ctx = ctx; R.copt = copt; R.eopt = eopt; R.n_contigs = n_contigs;
+    R.n = ctx->batch.last_seed_reads; R.n_chains = tot[0]; R.n_seeds = tot[1];
+    if ((rc = ext_begin(R)) || (rc = ext_filter(R)) || (rc = ext_workspace(R)) || (rc = ext_split(R))) return rc;
+    const i64 rounds = ctx->ext_live_only ? ctx->ext_rounds : 0;
+    if ((rc = rounds <= 0 ? ext_batch(R) : ext_rounds(R, rounds))) return rc;
+    HIP_TRY(hipEventRecord(ctx->ext.ev[1], ctx->stream));
+    return ext_hand_over(R, out);
 }

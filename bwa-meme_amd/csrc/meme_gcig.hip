@@ -569,129 +569,157 @@ __global__ void __launch_bounds__(256) k_md_pack(const meme_gres* __restrict__ r
     }
 }
 
-// The batch from the jobs in ctx->gcig.jobs (device) to packed results: scratch sizes, the alignment kernel, the packed operations (and MD strings).
-// with_md: NM + MD of every job (meme_gen_cigar_batch_host); host_jobs (may be null) only serves the error message of a bad query span.
-struct GcigRun { i64 tops = 0, tmd = 0; };
+// The batch from the jobs in ctx->gcig.jobs (device) to packed results: scratch sizes and kernel classes (gcig_plan), the alignment kernels (gcig_align), the packed
+// operations and MD strings (gcig_pack).  with_md: NM + MD of every job (meme_gen_cigar_batch_host).
+struct GcigRun {
+    i64 njobs; int qmax, tmax; const meme_bsw_opt* opt; bool with_md; const char* who;
+    size_t lds_base; int zcap, grp_qcap, grp_tcap, grp_z[3];     // LDS of k_gcig_t without its matrix, the matrix bytes it keeps; of k_gcig_grp<16 / 32 / 64>: query, target, matrix bytes
+    i64 tz = 0, tc = 0, tm = 0, ndp = 0, ngrp[3] = {0, 0, 0};    // bytes of matrices, CIGAR words, MD bytes; jobs of k_gcig_t and of the three group classes
+    i64 tops = 0, tmd = 0;                                        // packed operations, packed MD bytes
+};
 constexpr int Z_LDS_WINDOW = 2048;          // ... and when matrices do not fit anyway: the window the walk back reads them through
 constexpr int Z_LDS_CAP = 8192;             // a 250-row matrix of up to 32 band columns: the bands bwa_gen_cigar2 computes for reads with a few small indels
-int gcig_run(meme_ctx* ctx, i64 njobs, int qmax, int tmax, const meme_bsw_opt* opt, bool with_md, const char* who, GcigRun* out) {
+// Several jobs per wavefront for narrow bands (k_gcig_grp; tuning "gcig_groups" = 0: every job a wavefront): lanes, jobs per wavefront, the most matrix bytes a group keeps, the
+// LDS a wavefront's groups may take (24 KB: six wavefronts per CU and more).  Per group: rings for H and E, the query, the target and a matrix of `lanes` columns x the longest target.
+// (bands of 65-128 columns as one chunk, two columns per lane, were measured and removed: profiles/r06_gcig.md)
+constexpr struct { int lanes, per_wave, zmax, lds_max; } GCIG_GRP[3] = {{16, 4, 4096, 24 * 1024}, {32, 2, 8192, 24 * 1024}, {64, 1, 12288, 16 * 1024}};
+size_t grp_lds(const GcigRun& R, int g) { return (size_t)GCIG_GRP[g].per_wave * ((size_t)3 * 2 * GCIG_GRP[g].lanes * 4 + R.grp_qcap + R.grp_tcap + R.grp_z[g]); }
+
+// sizing and classing: LDS per job, the per-job scratch sizes and kernel classes, their scans and totals, the scratch itself
+int gcig_plan(meme_ctx* ctx, GcigRun& R) {
     int rc;
-    const size_t lds_base = (size_t)(3 * (qmax + 2)) * 4 + (size_t)((qmax + 3) & ~3) + (size_t)((tmax + 3) & ~3);
+    const i64 njobs = R.njobs;
+    R.lds_base = (size_t)(3 * (R.qmax + 2)) * 4 + (size_t)((R.qmax + 3) & ~3) + (size_t)((R.tmax + 3) & ~3);
     // The LDS kept per job for its backtrack matrix or window (tuning "gcig_zcap" overrides; 0: none).  Measured on two read classes only
     // (profiles/r05_gcig.md, 400 k calls each): where a typical matrix -- the rows of the longest target x the ~33 band columns bwa_gen_cigar2 computes
     // for a read with a few small indels -- fits, keeping it whole pays (150 bp: 7.1 ms against 9.8 without); where it does not, only the window is used
     // and a small one leaves room for more wavefronts (250 bp: 47.5 ms with 2 KB against 52.9 with 8 KB).
-    const int zauto = (size_t)tmax * 33 <= (size_t)Z_LDS_CAP ? Z_LDS_CAP : Z_LDS_WINDOW;
+    const int zauto = (size_t)R.tmax * 33 <= (size_t)Z_LDS_CAP ? Z_LDS_CAP : Z_LDS_WINDOW;
     const int zwant = ctx->gcig_zcap >= 0 ? (int)ctx->gcig_zcap : zauto;
-    const int zcap = lds_base + (size_t)zwant <= 32 * 1024 ? zwant : 0;          // (long reads: their rows fill the LDS, the matrix stays in global memory)
+    R.zcap = R.lds_base + (size_t)zwant <= 32 * 1024 ? zwant : 0;          // (long reads: their rows fill the LDS, the matrix stays in global memory)
     GcigWs& G = ctx->gcig;
     if ((rc = meme_buf_reserve(ctx, G.cols, GcigCols(nullptr, njobs).bytes)) || (rc = meme_buf_reserve(ctx, G.res, (size_t)njobs * sizeof(meme_gres)))) return rc;
     const GcigCols gc(G.cols.p, njobs);
-    // Several jobs per wavefront for narrow bands (k_gcig_grp; tuning "gcig_groups" = 0: every job a wavefront): per group rings for H and E, the query, the
-    // target and a matrix of 16 (32) columns x the longest target, as long as a wavefront's groups stay within 24 KB (six wavefronts per CU and more)
-    const int grp_qcap = (qmax + 3) & ~3, grp_tcap = (tmax + 3) & ~3;
-    auto grp_lds = [&](int g, int z) { return (size_t)(64 / g) * ((size_t)3 * 2 * g * 4 + grp_qcap + grp_tcap + z); };
-    int z16 = ctx->gcig_groups ? ((16 * tmax + 3) & ~3) : 0, z32 = ctx->gcig_groups ? ((32 * tmax + 3) & ~3) : 0;
-    int z64 = ctx->gcig_groups ? ((64 * tmax + 3) & ~3) : 0;
-    if (z16 > 4096) z16 = 4096;
-    if (z32 > 8192) z32 = 8192;
-    if (z64 > 12288) z64 = 12288;
-    if (grp_lds(16, z16) > 24 * 1024) z16 = 0;
-    if (grp_lds(32, z32) > 24 * 1024) z32 = 0;
-    if (grp_lds(64, z64) > 16 * 1024) z64 = 0;
-    // (bands of 65-128 columns as one chunk, two columns per lane, were measured and removed: profiles/r06_gcig.md)
+    R.grp_qcap = (R.qmax + 3) & ~3; R.grp_tcap = (R.tmax + 3) & ~3;
+    for (int g = 0; g < 3; ++g) {
+        int& z = R.grp_z[g];
+        z = ctx->gcig_groups ? ((GCIG_GRP[g].lanes * R.tmax + 3) & ~3) : 0;
+        if (z > GCIG_GRP[g].zmax) z = GCIG_GRP[g].zmax;
+        if (grp_lds(R, g) > (size_t)GCIG_GRP[g].lds_max) z = 0;
+    }
     // the gap-free shortcut on the packed reads the seeding call left on the ctx (reads of at most 500 bases)
     const bool fast = ctx->batch.packed.p != nullptr && ctx->batch.last_seed_max_len > 0;
-    const int pW = (int)((ctx->batch.last_seed_max_len + 31) / 32) + 2, pMW = (int)((ctx->batch.last_seed_max_len + 63) / 64);      // PackGeom of that batch (meme_seed.hip)
+    const meme_gjob* jobs = G.jobs.as<const meme_gjob>();
+    const i64* read_off = ctx->batch.read_off.as<const i64>();
     HIP_TRY(hipMemsetAsync(gc.bad, 0xff, 8, ctx->stream));
-    hipLaunchKernelGGL(k_gcig_check, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gjob*)G.jobs.p, (i64)njobs, (const i64*)ctx->batch.read_off.p, gc.bad);
-    hipLaunchKernelGGL(k_gcig_sizes, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gjob*)G.jobs.p, (i64)njobs, (const i64*)ctx->batch.read_off.p, fast, zcap, z16, z32, z64, gc.zsz, gc.csz,
-                       with_md ? gc.msz : (i64*)nullptr, gc.isdp, gc.is16, gc.is32, gc.is64);
+    hipLaunchKernelGGL(k_gcig_check, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, jobs, njobs, read_off, gc.bad);
+    hipLaunchKernelGGL(k_gcig_sizes, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, jobs, njobs, read_off, fast, R.zcap, R.grp_z[0], R.grp_z[1], R.grp_z[2], gc.zsz, gc.csz,
+                       R.with_md ? gc.msz : (i64*)nullptr, gc.isdp, gc.is16, gc.is32, gc.is64);
     if ((rc = meme_scan_exclusive(ctx, gc.zsz, gc.zoff, njobs)) || (rc = meme_scan_exclusive(ctx, gc.csz, gc.coff, njobs)) || (rc = meme_scan_exclusive(ctx, gc.isdp, gc.dpoff, njobs)) ||
         (rc = meme_scan_exclusive(ctx, gc.is16, gc.o16, njobs)) || (rc = meme_scan_exclusive(ctx, gc.is32, gc.o32, njobs)) || (rc = meme_scan_exclusive(ctx, gc.is64, gc.o64, njobs))) return rc;
     hipLaunchKernelGGL(k_gcig_dplist, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const i64*)gc.isdp, (const i64*)gc.dpoff, (const i64*)gc.is16, (const i64*)gc.o16,
-                       (const i64*)gc.is32, (const i64*)gc.o32, (const i64*)gc.is64, (const i64*)gc.o64, (i64)njobs, gc.dplist);
-    if (with_md && (rc = meme_scan_exclusive(ctx, gc.msz, gc.moff, njobs))) return rc;
-    i64 tz = 0, tc = 0, tm = 0, ndp = 0, n16 = 0, n32 = 0, n64 = 0;
-    HIP_TRY(hipMemcpyAsync(&n64, gc.o64 + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&ndp, gc.dpoff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&n16, gc.o16 + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&n32, gc.o32 + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&tz, gc.zoff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&tc, gc.coff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (with_md) HIP_TRY(hipMemcpyAsync(&tm, gc.moff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
+                       (const i64*)gc.is32, (const i64*)gc.o32, (const i64*)gc.is64, (const i64*)gc.o64, njobs, gc.dplist);
+    if (R.with_md && (rc = meme_scan_exclusive(ctx, gc.msz, gc.moff, njobs))) return rc;
+    // (every scan is queued before the first total is fetched: a fetch makes the host wait for the stream)
     i64 bad = -1;
-    HIP_TRY(hipMemcpyAsync(&bad, gc.bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+    const struct { i64* h; const i64* d; } back[8] = {{&R.ngrp[2], gc.o64 + njobs}, {&R.ndp, gc.dpoff + njobs}, {&R.ngrp[0], gc.o16 + njobs}, {&R.ngrp[1], gc.o32 + njobs},
+                                                      {&R.tz, gc.zoff + njobs}, {&R.tc, gc.coff + njobs}, {R.with_md ? &R.tm : nullptr, gc.moff + njobs}, {&bad, gc.bad}};
+    for (const auto& b : back) if (b.h) HIP_TRY(hipMemcpyAsync(b.h, b.d, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (bad >= 0) {
-        meme_set_error("%s: job %lld names a query span beyond the end of read it refers to", who, (long long)bad);
+        meme_set_error("%s: job %lld names a query span beyond the end of read it refers to", R.who, (long long)bad);
         return MEME_E_ARG;
     }
-    {
-        size_t free_b = 0, total_b = 0;
-        const size_t need = (size_t)tz + (size_t)tc * 4 + (size_t)tm;
-        const size_t have = G.z.cap + G.cig.cap + G.md.cap;
-        if (need > have && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b / 2 + have) {
-            meme_set_error("%s: %lld alignments need %.1f GB of backtrack matrices, more than half of the free HBM: submit fewer at a time", who, (long long)njobs, need / 1e9);
-            return MEME_E_CAPACITY;
-        }
+    const size_t need = (size_t)R.tz + (size_t)R.tc * 4 + (size_t)R.tm;
+    size_t free_b = 0;
+    if (!meme_fits_free_hbm(need, G.z.cap + G.cig.cap + G.md.cap, &free_b)) {
+        meme_set_error("%s: %lld alignments need %.1f GB of backtrack matrices, more than half of the free HBM: submit fewer at a time", R.who, (long long)njobs, need / 1e9);
+        return MEME_E_CAPACITY;
     }
-    if ((rc = meme_buf_reserve(ctx, G.z, (size_t)tz + 64)) || (rc = meme_buf_reserve(ctx, G.cig, (size_t)(tc + 1) * 4))) return rc;
-    if (with_md && ((rc = meme_buf_reserve(ctx, G.md, (size_t)tm + 64)) || (rc = meme_buf_reserve(ctx, G.nm, (size_t)njobs * 8 + 64)))) return rc;
+    if ((rc = meme_buf_reserve(ctx, G.z, (size_t)R.tz + 64)) || (rc = meme_buf_reserve(ctx, G.cig, (size_t)(R.tc + 1) * 4))) return rc;
+    if (R.with_md && ((rc = meme_buf_reserve(ctx, G.md, (size_t)R.tm + 64)) || (rc = meme_buf_reserve(ctx, G.nm, (size_t)njobs * 8 + 64)))) return rc;
+    return MEME_OK;
+}
+
+// the alignment launches: the gap-free shortcut over everything no class took, the three group classes off their table, a wavefront per job for the rest of the DP list
+int gcig_align(meme_ctx* ctx, const GcigRun& R) {
+    GcigWs& G = ctx->gcig;
+    const GcigCols gc(G.cols.p, R.njobs);
+    const i64 njobs = R.njobs, n_grp = R.ngrp[0] + R.ngrp[1] + R.ngrp[2];
+    const int pW = (int)((ctx->batch.last_seed_max_len + 31) / 32) + 2, pMW = (int)((ctx->batch.last_seed_max_len + 63) / 64);      // PackGeom of the seeded batch (meme_seed.hip)
     GcigArgs A;
-    A.jobs = (const meme_gjob*)G.jobs.p; A.njobs = njobs; A.reads = (const uint8_t*)ctx->batch.reads.p; A.read_off = (const i64*)ctx->batch.read_off.p; A.pac = ctx->idx.pac;
-    A.o = *opt; A.zoff = gc.zoff; A.z = (uint8_t*)G.z.p; A.coff = gc.coff; A.cig = (uint32_t*)G.cig.p; A.res = (meme_gres*)G.res.p;
-    A.mdoff = gc.moff; A.md = with_md ? (char*)G.md.p : nullptr;
-    A.nm = with_md ? (int32_t*)G.nm.p : nullptr; A.mdlen = with_md ? (int32_t*)G.nm.p + njobs : nullptr;
-    A.zcap = zcap; A.dp_list = nullptr; A.packed = (const u64*)ctx->batch.packed.p; A.pW = pW; A.pMW = pMW; A.pstride = 2 * pW + 2 * pMW + 1;
-    A.list_first = 0; A.grp_qcap = grp_qcap; A.grp_tcap = grp_tcap; A.grp_z = 0;
-    if (ndp + n16 + n32 + n64 < njobs) hipLaunchKernelGGL(k_gcig_nogap, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, A);
-    if (n16 > 0) {
-        GcigArgs D = A;
-        D.dp_list = gc.dplist; D.njobs = n16; D.list_first = 0; D.grp_z = z16;
-        hipLaunchKernelGGL(k_gcig_grp<16>, dim3((unsigned)((n16 + 3) / 4)), dim3(64), grp_lds(16, z16), ctx->stream, D);
+    A.jobs = G.jobs.as<const meme_gjob>(); A.njobs = njobs; A.reads = ctx->batch.reads.as<const uint8_t>(); A.read_off = ctx->batch.read_off.as<const i64>(); A.pac = ctx->idx.pac;
+    A.o = *R.opt; A.zoff = gc.zoff; A.z = G.z.as<uint8_t>(); A.coff = gc.coff; A.cig = G.cig.as<uint32_t>(); A.res = G.res.as<meme_gres>();
+    A.mdoff = gc.moff; A.md = R.with_md ? G.md.as<char>() : nullptr;
+    A.nm = R.with_md ? G.nm.as<int32_t>() : nullptr; A.mdlen = R.with_md ? G.nm.as<int32_t>() + njobs : nullptr;
+    A.zcap = R.zcap; A.dp_list = nullptr; A.packed = ctx->batch.packed.as<const u64>(); A.pW = pW; A.pMW = pMW; A.pstride = 2 * pW + 2 * pMW + 1;
+    A.list_first = 0; A.grp_qcap = R.grp_qcap; A.grp_tcap = R.grp_tcap; A.grp_z = 0;
+    if (R.ndp + n_grp < njobs) hipLaunchKernelGGL(k_gcig_nogap, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, A);
+    GcigArgs D = A;
+    D.dp_list = gc.dplist;
+    for (int g = 0; g < 3; ++g) {              // the DP list holds the classes one after the other
+        D.njobs = R.ngrp[g]; D.grp_z = R.grp_z[g];
+        const dim3 grid((unsigned)((D.njobs + GCIG_GRP[g].per_wave - 1) / GCIG_GRP[g].per_wave));
+        if (D.njobs > 0 && g == 0) hipLaunchKernelGGL(k_gcig_grp<16>, grid, dim3(64), grp_lds(R, g), ctx->stream, D);
+        if (D.njobs > 0 && g == 1) hipLaunchKernelGGL(k_gcig_grp<32>, grid, dim3(64), grp_lds(R, g), ctx->stream, D);
+        if (D.njobs > 0 && g == 2) hipLaunchKernelGGL(k_gcig_grp<64>, grid, dim3(64), grp_lds(R, g), ctx->stream, D);
+        D.list_first += D.njobs;
     }
-    if (n32 > 0) {
-        GcigArgs D = A;
-        D.dp_list = gc.dplist; D.njobs = n32; D.list_first = n16; D.grp_z = z32;
-        hipLaunchKernelGGL(k_gcig_grp<32>, dim3((unsigned)((n32 + 1) / 2)), dim3(64), grp_lds(32, z32), ctx->stream, D);
-    }
-    if (n64 > 0) {
-        GcigArgs D = A;
-        D.dp_list = gc.dplist; D.njobs = n64; D.list_first = n16 + n32; D.grp_z = z64;
-        hipLaunchKernelGGL(k_gcig_grp<64>, dim3((unsigned)n64), dim3(64), grp_lds(64, z64), ctx->stream, D);
-    }
-    ctx->tm.gcig_class_jobs[0] = n16; ctx->tm.gcig_class_jobs[1] = n32; ctx->tm.gcig_class_jobs[2] = ndp; ctx->tm.gcig_class_jobs[3] = njobs - ndp - n16 - n32 - n64; ctx->tm.gcig_class_jobs[4] = n64;
-    ctx->tm.gcig_class_jobs[5] = 0;
-    if (ndp > 0) {
-        GcigArgs D = A;
-        D.dp_list = gc.dplist; D.njobs = ndp; D.list_first = n16 + n32 + n64;
-        const size_t lds = lds_base + (size_t)zcap;
+    i64* cj = ctx->tm.gcig_class_jobs;
+    cj[0] = R.ngrp[0]; cj[1] = R.ngrp[1]; cj[2] = R.ndp; cj[3] = njobs - R.ndp - n_grp; cj[4] = R.ngrp[2]; cj[5] = 0;
+    if (R.ndp > 0) {
+        D.njobs = R.ndp; D.grp_z = 0;
+        const size_t lds = R.lds_base + (size_t)R.zcap;
         if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_gcig_t, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_gcig_t, dim3((unsigned)ndp), dim3(64), lds, ctx->stream, D);
+        hipLaunchKernelGGL(k_gcig_t, dim3((unsigned)R.ndp), dim3(64), lds, ctx->stream, D);
     }
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_gcig_ncig, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gres*)G.res.p, (i64)njobs, gc.ncig);
+    return MEME_OK;
+}
+
+// operations (and MD strings) of the jobs packed in job order
+int gcig_pack(meme_ctx* ctx, GcigRun& R) {
+    GcigWs& G = ctx->gcig;
+    const GcigCols gc(G.cols.p, R.njobs);
+    const i64 njobs = R.njobs;
+    const int32_t* nm = G.nm.as<const int32_t>();       // nm, then mdlen (with_md)
+    const dim3 grid(grid_blocks(njobs, 256)), block(256);
+    int rc;
+    hipLaunchKernelGGL(k_gcig_ncig, grid, block, 0, ctx->stream, G.res.as<const meme_gres>(), njobs, gc.ncig);
     if ((rc = meme_scan_exclusive(ctx, gc.ncig, gc.ooff, njobs))) return rc;
-    if (with_md) {
-        hipLaunchKernelGGL(k_md_sizes, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const int32_t*)A.mdlen, (i64)njobs, gc.psz);
+    if (R.with_md) {
+        hipLaunchKernelGGL(k_md_sizes, grid, block, 0, ctx->stream, nm + njobs, njobs, gc.psz);
         if ((rc = meme_scan_exclusive(ctx, gc.psz, gc.poff, njobs))) return rc;
     }
-    i64 tops = 0, tmd = 0;
-    HIP_TRY(hipMemcpyAsync(&tops, gc.ooff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (with_md) HIP_TRY(hipMemcpyAsync(&tmd, gc.poff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&R.tops, gc.ooff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (R.with_md) HIP_TRY(hipMemcpyAsync(&R.tmd, gc.poff + njobs, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if ((rc = meme_buf_reserve(ctx, G.ops, (size_t)(tops + 1) * 4))) return rc;
-    hipLaunchKernelGGL(k_gcig_pack, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gres*)G.res.p, (const i64*)gc.coff, (const uint32_t*)G.cig.p,
-                       (const i64*)gc.ooff, (i64)njobs, (uint32_t*)G.ops.p);
-    hipLaunchKernelGGL(k_gcig_fix, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (meme_gres*)G.res.p, (const i64*)gc.ooff, (i64)njobs);
-    if (with_md) {
-        if ((rc = meme_buf_reserve(ctx, G.md_packed, (size_t)tmd + 64)) || (rc = meme_buf_reserve(ctx, G.cres, (size_t)njobs * sizeof(meme_cres)))) return rc;
-        hipLaunchKernelGGL(k_md_pack, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_gres*)G.res.p, (const int32_t*)A.nm, (const int32_t*)A.mdlen,
-                           (const i64*)gc.moff, (const char*)G.md.p, (const i64*)gc.poff, (i64)njobs, (char*)G.md_packed.p, (meme_cres*)G.cres.p);
+    if ((rc = meme_buf_reserve(ctx, G.ops, (size_t)(R.tops + 1) * 4))) return rc;
+    hipLaunchKernelGGL(k_gcig_pack, grid, block, 0, ctx->stream, G.res.as<const meme_gres>(), (const i64*)gc.coff, G.cig.as<const uint32_t>(), (const i64*)gc.ooff, njobs, G.ops.as<uint32_t>());
+    hipLaunchKernelGGL(k_gcig_fix, grid, block, 0, ctx->stream, G.res.as<meme_gres>(), (const i64*)gc.ooff, njobs);
+    if (R.with_md) {
+        if ((rc = meme_buf_reserve(ctx, G.md_packed, (size_t)R.tmd + 64)) || (rc = meme_buf_reserve(ctx, G.cres, (size_t)njobs * sizeof(meme_cres)))) return rc;
+        hipLaunchKernelGGL(k_md_pack, grid, block, 0, ctx->stream, G.res.as<const meme_gres>(), nm, nm + njobs, (const i64*)gc.moff, G.md.as<const char>(), (const i64*)gc.poff, njobs,
+                           G.md_packed.as<char>(), G.cres.as<meme_cres>());
     }
     HIP_TRY(hipGetLastError());
-    out->tops = tops; out->tmd = tmd;
+    return MEME_OK;
+}
+
+// what both entry points do with the staged jobs: the three parts between the stage's events, then the per-job records (`rec` bytes each, in `d_res`), the packed
+// operations and the packed MD strings to the host; *ms: the stage's time
+int gcig_run(meme_ctx* ctx, GcigRun& R, const DevBuf& d_res, size_t rec, float* ms) {
+    GcigWs& G = ctx->gcig;
+    int rc;
+    if ((rc = gcig_plan(ctx, R)) || (rc = gcig_align(ctx, R)) || (rc = gcig_pack(ctx, R))) return rc;
+    HIP_TRY(hipEventRecord(G.ev[1], ctx->stream));
+    if ((rc = meme_hostbuf_reserve(ctx, G.h_res, (size_t)R.njobs * rec)) || (rc = meme_hostbuf_reserve(ctx, G.h_ops, (size_t)(R.tops + 1) * 4)) ||
+        (R.with_md && (rc = meme_hostbuf_reserve(ctx, G.h_md, (size_t)R.tmd + 64)))) return rc;
+    HIP_TRY(hipMemcpyAsync(G.h_res.p, d_res.p, (size_t)R.njobs * rec, hipMemcpyDeviceToHost, ctx->stream));
+    if (R.tops) HIP_TRY(hipMemcpyAsync(G.h_ops.p, G.ops.p, (size_t)R.tops * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (R.tmd) HIP_TRY(hipMemcpyAsync(G.h_md.p, G.md_packed.p, (size_t)R.tmd, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipEventElapsedTime(ms, G.ev[0], G.ev[1]));
     return MEME_OK;
 }
 
@@ -703,7 +731,7 @@ int gcig_preamble(meme_ctx* ctx, const void* jobs, int64_t njobs, const meme_bsw
     if (nreads <= 0 || !ctx->batch.reads.p || !ctx->batch.read_off.p || !ctx->idx.pac || !ctx->batch.reads_resident) { meme_set_error("%s: no seeded batch on this ctx (the jobs name its reads)", who); return MEME_E_STATE; }
     if (opt->e_del < 1 || opt->e_ins < 1) { meme_set_error("%s: gap extension penalties must be positive", who); return MEME_E_ARG; }
     if (ctx->max_batch > 0 && njobs > ctx->max_batch) { meme_set_error("%s: %lld jobs exceed the ctx's max_batch of %lld", who, (long long)njobs, (long long)ctx->max_batch); return MEME_E_CAPACITY; }
-    for (int i = 0; i < 2; ++i) if (!ctx->gcig.ev[i]) HIP_TRY(hipEventCreate(&ctx->gcig.ev[i]));
+    HIP_TRY(ctx->gcig.ev.ensure());
     return MEME_OK;
 }
 
@@ -733,16 +761,10 @@ extern "C" int meme_global_batch_host(meme_ctx* ctx, const meme_gjob* jobs, int6
     if ((rc = meme_buf_reserve(ctx, G.jobs, (size_t)njobs * sizeof(meme_gjob)))) return rc;
     HIP_TRY(hipMemcpyAsync(G.jobs.p, jobs, (size_t)njobs * sizeof(meme_gjob), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->gcig.ev[0], ctx->stream));
-    GcigRun R;
-    if ((rc = gcig_run(ctx, njobs, qmax, tmax, opt, false, who, &R))) return rc;
-    HIP_TRY(hipEventRecord(ctx->gcig.ev[1], ctx->stream));
-    if ((rc = meme_hostbuf_reserve(ctx, G.h_res, (size_t)njobs * sizeof(meme_gres))) || (rc = meme_hostbuf_reserve(ctx, G.h_ops, (size_t)(R.tops + 1) * 4))) return rc;
-    HIP_TRY(hipMemcpyAsync(G.h_res.p, G.res.p, (size_t)njobs * sizeof(meme_gres), hipMemcpyDeviceToHost, ctx->stream));
-    if (R.tops) HIP_TRY(hipMemcpyAsync(G.h_ops.p, G.ops.p, (size_t)R.tops * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    GcigRun R{njobs, qmax, tmax, opt, false, who};
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->gcig.ev[0], ctx->gcig.ev[1]));
-    out->njobs = njobs; out->res = (const meme_gres*)G.h_res.p; out->cigars = (const uint32_t*)G.h_ops.p; out->total_ops = R.tops; out->kernel_ms = ms;
+    if ((rc = gcig_run(ctx, R, G.res, sizeof(meme_gres), &ms))) return rc;
+    out->njobs = njobs; out->res = G.h_res.as<const meme_gres>(); out->cigars = G.h_ops.as<const uint32_t>(); out->total_ops = R.tops; out->kernel_ms = ms;
     return MEME_OK;
 }
 
@@ -770,18 +792,10 @@ extern "C" int meme_gen_cigar_batch_host(meme_ctx* ctx, const meme_cjob* jobs, i
     HIP_TRY(hipMemcpyAsync(G.cjobs.p, jobs, (size_t)njobs * sizeof(meme_cjob), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->gcig.ev[0], ctx->stream));
     hipLaunchKernelGGL(k_cjob_prep, dim3(grid_blocks(njobs, 256)), dim3(256), 0, ctx->stream, (const meme_cjob*)G.cjobs.p, (i64)njobs, l_pac, *opt, (meme_gjob*)G.jobs.p);
-    GcigRun R;
-    if ((rc = gcig_run(ctx, njobs, qmax, tmax, opt, true, who, &R))) return rc;
-    HIP_TRY(hipEventRecord(ctx->gcig.ev[1], ctx->stream));
-    if ((rc = meme_hostbuf_reserve(ctx, G.h_res, (size_t)njobs * sizeof(meme_cres))) || (rc = meme_hostbuf_reserve(ctx, G.h_ops, (size_t)(R.tops + 1) * 4)) ||
-        (rc = meme_hostbuf_reserve(ctx, G.h_md, (size_t)R.tmd + 64))) return rc;
-    HIP_TRY(hipMemcpyAsync(G.h_res.p, G.cres.p, (size_t)njobs * sizeof(meme_cres), hipMemcpyDeviceToHost, ctx->stream));
-    if (R.tops) HIP_TRY(hipMemcpyAsync(G.h_ops.p, G.ops.p, (size_t)R.tops * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (R.tmd) HIP_TRY(hipMemcpyAsync(G.h_md.p, G.md_packed.p, (size_t)R.tmd, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    GcigRun R{njobs, qmax, tmax, opt, true, who};
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->gcig.ev[0], ctx->gcig.ev[1]));
-    out->njobs = njobs; out->res = (const meme_cres*)G.h_res.p; out->cigars = (const uint32_t*)G.h_ops.p; out->total_ops = R.tops; out->md = (const char*)G.h_md.p; out->md_bytes = R.tmd;
+    if ((rc = gcig_run(ctx, R, G.cres, sizeof(meme_cres), &ms))) return rc;
+    out->njobs = njobs; out->res = G.h_res.as<const meme_cres>(); out->cigars = G.h_ops.as<const uint32_t>(); out->total_ops = R.tops; out->md = G.h_md.as<const char>(); out->md_bytes = R.tmd;
     out->kernel_ms = ms;
     return MEME_OK;
 }

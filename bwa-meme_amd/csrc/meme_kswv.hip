@@ -359,7 +359,7 @@ int meme_kswv_run(meme_ctx* ctx, const meme_kswv_job* jobs, int64_t njobs, const
         (rc = meme_buf_reserve(ctx, K.res, (size_t)n * sizeof(meme_kswr))) || (rc = meme_buf_reserve(ctx, K.rowmax, (size_t)rows_total * 128 + 256)) ||
         (rc = meme_buf_reserve(ctx, K.rm_off, rm_off.size() * 8 + 8))) return rc;
     Events<2>& ev = K.ev;
-    for (int i = 0; i < 2; ++i) if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
+    HIP_TRY(ev.ensure());
     if (!staged) HIP_TRY(hipMemcpyAsync(K.jobs.p, jobs, (size_t)n * sizeof(meme_kswv_job), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(K.order.p, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     if (!staged) {                                     // (staged: the caller's kernels have written the jobs and both sequence buffers where they are read)

@@ -180,7 +180,7 @@ extern "C" int meme_matesw_batch_host(meme_ctx* ctx, meme_ctx* reads_of, const m
     if ((rc = meme_buf_reserve(ctx, M.regs, (size_t)(nrec + 1) * sizeof(meme_mate_reg))) || (rc = meme_buf_reserve(ctx, M.reg_off, (size_t)(n + 1) * 8)) ||
         (rc = meme_buf_reserve(ctx, M.counts, MateCounts(nullptr, n).bytes)) || (rc = meme_buf_reserve(ctx, M.batch_off, (size_t)(nb + 1) * 16))) return rc;
     Events<2>& ev = ctx->kswv.ev;
-    for (int i = 0; i < 2; ++i) if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
+    HIP_TRY(ev.ensure());
     if (nrec) HIP_TRY(hipMemcpyAsync(M.regs.p, regs, (size_t)nrec * sizeof(meme_mate_reg), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(M.reg_off.p, reg_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     MateArgs A;

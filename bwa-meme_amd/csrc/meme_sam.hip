@@ -284,7 +284,7 @@ extern "C" int meme_sam_format_batch_host(meme_ctx* ctx, const meme_sam_rec* rec
     const size_t ctab = (size_t)contig_name_off[n_contigs] + (size_t)(n_contigs + 1) * 4 + (size_t)rg_len + 64;
     if ((rc = meme_buf_reserve(ctx, S.recs, (size_t)nrecs * sizeof(meme_sam_rec))) || (rc = meme_buf_reserve(ctx, S.blob, (size_t)blob_bytes + 128)) ||
         (rc = meme_buf_reserve(ctx, S.cols, SamCols(nullptr, nrecs).bytes)) || (rc = meme_buf_reserve(ctx, S.contigs, ctab))) return rc;
-    for (int i = 0; i < 2; ++i) if (!S.ev[i]) HIP_TRY(hipEventCreate(&S.ev[i]));
+    HIP_TRY(S.ev.ensure());
     HIP_TRY(hipMemcpyAsync(S.recs.p, recs, (size_t)nrecs * sizeof(meme_sam_rec), hipMemcpyHostToDevice, ctx->stream));
     if (blob_bytes) HIP_TRY(hipMemcpyAsync(S.blob.p, blob, (size_t)blob_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemsetAsync((char*)S.blob.p + blob_bytes, 0, 128, ctx->stream));            // (the strlen loops read 64 bytes at a time)
@@ -299,9 +299,8 @@ extern "C" int meme_sam_format_batch_host(meme_ctx* ctx, const meme_sam_rec* rec
     HIP_TRY(hipMemsetAsync(sc.bad, 0xff, 8, ctx->stream));
     hipLaunchKernelGGL(k_sam_bounds, dim3(grid_blocks(nrecs, 256)), dim3(256), 0, ctx->stream, (const meme_sam_rec*)S.recs.p, (i64)nrecs, (const i64*)ctx->batch.read_off.p, (const i64*)S.name_off.p,
                        (const uint8_t*)S.blob.p, (i64)blob_bytes, max_contig, rg_len, sc.bound, sc.bad);
-    if ((rc = meme_scan_exclusive(ctx, sc.bound, sc.soff, nrecs))) return rc;
     i64 total_scratch = 0, bad = -1;
-    HIP_TRY(hipMemcpyAsync(&total_scratch, sc.soff + nrecs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = meme_scan_total(ctx, sc.bound, sc.soff, nrecs, &total_scratch))) return rc;
     HIP_TRY(hipMemcpyAsync(&bad, sc.bad, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (bad >= 0) { meme_set_error("%s: record %lld names a string that does not end inside the blob", who, (long long)bad); return MEME_E_ARG; }
@@ -313,9 +312,8 @@ extern "C" int meme_sam_format_batch_host(meme_ctx* ctx, const meme_sam_rec* rec
     A.rg = d_tab + off_bytes + contig_name_off[n_contigs]; A.rg_len = rg_len;
     A.soff = sc.soff; A.scratch = (char*)S.scratch.p; A.len = sc.len; A.over = sc.bad;            // (sc.bad is all-ones again: the bounds kernel found nothing)
     hipLaunchKernelGGL(k_sam_format, dim3((unsigned)((nrecs + 3) / 4)), dim3(256), 0, ctx->stream, A);
-    if ((rc = meme_scan_exclusive(ctx, sc.len, sc.toff, nrecs))) return rc;
     i64 total = 0, over = -1;
-    HIP_TRY(hipMemcpyAsync(&total, sc.toff + nrecs, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = meme_scan_total(ctx, sc.len, sc.toff, nrecs, &total))) return rc;
     HIP_TRY(hipMemcpyAsync(&over, sc.bad, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (over >= 0) { meme_set_error("%s: the text of record %lld is longer than the slot k_sam_bounds gave it (formatter and bound disagree)", who, (long long)over); return MEME_E_STATE; }

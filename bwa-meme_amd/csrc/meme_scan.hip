@@ -66,3 +66,9 @@ int meme_scan_exclusive(meme_ctx* ctx, const i64* d_in, i64* d_out, i64 n) {
     HIP_TRY(hipGetLastError());
     return MEME_OK;
 }
+
+int meme_scan_total(meme_ctx* ctx, const i64* d_in, i64* d_out, i64 n, i64* h_total) {
+    const int rc = meme_scan_exclusive(ctx, d_in, d_out, n);
+    if (!rc) HIP_TRY(hipMemcpyAsync(h_total, d_out + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    return rc;
+}

@@ -242,8 +242,8 @@ int launch_tier(SeedRun& R, int tier, i64 n_todo, const i64* pending, int cset, 
     if (tier > 0 && need > sb.cap) {
         // overflow tiers re-run the reads that emitted more SMEMs than their slots hold, with 32 x more slots each:
         // refuse instead of exhausting the HBM the index lives in
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b / 2) {
+        size_t free_b = 0;
+        if (!meme_fits_free_hbm(need, 0, &free_b)) {
             meme_set_error("%lld reads emitted more than %d SMEMs each: re-running them needs %.1f GB of slots, more than half of the "
                            "free HBM (%.1f GB); seed this batch in smaller pieces", (long long)n_todo, R.tiers.cap[tier - 1],
                            need / 1e9, free_b / 1e9);
@@ -493,7 +493,7 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
     if ((rc = meme_buf_reserve(ctx, S.slot_hits, (size_t)nreads * sizeof(i64)))) return rc;
     if ((rc = meme_buf_reserve(ctx, S.slot_loc, (size_t)nreads * sizeof(i64)))) return rc;
     if ((rc = meme_buf_reserve(ctx, S.counters, 2 * SEED_CTRS * sizeof(unsigned long long)))) return rc;
-    for (int i = 0; i < SEED_EVS; ++i) if (!S.ev[i]) HIP_TRY(hipEventCreate(&S.ev[i]));
+    HIP_TRY(S.ev.ensure());
     SeedRun R;
     R.ctx = ctx; R.d_read_off = d_read_off; R.nreads = nreads; R.opt = opt;
     if ((rc = seed_pack(R, d_reads, max_len, total_bytes)) || (rc = seed_tier0(R)) || (rc = seed_overflow_tiers(R))) return rc;

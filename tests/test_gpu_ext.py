@@ -19,7 +19,7 @@ def _ext_split(request, monkeypatch):
     monkeypatch.setenv("MEME_TUNING", "ext_split=%d" % request.param)
 
 
-def _device_records(tmp_path, I, ext_opt=None, ascii=False, chain_opt=None, live_only=False, rounds=None):
+def _device_records(tmp_path, I, ext_opt=None, ascii=False, chain_opt=None, live_only=False, rounds=None, slab_jobs=None):
     fa = str(tmp_path / "c.fa")
     synth.write_fasta(fa, I["genome"], name="cg", contigs=3)
     prefix = build_index(fa, bits=14)
@@ -30,6 +30,8 @@ def _device_records(tmp_path, I, ext_opt=None, ascii=False, chain_opt=None, live
             ctx.set_tuning("ext_live_only", 1)
         if rounds is not None:
             ctx.set_tuning("ext_rounds", rounds)
+        if slab_jobs is not None:
+            ctx.set_tuning("ext_slab_jobs", slab_jobs)
         if ascii:       # the reads as FASTQ letters (mixed case, N and other IUPAC letters for ambiguous bases): converted on the device
             letters = np.frombuffer(b"ACGTN", np.uint8)[np.minimum(I["reads"], 4)].copy()
             rng = np.random.default_rng(3)
@@ -91,6 +93,62 @@ def test_live_only_hand_over_is_the_golden_records_minus_the_purged_ones(tmp_pat
         assert int(keep.sum()) <= R["n_ext_seeds"] < keep.shape[0]          # fewer seeds extended than chained, at least the survivors
     if rounds == 6:
         assert R["n_ext_seeds"] < 0.62 * keep.shape[0]
+
+
+_one_slab = {}
+
+
+def _one_slab_run(tmp_path, name, make, **kw):
+    """the default run (one slab) of a workload, once per setting of "ext_split": what the runs in slabs are compared with"""
+    key = (name, os.environ["MEME_TUNING"])
+    if key not in _one_slab:
+        _one_slab[key] = _device_records(tmp_path, make(), **kw)
+    return _one_slab[key]
+
+
+@pytest.mark.parametrize("slab_jobs", [256, 1])
+def test_slabs_give_the_one_slab_records(tmp_path, slab_jobs):
+    """Tuning "ext_slab_jobs": the jobs posed and aligned in slabs of whole reads (a slab's SeqPair offsets are 32-bit and start at the slab's
+    first job and byte).  The golden batch has more than 5 000 records and more jobs than records, so 256 jobs per side make at least five
+    slabs; 1 makes a slab of every read that has jobs -- every read's own offsets are then subtracted.  Same records, same jobs, more calls."""
+    I = ext_golden_inputs()
+    G = np.load(os.path.join(GOLDEN, "ext_golden.npz"))
+    D = _one_slab_run(tmp_path, "golden", ext_golden_inputs)
+    R = _device_records(tmp_path, I, slab_jobs=slab_jobs)
+    assert np.array_equal(R["reg_off"], G["reg_off"])
+    _assert_same(R["regs"], G["regs"], G["frac_rep_bits"])
+    assert R["n_pairs"] == D["n_pairs"] and R["n_retried"] == D["n_retried"]
+    assert R["n_bsw_calls"] > D["n_bsw_calls"]
+
+
+def test_slabs_in_rounds_give_the_golden_survivors(tmp_path):
+    """the same behind k_ext_advance: every round of "ext_rounds" poses its jobs in slabs of its own"""
+    I = ext_golden_inputs()
+    G = np.load(os.path.join(GOLDEN, "ext_golden.npz"))
+    D = _one_slab_run(tmp_path, "golden-rounds-2", ext_golden_inputs, live_only=True, rounds=2)
+    R = _device_records(tmp_path, I, live_only=True, rounds=2, slab_jobs=256)
+    keep, want_off = _live_of(G["reg_off"], G["regs"][:, 2], G["regs"][:, 3])
+    assert 0 < int(keep.sum()) < keep.shape[0] and R["total_seeds"] == keep.shape[0]
+    assert np.array_equal(R["reg_off"], want_off)
+    _assert_same(R["regs"], G["regs"][keep], G["frac_rep_bits"][keep])
+    assert int(keep.sum()) <= R["n_ext_seeds"] < keep.shape[0]
+    assert (R["n_pairs"], R["n_retried"], R["n_ext_seeds"]) == (D["n_pairs"], D["n_retried"], D["n_ext_seeds"])
+    assert R["n_bsw_calls"] > D["n_bsw_calls"]                     # (several slabs did run in the rounds)
+
+
+def test_slabs_behind_the_seed_filter_give_the_one_slab_records(tmp_path):
+    """the slabs walk the seed offsets the filter made (mem_flt_chained_seeds under -W 5: every read of the batch)"""
+    from common import flt_workload
+    make = lambda: flt_workload(5, lo=420, hi=500)
+    I = make()
+    co = hipapi.default_chain_opt(I["l_pac"])
+    co.min_chain_weight = 5
+    D = _one_slab_run(tmp_path, "flt5", make, chain_opt=co)
+    R = _device_records(tmp_path, I, chain_opt=co, slab_jobs=256)
+    assert D["regs"].shape[0] > 0 and D["n_flt_jobs"] > 500 and R["n_bsw_calls"] > D["n_bsw_calls"]
+    assert np.array_equal(R["reg_off"], D["reg_off"])
+    assert hipapi.records_equal(R["regs"], D["regs"])          # (field by field: the padding of a copied record array is whatever the allocator left)
+    assert (R["n_pairs"], R["n_retried"], R["n_flt_jobs"], R["n_flt_dropped"]) == (D["n_pairs"], D["n_retried"], D["n_flt_jobs"], D["n_flt_dropped"])
 
 
 def test_reads_as_fastq_letters_give_the_same_records(tmp_path):
