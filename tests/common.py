@@ -193,11 +193,12 @@ def flt_workload(min_chain_weight=0, n_long=120, n_short=400, lo=800, hi=1300):
             "text": text, "l_pac": l_pac, "contig_off": G["contig_off"], "contig_len": G["contig_len"]}
 
 
-def gcig_workload(n=3000, seed=77):
+def gcig_workload(n=3000, seed=77, read_len=(40, 251), bands=(1, 3, 10, 30, 100, 200, 400)):
     """Inputs of the CIGAR-kernel tests (tests/golden/gcig_golden.npz): a 300 kbp genome, reads of 40-250 bases sampled with
     substitutions, indels (up to 30 bases) and an occasional N, from both strands; per read one or two global-alignment jobs the way
     mem_reg2aln (src/bwamem.cpp:2314-2380) would pose them -- a query span of the read against the text span it came from (fwd+rc
-    coordinates; rev = both sequences reversed when on the reverse strand), band from 1 to 400.
+    coordinates; rev = both sequences reversed when on the reverse strand), band from 1 to 400.  read_len / bands: other read lengths
+    [lo, hi) and band choices (the defaults draw what the fixture was made from).
     Returns (genome, reads list, jobs as hipapi.GJOB records, explicit (query, target) code arrays per job)."""
     from pymeme import hipapi, synth
     rng = np.random.default_rng(seed)
@@ -206,7 +207,7 @@ def gcig_workload(n=3000, seed=77):
     l_pac = g.shape[0]
     reads, jobs, seqs = [], [], []
     for r in range(n):
-        L = int(rng.integers(40, 251))
+        L = int(rng.integers(*read_len))
         strand = int(rng.integers(0, 2))
         p = int(rng.integers(0, 2 * l_pac - 2 * L - 64)) if False else int(rng.integers(0, l_pac - L - 64)) + strand * l_pac
         src = text[p:p + L + 40]
@@ -233,7 +234,7 @@ def gcig_workload(n=3000, seed=77):
             qe = L - (int(rng.integers(0, 8)) if rng.random() < 0.5 else 0)
             rb = p + qb
             tl = max(1, min(tlen - qb + int(rng.integers(-3, 4)), 2 * l_pac - rb - 1, (l_pac - rb) if rb < l_pac else 10 ** 9))
-            w = int(rng.choice([1, 3, 10, 30, 100, 200, 400]))
+            w = int(rng.choice(list(bands)))
             w = max(w, abs(tl - (qe - qb)) + 3)                    # min_w of bwa_gen_cigar2 (src/bwa.cpp:314-315): the last cell is inside the band
             rev = 1 if rb >= l_pac else 0
             jobs.append((rb, r, qb, qe - qb, tl, w, rev))
@@ -334,13 +335,13 @@ KSWV_EDGE_WANT = [[150, 249, 149, -1, -1, 100, 0], [1, 0, 0, -1, -1, -1, -1], [6
                   [150, 1149, 149, -1, -1, 1000, 0]]
 
 
-def gencig_workload(n=2500, seed=177):
+def gencig_workload(n=2500, seed=177, read_len=(40, 251), bands=(0, 1, 3, 10, 30, 100, 200, 400)):
     """Inputs of the bwa_gen_cigar2 tests (tests/golden/gencig_golden.npz): the reads and genome of gcig_workload's kind, but the jobs are CALLS of
     bwa_gen_cigar2 as mem_reg2aln makes them (src/bwamem.cpp:2340-2347) -- w_ is the band ARGUMENT (0 .. 400, the function derives the band),
     a share of the calls have equal lengths and w_ = 0 (the gap-free shortcut), spans start and end inside the read, both strands.
     Returns (genome, reads list, calls as hipapi.CJOB records)."""
     from pymeme import hipapi
-    g, reads, jobs, _ = gcig_workload(n=n, seed=seed)
+    g, reads, jobs, _ = gcig_workload(n=n, seed=seed, read_len=read_len)
     rng = np.random.default_rng(seed + 5)
     l_pac = g.shape[0]
     calls = np.zeros(jobs.shape[0], dtype=hipapi.CJOB)
@@ -354,7 +355,7 @@ def gencig_workload(n=2500, seed=177):
             tlen = qlen
             w_ = int(rng.choice([1, 5, 100]))
         else:
-            w_ = int(rng.choice([0, 1, 3, 10, 30, 100, 200, 400]))
+            w_ = int(rng.choice(list(bands)))
         tlen = max(1, min(tlen, (l_pac - rb) if rb < l_pac else 2 * l_pac - rb))
         calls[k] = (rb, int(J["read"]), int(J["qb"]), qlen, tlen, w_, 0)
     return g, reads, calls
@@ -515,3 +516,110 @@ def matesw_pose_workload(seed=301, n_pairs=600, l_pac=240_000, n_contigs=3, read
         R[k] = (rb, rid, sc)
     return dict(genome=g, text=text, l_pac=l_pac, contig_off=contig_off, contig_len=contig_len, reads=np.concatenate(reads).astype(np.uint8), read_off=read_off,
                 read_len=np.array(lens, np.int32), regs=R, reg_off=np.array(reg_off, np.int64), pes=np.array(pes, np.int32))
+
+
+SAM_LONG_STRINGS = (63, 64, 65, 127, 128, 129, 400)
+SAM_LONG_NAMES = (1, 63, 64, 65, 128, 300)
+SAM_LONG_READS = (1, 63, 64, 65, 500)
+
+
+def sam_long_workload(n=336, seed=401):
+    """Records for the SAM-text kernel's 64-lane copy loops (a second set beside sam_workload(); checked against the oracle only): names of 1-300 bytes,
+    MD and XA strings of SAM_LONG_STRINGS bytes -- valid MD text of mismatches and long deletions, XA lists of several alternates -- at blob offsets of
+    every residue mod 4 (the operations in front of an MD string then start at an unaligned byte), the last XA string in the blob's final bytes; reads of
+    1-500 bases, both strands; then ten supplementary records (which = 1, not alt) whose clipping is cut off SEQ and QUAL on either strand, and one
+    record with every numeric field at its widest on a contig with a 60-byte name.  Layout of sam_workload()'s return."""
+    from oracle_py import SAM_REC_DTYPE
+    rng = np.random.default_rng(seed)
+    contigs = ["chr1", "chr2_random", "HLA-A*01:01", "c", "chrUn_" + "K" * 54]
+    assert len(contigs[4]) == 60
+    blob = bytearray()
+    names, reads, quals, rows = [], [], [], []
+
+    def pad_to(res):
+        while len(blob) % 4 != res:
+            blob.append(0)
+
+    def bases(k):
+        return "".join("ACGT"[int(x)] for x in rng.integers(0, 4, size=k))
+
+    def md_of(n):
+        s, big = "", n > 200
+        while n - len(s) > 44:
+            if big and rng.random() < 0.3 and n - len(s) > 160:
+                s += "%d^%s" % (int(rng.integers(0, 100)), bases(int(rng.integers(50, 101))))          # a long deletion
+            else:
+                s += "%d%s" % (int(rng.integers(0, 30)), bases(1))                                     # a mismatch
+        r = n - len(s)
+        s += ("0^%s5" % bases(r - 3)) if r >= 4 else "123"[:r]
+        assert len(s) == n
+        return s.encode()
+
+    def xa_of(n):
+        s = ""
+        while n - len(s) >= 12 + 34:
+            s += "%s,%s%d,%dM%dS,%d;" % (contigs[int(rng.integers(0, 4))], "+-"[int(rng.integers(0, 2))], int(rng.integers(1, 10 ** 9)), int(rng.integers(1, 200)),
+                                         int(rng.integers(1, 99)), int(rng.integers(0, 30)))
+        r = n - len(s)                       # the last alternate takes what is left: "c,+P,1M1M...,0;" = 7 + digits of P + 2 per operation
+        pd = 1 if (r - 7) % 2 else 2
+        s += "c,+%s,%s,0;" % ("7" * pd, "1M" * ((r - 7 - pd) // 2))
+        assert len(s) == n, (n, len(s))
+        return s.encode()
+
+    def cigar_of(L, clip):
+        if L < 8:
+            return np.array([L << 4], np.uint32)
+        ops, left = [], L
+        front = back = 0
+        if clip:
+            front, back = int(rng.integers(1, L // 4 + 1)), int(rng.integers(1, L // 4 + 1))
+            left -= front + back
+        m = int(rng.integers(1, left))
+        mid = [(m, 0), (int(rng.integers(1, 40)), 2), (left - m, 0)] if rng.random() < 0.6 else [(m, 0), (1, 1), (left - m - 1, 0)] if left - m > 1 else [(left, 0)]
+        if front:
+            ops.append((front, 3 if rng.random() < 0.5 else 4))
+        ops += mid
+        if back:
+            ops.append((back, 3 if rng.random() < 0.5 else 4))
+        return np.array([l << 4 | o for l, o in ops], np.uint32)
+
+    def add(L, name_len, md_len, xa_len, cig_res, xa_res, is_rev, which, has_q, **over):
+        k = len(rows)
+        reads.append(rng.choice(np.array([0, 1, 2, 3, 4], np.uint8), size=L, p=[0.245, 0.245, 0.245, 0.245, 0.02]))
+        quals.append(bytes(rng.integers(33, 74, size=L).astype(np.uint8)) if has_q else None)
+        names.append((("r%d:" % k) + "n" * 300).encode()[:name_len])
+        r = np.zeros(1, SAM_REC_DTYPE)[0]
+        r["read"], r["rid"], r["pos"], r["is_rev"], r["mapq"] = k, int(rng.integers(0, len(contigs))), int(rng.integers(0, 3 * 10 ** 9)), is_rev, int(rng.integers(0, 61))
+        r["flag"] = (0x40 if k & 1 else 0x80) | (2 if rng.random() < 0.6 else 0) | (0x800 if which else 0)
+        r["which"], r["score"], r["sub"], r["NM"] = which, int(rng.integers(0, 501)), int(rng.integers(-1, 400)), int(rng.integers(0, 80))
+        cg = cigar_of(L, clip=bool(which) or rng.random() < 0.3)
+        pad_to(cig_res)
+        r["cigar_off"], r["n_cigar"] = len(blob), cg.shape[0]
+        blob.extend(cg.tobytes()); blob.extend(md_of(md_len)); blob.append(0)
+        if k % 4 != 3:
+            r["has_mate"], r["m_rid"], r["m_pos"], r["m_is_rev"] = 1, (int(r["rid"]) if k % 2 else int(rng.integers(0, len(contigs)))), int(r["pos"]) + int(rng.integers(-600, 600)), int(rng.integers(0, 2))
+            if r["m_pos"] < 0:
+                r["m_pos"] = 0
+            mc = cigar_of(int(rng.integers(30, 251)), clip=rng.random() < 0.5)
+            pad_to(int(rng.integers(0, 4)))
+            r["m_cigar_off"], r["m_n_cigar"] = len(blob), mc.shape[0]
+            blob.extend(mc.tobytes())
+        for f, v in over.items():
+            r[f] = v
+        r["xa_off"] = -1
+        if xa_len:
+            pad_to(xa_res)
+            r["xa_off"] = len(blob)
+            blob.extend(xa_of(xa_len)); blob.append(0)
+        rows.append(r)
+
+    S, N, R = SAM_LONG_STRINGS, SAM_LONG_NAMES, SAM_LONG_READS + (150, 250)
+    for k in range(n):
+        add(R[(k + k // 7) % 7], N[k % 6], S[k % 7], S[(k // 7) % 7] if k % 3 else 0, k % 4, (k // 49) % 4, k & 1, 0, k % 11 != 0)
+    for L in SAM_LONG_READS:                         # hard clipping cut off SEQ / QUAL: reverse strand (the clipped end swaps), then forward
+        for is_rev in (1, 0):
+            add(L, 64, 65, 129, 1, 2, is_rev, 1, True, is_alt=0)
+    add(150, 300, 400, 400, 3, 0, 1, 0, True, pos=(1 << 33) - 5, m_pos=(1 << 33) - 600, rid=4, m_rid=4, has_mate=1, m_is_rev=0, NM=2 ** 31 - 1, score=2 ** 31 - 1, sub=2 ** 31 - 1,
+        mapq=255, flag=0xfeff | 0x10000)
+    add(65, 128, 129, 400, 2, 1, 0, 0, True)         # the blob ends with this record's XA string and its NUL
+    return np.array(rows, SAM_REC_DTYPE), np.frombuffer(bytes(blob), dtype=np.uint8).copy(), names, reads, quals, contigs

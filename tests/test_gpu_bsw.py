@@ -129,3 +129,134 @@ def test_ring_of_band_columns_equals_a_word_per_query_column(w):
                 assert np.array_equal(bsw_gen.outputs(got), bsw_gen.outputs(want)), (kw, w, circ)
     finally:
         c.close()
+
+
+# ---- the launch shapes only production-sized batches select: the device entry (class ranges read back, every class launched), one launch per LDS class from the
+# ---- host entry, and grids of one and three workgroups, where a lane / group handles dozens of pairs in sequence -------------------------------------------
+_oracle_cache = {}
+
+
+def _oracle(key, make, w, eb=5):
+    """(pairs, ref, qer, the oracle's six outputs) of a generated batch, computed once per module run"""
+    if (key, w, eb) not in _oracle_cache:
+        if key not in _oracle_cache:
+            _oracle_cache[key] = make()
+        pairs, ref, qer = _oracle_cache[key]
+        want = pairs.copy()
+        O.bsw_batch(want, ref, qer, w, O.default_bsw_params(eb), threads=0)
+        _oracle_cache[(key, w, eb)] = bsw_gen.outputs(want)
+    return _oracle_cache[key] + (_oracle_cache[(key, w, eb)],)
+
+
+def _concat(batches):
+    """several make_pairs batches as one (the sequence offsets shifted)"""
+    ps, rs, qs, ro, qo = [], [], [], 0, 0
+    for p, r, q in batches:
+        p = p.copy(); p["idr"] += ro; p["idq"] += qo
+        ps.append(p); rs.append(r); qs.append(q)
+        ro += r.shape[0]; qo += q.shape[0]
+    return np.concatenate(ps), np.concatenate(rs), np.concatenate(qs)
+
+
+_BOUNDARY_Q = (1, 30, 31, 62, 63, 94, 95, 126, 127, 158, 159, 222, 223, 318, 319, 600, 601)
+
+
+def _boundary_batch():
+    return _concat([bsw_gen.make_pairs(130, seed=100 + q, min_q=q, max_q=q, h0_max=60) for q in _BOUNDARY_Q])
+
+
+def _mixed_batch():
+    a = bsw_gen.make_pairs(300, seed=21, max_q=120, h0_max=30000)
+    b = bsw_gen.make_pairs(300, seed=22, max_q=700)
+    pairs, ref, qer = _concat([a, b])
+    return pairs[np.random.default_rng(3).permutation(pairs.shape[0])].copy(), ref, qer
+
+
+def _on_device(ctx, pairs, ref, qer, w, opt):
+    """meme_bsw_batch_device on torch tensors, as bench.py's BSW leg calls it; the six outputs back"""
+    import torch
+    d_pairs = torch.from_numpy(pairs.copy().view(np.uint8)).cuda()
+    d_ref = torch.from_numpy(np.concatenate([ref, np.zeros(16, np.uint8)])).cuda()        # (the host entry's buffers have 16 bytes beyond the sequences too)
+    d_qer = torch.from_numpy(np.concatenate([qer, np.zeros(16, np.uint8)])).cuda()
+    torch.cuda.synchronize()
+    ctx.bsw_batch_device(d_pairs.data_ptr(), d_ref.data_ptr(), d_qer.data_ptr(), pairs.shape[0], w, opt)
+    ctx.sync()
+    return bsw_gen.outputs(d_pairs.cpu().numpy().view(hipapi.SEQPAIR))
+
+
+@pytest.mark.parametrize("circ", [1, 0])
+def test_device_entry_equals_golden_and_oracle(ctx, circ):
+    """meme_bsw_batch_device does not know the longest query: it reads it back and launches EVERY length class, each finding its range on the device and
+    leaving when it is empty -- bench.py's and the extension stage's entry, which no other test calls."""
+    ctx.set_tuning("bsw_circ", circ)
+    try:
+        z = np.load(os.path.join(GOLDEN, "bsw_golden.npz"))
+        pairs = z["pairs"].astype(hipapi.SEQPAIR).copy()
+        for w in (100, 200):
+            for eb in (5, 0):
+                assert np.array_equal(_on_device(ctx, pairs, z["ref"], z["qer"], w, _opt(eb)), z["scalar_w%d_eb%d" % (w, eb)]), (w, eb)
+        # every class boundary in ONE batch: several classes have a range, the others are empty, in the same call
+        pairs, ref, qer, want = _oracle("boundaries", _boundary_batch, 100)
+        lens = set(pairs["len2"].tolist())
+        assert lens == set(_BOUNDARY_Q) and pairs.shape[0] == 17 * 130
+        assert np.array_equal(_on_device(ctx, pairs, ref, qer, 100, _opt(5)), want)
+        pairs, ref, qer, want = _oracle("mixed", _mixed_batch, 100)
+        assert np.array_equal(_on_device(ctx, pairs, ref, qer, 100, _opt(5)), want)
+    finally:
+        ctx.set_tuning("bsw_circ", 1)
+
+
+@pytest.mark.parametrize("max_q", [600, 120])
+def test_host_entry_launches_per_class_beyond_the_one_launch_bound(max_q):
+    """launch_bsw sends a batch of fewer than n_cus * 64 * 16 pairs out as ONE launch of the longest query's class; production's 2 M-read chunks are beyond
+    that and get one launch per LDS class.  3 000 oracle-checked pairs, named n_cus * 1024 + 1000 times over (the replicas share the sequence bytes).
+    max_q = 120: the classes above the longest query are skipped by the host."""
+    import torch
+    n_cus = torch.cuda.get_device_properties(0).multi_processor_count
+    base, ref, qer, want = _oracle(("classes", max_q), lambda: bsw_gen.make_pairs(3000, seed=71 + max_q, max_q=max_q, min_q=1), 100)
+    n = n_cus * 1024 + 1000
+    assert n > n_cus * 64 * 16
+    idx = np.arange(n) % base.shape[0]
+    pairs = base[idx].copy()
+    c = hipapi.Context(0)
+    try:
+        c.set_tuning("bsw_lane_min_pairs", 0)
+        for circ in (1, 0):
+            c.set_tuning("bsw_circ", circ)
+            got = pairs.copy()
+            c.bsw_batch(got, ref, qer, 100, _opt(5))
+            bad = np.nonzero((bsw_gen.outputs(got) != want[idx]).any(axis=1))[0]
+            assert bad.size == 0, (circ, bad.size, int(bad[0]), int(idx[bad[0]]))
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("blocks", [1, 3])
+def test_one_and_three_workgroups_take_the_whole_batch(blocks):
+    """Tuning "bsw_blocks": the persistent grids draw pairs by ticket; with the default grid and a test-sized batch a lane or group sees one pair, at most two.
+    One and three workgroups: a lane of k_bsw_lane / k_bsw_lane_circ takes ~24 pairs in turn (state left in the LDS ring or the registers by pair n would show
+    in pair n + 1), a group of k_bsw<LP> ~25, HBM-workspace rows included."""
+    c = hipapi.Context(0)
+    try:
+        c.set_tuning("bsw_blocks", blocks)
+        c.set_tuning("bsw_lane_min_pairs", 0)
+        for w in (100, 7):
+            pairs, ref, qer, want = _oracle("lanes", lambda: bsw_gen.make_pairs(1500, seed=81, max_q=320, min_q=100, h0_max=900), w)
+            assert pairs.shape[0] // (64 * blocks) >= 7 and (blocks > 1 or pairs.shape[0] // 64 >= 20)
+            for circ in (1, 0):
+                c.set_tuning("bsw_circ", circ)
+                got = pairs.copy()
+                c.bsw_batch(got, ref, qer, w, _opt(5))
+                assert np.array_equal(bsw_gen.outputs(got), want), (w, circ)
+        c.set_tuning("bsw_circ", 1)
+        c.set_tuning("bsw_lane_min_pairs", 1 << 30)
+        pairs, ref, qer, want = _oracle("groups", lambda: bsw_gen.make_pairs(400, seed=82, max_q=700), 100)
+        got = pairs.copy()
+        c.bsw_batch(got, ref, qer, 100, _opt(5))
+        assert np.array_equal(bsw_gen.outputs(got), want)
+        pairs, ref, qer, want = _oracle("hbm rows", lambda: _concat([bsw_gen.make_pairs(6, seed=31, min_q=5000, max_q=9000, h0_max=100), bsw_gen.make_pairs(200, seed=32, max_q=300)]), 100)
+        got = pairs.copy()
+        c.bsw_batch(got, ref, qer, 100, _opt(5))
+        assert np.array_equal(bsw_gen.outputs(got), want)
+    finally:
+        c.close()

@@ -13,8 +13,10 @@ from pymeme import hipapi, synth
 pytestmark = pytest.mark.gpu
 
 
-def _run(ctx, prefix, reads, wave_tiers=1):
+def _run(ctx, prefix, reads, wave_tiers=1, tuning=()):
     ctx.set_tuning("chain_wave_tiers", wave_tiers)
+    for key, value in tuning:
+        ctx.set_tuning(key, value)
     off = np.zeros(len(reads) + 1, np.int64)
     off[1:] = np.cumsum([len(r) for r in reads])
     flat = np.concatenate(reads)
@@ -31,6 +33,23 @@ def _run(ctx, prefix, reads, wave_tiers=1):
 def test_device_chains_equal_reference_golden_and_oracle(tmp_path, wave_tiers):
     """wave_tiers 1: repeat-rich reads go through the LDS tier (one wavefront per read, chains in LDS), the B-tree tier takes what that
     leaves; 0: everything beyond the lane-per-read tier goes through the B-tree tier."""
+    _golden_body(tmp_path, wave_tiers)
+
+
+def test_golden_reads_with_nothing_routed_past_the_lane_tier(tmp_path):
+    """The fixture's reads are the ones the lane tier normally finishes or never sees (more than chain_light_hits hits: LDS tier at once).  With
+    chain_light_hits out of reach the lane tier starts on every read with at most 256 hits and hands what it cannot hold to the LDS tier of 256 chains."""
+    G = np.load(os.path.join(GOLDEN, "chain_golden.npz"))
+    sm = np.zeros(G["smems"].shape[0], hipapi.MEM_TL)
+    sm["start"], sm["end"], sm["hitbeg"], sm["hitcount"] = G["smems"].T
+    work = _work(sm, G["smem_off"], G["read_len"])
+    assert ((work > 32) & (work <= 256)).sum() >= 20 and (work > 256).sum() == 0       # by default routed to the LDS tier at once; with the key all of them are the lane tier's
+    _golden_body(tmp_path, 1, (("chain_light_hits", 1 << 30),), every=6)
+
+
+def _golden_body(tmp_path, wave_tiers, tuning=(), every=1):
+    """every: the stride of the read-by-read comparisons with the fixture (Python loops, 13 s for all reads); the counts and tree sizes of every read, and the
+    oracle on every read, are compared whatever it is"""
     g, reads = chain_golden_workload()
     fa = str(tmp_path / "c.fa")
     synth.write_fasta(fa, g, name="cg", contigs=3)
@@ -38,7 +57,7 @@ def test_device_chains_equal_reference_golden_and_oracle(tmp_path, wave_tiers):
     G = np.load(os.path.join(GOLDEN, "chain_golden.npz"))
     ctx = hipapi.Context(0)
     try:
-        (smems, smem_off, hits, hit_off), R, l_pac, contigs = _run(ctx, prefix, reads, wave_tiers)
+        (smems, smem_off, hits, hit_off), R, l_pac, contigs = _run(ctx, prefix, reads, wave_tiers, tuning)
     finally:
         ctx.close()
     n = len(reads)
@@ -50,7 +69,7 @@ def test_device_chains_equal_reference_golden_and_oracle(tmp_path, wave_tiers):
 
     def canon(sm_start, sm_end, sm_hb, sm_hc, hv):
         return sorted((int(a), int(b), tuple(int(x) for x in hv[int(hb):int(hb) + int(hc)])) for a, b, hb, hc in zip(sm_start, sm_end, sm_hb, sm_hc))
-    for r in range(n):
+    for r in range(0, n, every):
         s0, s1, h0, h1 = int(smem_off[r]), int(smem_off[r + 1]), int(hit_off[r]), int(hit_off[r + 1])
         mine = canon(smems["start"][s0:s1], smems["end"][s0:s1], smems["hitbeg"][s0:s1], smems["hitcount"][s0:s1], hits[h0:h1])
         gs = G["smems"][s0:s1]
@@ -59,7 +78,8 @@ def test_device_chains_equal_reference_golden_and_oracle(tmp_path, wave_tiers):
     contig_off = np.array([c[0] for c in contigs], np.int64)
     contig_alt = np.zeros(len(contigs), np.uint8)
     assert R["n_fallback"] == 0 and not R["fallback"].any()                 # every read is chained on the device
-    for r in range(n):
+    assert np.array_equal(R["chain_off"], G["chain_off"]) and np.array_equal(R["tree_size"], G["tree_size"])
+    for r in range(0, n, every):
         c0, c1 = int(G["chain_off"][r]), int(G["chain_off"][r + 1])
         d0, d1 = int(R["chain_off"][r]), int(R["chain_off"][r + 1])
         assert d1 - d0 == c1 - c0 and int(R["tree_size"][r]) == int(G["tree_size"][r]), r
@@ -96,6 +116,10 @@ def test_device_chains_equal_reference_on_equal_positions_and_big_trees():
         R = ctx.chain_batch_host(sm, G["smem_off"], G["hits"], G["hit_off"], G["read_len"], _contigs3(), hipapi.default_chain_opt(int(G["l_pac"])))
     finally:
         ctx.close()
+    _assert_dup_golden(R, G)
+
+
+def _assert_dup_golden(R, G):
     assert R["n_fallback"] == 0
     assert np.array_equal(R["chain_off"], G["chain_off"]) and np.array_equal(R["seed_off"], G["seed_off"])
     assert np.array_equal(R["tree_size"], G["tree_size"])
@@ -178,3 +202,99 @@ def test_chain_call_needs_a_seeded_batch_and_sane_options(tmp_path):
             assert np.all(c[:-1] >= c[1:])
     finally:
         ctx.close()
+
+
+# ---- the routes between the tiers: k_chain_route's thresholds and the lane tier's give-up limit moved through the tuning keys, so that every hand-over
+# ---- (lane -> LDS256 -> B-tree, LDS-N -> B-tree) is taken by reads the default thresholds send elsewhere ------------------------------------------------
+_ROUTES = [(0, 256), (1 << 30, 256), (1 << 30, 0), (1 << 30, 1 << 30), (32, 31), (32, 32), (32, 33)]          # (chain_light_hits, chain_lane_hits)
+_route_inputs = {}
+
+
+def _work(smems, smem_off, read_len, max_occ=500, min_seed_len=19):
+    """k_chain_route's measure: the hits a read has to walk, sum over its SMEMs of min(hitcount, max_occ); 0 for reads below min_seed_len"""
+    h = np.minimum(smems["hitcount"].astype(np.int64), max_occ)
+    cs = np.concatenate([[0], np.cumsum(h)])
+    return np.where(np.asarray(read_len) >= min_seed_len, cs[smem_off[1:]] - cs[smem_off[:-1]], 0)
+
+
+def _route_model(work, n_smems, light, lane_hits):
+    """(class k_chain_route gives a read: 0 lane tier, 1 / 2 / 3 LDS tier of 256 / 512 / 1 024 chains; reads certain to pass through a wavefront tier; chains the
+    last LDS tier on a read's way holds)"""
+    cls = np.where(work > 512, 3, np.where(work > 256, 2, np.where(work > light, 1, 0)))
+    gives_up = (cls == 0) & (work > 0) & ((work > lane_hits) | (n_smems > 48))            # (SMEM_CAP1 = 48; the 16-chain / 8-seed limits give up more)
+    return cls, (cls > 0) | gives_up, np.where(cls == 3, 1024, np.where(cls == 2, 512, 256))
+
+
+def _inputs(name):
+    if name not in _route_inputs:
+        if name == "dup":
+            G = np.load(os.path.join(GOLDEN, "chain_dup_golden.npz"))
+            sm = np.zeros(G["smems"].shape[0], hipapi.MEM_TL)
+            sm["start"], sm["end"], sm["hitbeg"], sm["hitcount"] = G["smems"].T
+            _route_inputs[name] = (sm, G["smem_off"], G["hits"], G["hit_off"], G["read_len"], int(G["l_pac"]), G)
+        else:
+            _route_inputs[name] = _with_boundary_reads(*_adversarial(1500, 1300)) + (200_000, None)
+    return _route_inputs[name]
+
+
+def _with_boundary_reads(smems, smem_off, hits, hit_off, read_len):
+    """+ 30 reads with exactly 31, 32 and 33 hits to walk (made-up reads cut off at that many hits): the two sides of chain_light_hits = 32 and of the
+    chain_lane_hits values next to it"""
+    import chain_gen
+    rng = np.random.default_rng(77)
+    sm_l, h_l, so, ho = [smems], [hits], list(smem_off), list(hit_off)
+    for k in range(30):
+        want = 31 + k % 3
+        while True:
+            sm, h = chain_gen.make_read(rng, n_smems=6, max_hits=40)
+            if int(sm["hitcount"].sum()) >= want:
+                break
+        keep = int(np.searchsorted(np.cumsum(sm["hitcount"]), want))               # the SMEM the cut falls into
+        sm = sm[:keep + 1].copy()
+        sm["hitcount"][keep] = want - int(sm["hitcount"][:keep].sum())
+        sm_l.append(sm.astype(hipapi.MEM_TL)); h_l.append(h[:want])
+        so.append(so[-1] + sm.shape[0]); ho.append(ho[-1] + want)
+    return np.concatenate(sm_l), np.array(so, np.int64), np.concatenate(h_l), np.array(ho, np.int64), np.concatenate([read_len, np.full(30, 150, np.int32)])
+
+
+@pytest.mark.parametrize("light,lane_hits", _ROUTES)
+def test_every_route_between_the_tiers_gives_the_same_chains(light, lane_hits):
+    """light = 0: every read with hits is routed to an LDS tier at once; 1 << 30: none by chain_light_hits (reads beyond 256 / 512 hits still go to the tiers of
+    512 / 1 024 chains: those thresholds are fixed), the lane tier starts on the rest -- and gives every one up (lane_hits = 0), or walks until its 16 chains or
+    8 seeds per chain are full (1 << 30); 31 / 32 / 33: either side of the default."""
+    for name, change in (("dup", {}), ("adversarial", {}), ("adversarial", dict(w=3))):
+        smems, smem_off, hits, hit_off, read_len, l_pac, G = _inputs(name)
+        do, oo = hipapi.default_chain_opt(l_pac), O.default_chain_opt(l_pac)
+        for k, v in change.items():
+            setattr(do, k, v); setattr(oo, k, v)
+        work = _work(smems, smem_off, read_len)
+        cls, waved, cap = _route_model(work, np.diff(smem_off), light, lane_hits)
+        assert (work > 0).sum() > 0.9 * work.shape[0] and (work > 256).sum() > 0 and (work > 512).sum() > 0
+        if light == 0:
+            assert (cls[work > 0] > 0).all()
+        elif light == 1 << 30:
+            assert ((cls == 0) & (work > 32)).sum() > 100                # reads the default sends to an LDS tier at once, now the lane tier's
+        elif G is None:
+            assert all((work == v).sum() >= 10 for v in (31, 32, 33))    # 32 hits: the lane tier's, given up at lane_hits = 31; 33: routed
+        ctx = hipapi.Context(0)
+        try:
+            ctx.set_tuning("chain_light_hits", light)
+            ctx.set_tuning("chain_lane_hits", lane_hits)
+            R = ctx.chain_batch_host(smems, smem_off, hits, hit_off, read_len, _contigs3(), do)
+            tier3 = int(ctx.timings().chain_tier3_reads)
+        finally:
+            ctx.close()
+        print("%s %s light=%d lane_hits=%d: n_tier2 %d (model: at least %d), chain_tier3_reads %d" % (name, change, light, lane_hits, R["n_tier2"], int(waved.sum()), tier3))
+        assert R["n_fallback"] == 0
+        assert R["n_tier2"] >= int(waved.sum())
+        if light == 0 or lane_hits == 0:
+            assert R["n_tier2"] >= int((work > 0).sum())
+        if G is not None:
+            _assert_dup_golden(R, G)
+            # a read with more chains than the last LDS tier on its way holds ends in the B-tree tier (k_chain_lds<N> gives up beyond N chains)
+            over = int((G["tree_size"] > cap).sum())
+            assert over >= 4 and tier3 >= over, (over, tier3)
+        else:
+            bad = O.chain_compare_batch(smems, smem_off, hits, hit_off, read_len, np.array([0, 70_000, 150_000], np.int64), np.array([0, 0, 1], np.uint8), oo, R)
+            assert bad == (0, -1), (name, change, bad)
+            assert tier3 >= int((R["tree_size"] > cap).sum())

@@ -260,3 +260,37 @@ def test_extension_refuses_seeds_without_their_reads(tmp_path):
         assert R["regs"].shape[0] > 0
     finally:
         ctx.close()
+
+
+def test_max_batch_refuses_more_reads_and_takes_that_many(tmp_path):
+    """Tuning "max_batch" (the bound aligner sets it from its memory budget and feeds pieces when a call answers MEME_E_CAPACITY): the stage refuses a seeded
+    batch of 11 reads and gives for 10 the records an unrestricted ctx gives."""
+    from common import chain_golden_workload
+    g, reads = chain_golden_workload()
+    fa = str(tmp_path / "c.fa")
+    synth.write_fasta(fa, g, name="cg", contigs=3)
+    prefix = build_index(fa, bits=14)
+    ann = [l.split() for l in open(prefix + ".ann")]
+    l_pac = int(ann[0][0])
+    contigs = [(int(ann[2 + 2 * k][0]), int(ann[2 + 2 * k][1]), 0) for k in range(int(ann[0][1]))]
+
+    def batch(n):
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum([len(r) for r in reads[:n]])
+        return np.concatenate(reads[:n]), off
+    ctx, free = hipapi.Context(0), hipapi.Context(0)
+    try:
+        ctx.load_index_files(prefix)
+        free.load_index_files(prefix)
+        ctx.set_tuning("max_batch", 10)
+        ctx.seed_batch_resident(*batch(11))
+        with pytest.raises(hipapi.MemeError, match="exceed the ctx's"):
+            ctx.extend_last_batch_host(contigs, hipapi.default_chain_opt(l_pac))
+        ctx.seed_batch_resident(*batch(10))
+        free.seed_batch_resident(*batch(10))
+        a, b = ctx.extend_last_batch_host(contigs, hipapi.default_chain_opt(l_pac)), free.extend_last_batch_host(contigs, hipapi.default_chain_opt(l_pac))
+        assert a["reg_off"].shape[0] == 11 and a["regs"].shape[0] > 0
+        assert np.array_equal(a["reg_off"], b["reg_off"]) and hipapi.records_equal(a["regs"], b["regs"])
+    finally:
+        ctx.close()
+        free.close()

@@ -135,3 +135,284 @@ def test_device_gen_cigar_equals_oracle_with_other_penalties(tmp_path):
             _check_calls(res, cig, md, want)
     finally:
         ctx.close()
+
+
+# ---- the storage modes, LDS budgets and batch limits that only the batch's SIZE selects: forced through the tuning keys, the host-side model of
+# ---- gcig_plan / k_gcig_sizes (csrc/meme_gcig.hip) says before the GPU call which path every job takes ---------------------------------------
+_GRP = ((16, 4, 4096, 24 * 1024), (32, 2, 8192, 24 * 1024), (64, 1, 12288, 16 * 1024))      # GCIG_GRP: lanes, jobs per wavefront, zmax, lds_max
+_Z_LDS_CAP, _Z_LDS_WINDOW = 8192, 2048
+
+
+def _groups_on():
+    return os.environ["MEME_TUNING"] == "gcig_groups=1"
+
+
+def _plan(qlen, tlen, w, groups, zcap_key=-1):
+    """gcig_plan + k_gcig_sizes on the host.  w < 0: the gap-free shortcut.  Returns (zcap in force, LDS matrix bytes of the three group classes, class per job
+    -- 0 / 1 / 4: k_gcig_grp<16 / 32 / 64>, 2: k_gcig_t, 3: k_gcig_nogap, the slots of meme_timings::gcig_class_jobs --, band columns per job)."""
+    qlen, tlen, w = (np.asarray(x, np.int64) for x in (qlen, tlen, w))
+    qmax, tmax = int(qlen.max()), int(tlen.max())
+    qcap, tcap = (qmax + 3) & ~3, (tmax + 3) & ~3
+    lds_base = 3 * (qmax + 2) * 4 + qcap + tcap
+    zwant = zcap_key if zcap_key >= 0 else (_Z_LDS_CAP if tmax * 33 <= _Z_LDS_CAP else _Z_LDS_WINDOW)
+    zcap = zwant if lds_base + zwant <= 32 * 1024 else 0
+    grp_z = []
+    for lanes, per_wave, zmax, lds_max in _GRP:
+        z = min((lanes * tmax + 3) & ~3, zmax) if groups else 0
+        if per_wave * (3 * 2 * lanes * 4 + qcap + tcap + z) > lds_max:
+            z = 0
+        grp_z.append(z)
+    n_col = np.minimum(qlen, 2 * w + 1)
+    cls = np.full(qlen.shape[0], 3, np.int64)
+    left = w >= 0
+    for slot, (lanes, _, _, _), z in zip((0, 1, 4), _GRP, grp_z):
+        take = left & (n_col <= lanes) & (n_col * tlen <= z)
+        cls[take] = slot
+        left &= ~take
+    cls[left] = 2
+    return zcap, grp_z, cls, n_col
+
+
+def _walks(n_col, tlen, zcap):
+    """how k_gcig_t walks a job's matrix back: (whole matrix in LDS, through a window of LDS rows, straight on global memory) masks; rows of the window"""
+    in_lds = n_col * tlen <= zcap
+    windowed = ~in_lds & (zcap >= 2 * n_col + 8)
+    return in_lds, windowed, ~in_lds & ~windowed, np.where(windowed, (zcap - 8) // np.maximum(n_col, 1), 0)
+
+
+def _class_counts(cls):
+    return [int((cls == k).sum()) for k in range(6)]
+
+
+def _cjob_band(qlen, tlen, w_, a=1, o_del=6, e_del=1, o_ins=6, e_ins=1):
+    """k_cjob_prep = bwa_gen_cigar2's preamble (src/bwa.cpp:288-316): the band ksw_global2 gets, -1 for the gap-free shortcut"""
+    qlen, tlen, w_ = (np.asarray(x, np.int64) for x in (qlen, tlen, w_))
+    half = ((qlen + 1) >> 1) * a
+    max_ins = ((half - o_ins) / e_ins + 1.).astype(np.int64)            # (int) of a double: towards zero, as astype does
+    max_del = ((half - o_del) / e_del + 1.).astype(np.int64)
+    max_gap = np.maximum(np.maximum(max_ins, max_del), 1)
+    dl = np.abs(tlen - qlen)
+    w = np.maximum(np.minimum((max_gap + dl + 1) >> 1, w_), dl + 3)
+    return np.where((qlen == tlen) & (w_ == 0), -1, w)
+
+
+# matrix in LDS / walked through a window / walked straight on global memory, of the 4 000 jobs of gcig_workload() when all go to k_gcig_t
+_ZCAP_SPLIT = {0: (0, 0, 4000), 64: (0, 1183, 2817), 2048: (777, 3223, 0), 8192: (2187, 1813, 0), 24576: (3280, 720, 0)}
+
+
+@pytest.mark.parametrize("zcap", sorted(_ZCAP_SPLIT))
+def test_every_matrix_storage_mode_gives_the_golden_cigars(tmp_path, zcap):
+    """Tuning "gcig_zcap": the LDS k_gcig_t keeps per job for its backtrack matrix.  The fixture's targets reach 290 bases, so by default every test of this
+    file runs with 2 048 bytes; 8 192 is what 150-bp reads get, 0 and 64 walk the matrix straight on global memory, 64 also through a window of two rows."""
+    g, reads, jobs, _ = gcig_workload()
+    G = np.load(os.path.join(GOLDEN, "gcig_golden.npz"))
+    groups = _groups_on()
+    q, t, w = jobs["qlen"], jobs["tlen"], jobs["w"]
+    # every job a wavefront: the table of the modes
+    zc, _, cls_all, n_col = _plan(q, t, w, False, zcap)
+    assert zc == zcap and (cls_all == 2).all()
+    in_lds, windowed, straight, rows = _walks(n_col, t.astype(np.int64), zc)
+    assert (int(in_lds.sum()), int(windowed.sum()), int(straight.sum())) == _ZCAP_SPLIT[zcap]
+    if zcap == 64:
+        assert int((rows[windowed] == 2).sum()) > 0
+    if zcap == 8192:
+        assert int(in_lds.sum()) > jobs.shape[0] // 2
+    # the run's own classes: what is left to k_gcig_t, and the modes among that
+    zc, _, cls, _ = _plan(q, t, w, groups, zcap)
+    mine = cls == 2
+    assert mine.sum() > 0 and (groups or mine.all())
+    m_lds, m_win, m_str, _ = _walks(n_col[mine], t.astype(np.int64)[mine], zc)
+    if zcap in (0, 64):
+        assert int(m_str.sum()) > 0
+    if zcap >= 2048 or (zcap == 64 and not groups):            # (with groups on, the bands a 64-byte window can hold are the group classes')
+        assert int(m_win.sum()) > 0
+    ctx = _ctx_with_reads(tmp_path, g, reads)
+    try:
+        ctx.set_tuning("gcig_zcap", zcap)
+        res, cig, ms = ctx.global_batch_host(jobs)
+        got_cls = list(ctx.timings().gcig_class_jobs)
+    finally:
+        ctx.close()
+    print("gcig_zcap=%d groups=%d: gcig_class_jobs %s, k_gcig_t jobs in LDS / window / global %d / %d / %d" % (zcap, groups, got_cls, m_lds.sum(), m_win.sum(), m_str.sum()))
+    assert got_cls == _class_counts(cls)
+    assert got_cls[2] > 0 and (groups or got_cls[2] == jobs.shape[0])
+    assert np.array_equal(res["score"], G["score"])
+    assert np.array_equal(res["n_cigar"], G["n_cigar"])
+    assert np.array_equal(res["cigar_off"], np.concatenate([[0], np.cumsum(G["n_cigar"])])[:-1])
+    assert np.array_equal(cig, G["cigars"])
+
+
+@pytest.mark.parametrize("zcap", sorted(_ZCAP_SPLIT))
+def test_every_matrix_storage_mode_gives_the_golden_gen_cigar_results(tmp_path, zcap):
+    """The same for meme_gen_cigar_batch_host: NM and MD are read off the operations the walk wrote."""
+    g, reads, calls = gencig_workload()
+    G = np.load(os.path.join(GOLDEN, "gencig_golden.npz"))
+    off = np.concatenate([[0], np.cumsum(G["n_cigar"])])
+    mds = G["md"].tobytes().split(b"\0")
+    want = [(int(G["score"][k]), G["cigars"][off[k]:off[k + 1]], int(G["nm"][k]), mds[k]) for k in range(calls.shape[0])]
+    groups = _groups_on()
+    q, t = calls["qlen"], calls["tlen"]
+    w = _cjob_band(q, t, calls["w_"])
+    zc, _, cls, n_col = _plan(q, t, w, groups, zcap)
+    mine = cls == 2
+    assert zc == zcap and mine.sum() > 0 and (cls == 3).sum() > 0
+    m_lds, m_win, m_str, rows = _walks(n_col[mine], t.astype(np.int64)[mine], zc)
+    if zcap in (0, 64):
+        assert int(m_str.sum()) > 0
+    if zcap == 64 and not groups:
+        assert int((rows[m_win] == 2).sum()) > 0
+    if zcap >= 2048:
+        assert int(m_win.sum()) > 0 and (groups or int(m_lds.sum()) > 0)    # (with groups on, the small matrices are mostly the group classes')
+    ctx = _ctx_with_reads(tmp_path, g, reads)
+    try:
+        ctx.set_tuning("gcig_zcap", zcap)
+        res, cig, md, ms = ctx.gen_cigar_batch_host(calls)
+        got_cls = list(ctx.timings().gcig_class_jobs)
+    finally:
+        ctx.close()
+    print("gen_cigar gcig_zcap=%d groups=%d: gcig_class_jobs %s, k_gcig_t jobs in LDS / window / global %d / %d / %d" % (zcap, groups, got_cls, m_lds.sum(), m_win.sum(), m_str.sum()))
+    assert got_cls == _class_counts(cls)
+    assert got_cls[2] > 0 and (groups or got_cls[2] == int((w >= 0).sum()))
+    _check_calls(res, cig, md, want)
+
+
+def _check_global(res, cig, jobs, seqs, pen):
+    a, b, od, ed, oi, ei = pen
+    for k, (J, (q, t)) in enumerate(zip(jobs, seqs)):
+        sc, cg = O.ksw_global2(q, t, int(J["w"]), a, b, od, ed, oi, ei)
+        o0 = int(res["cigar_off"][k])
+        assert sc == int(res["score"][k]) and np.array_equal(cg, cig[o0:o0 + int(res["n_cigar"][k])]), (k, pen)
+
+
+def test_short_reads_take_the_whole_matrix_mode_by_default(tmp_path):
+    """Reads of 40-150 bases -- production's commonest class: the longest target x 33 columns fits 8 192 bytes, so gcig_plan keeps 8 192 bytes per job WITHOUT any
+    key (every other test of this file has targets of 290 bases and gets 2 048)."""
+    g, reads, jobs, seqs = gcig_workload(n=600, seed=301, read_len=(40, 151))
+    assert jobs.shape[0] == 800 and int(jobs["tlen"].max()) * 33 <= _Z_LDS_CAP
+    groups = _groups_on()
+    zc, _, cls, n_col = _plan(jobs["qlen"], jobs["tlen"], jobs["w"], groups)
+    mine = cls == 2
+    m_lds, m_win, m_str, _ = _walks(n_col[mine], jobs["tlen"].astype(np.int64)[mine], zc)
+    assert zc == _Z_LDS_CAP and int(m_lds.sum()) > 0 and int(m_win.sum()) > 0 and int(m_str.sum()) == 0
+    ctx = _ctx_with_reads(tmp_path, g, reads)
+    try:
+        for pen in ((1, 4, 6, 1, 6, 1), (2, 3, 4, 2, 7, 1)):
+            a, b, od, ed, oi, ei = pen
+            res, cig, _ = ctx.global_batch_host(jobs, hipapi.BswOpt(od, ed, oi, ei, 100, 5, a, b))
+            assert list(ctx.timings().gcig_class_jobs) == _class_counts(cls)
+            _check_global(res, cig, jobs, seqs, pen)
+    finally:
+        ctx.close()
+    g, reads, calls = gencig_workload(n=600, seed=303, read_len=(40, 151))
+    assert int(calls["tlen"].max()) * 33 <= _Z_LDS_CAP
+    w = _cjob_band(calls["qlen"], calls["tlen"], calls["w_"])
+    zc, _, cls, _ = _plan(calls["qlen"], calls["tlen"], w, groups)
+    assert zc == _Z_LDS_CAP and (cls == 2).sum() > 0
+    text = hipapi.fwd_rc_text(g)
+    (tmp_path / "calls").mkdir()                                   # (another genome: an index of its own)
+    ctx = _ctx_with_reads(tmp_path / "calls", g, reads)
+    try:
+        res, cig, md, _ = ctx.gen_cigar_batch_host(calls)
+        assert list(ctx.timings().gcig_class_jobs) == _class_counts(cls)
+        want = [O.gen_cigar2(text, g.shape[0], reads[int(J["read"])][int(J["qb"]):int(J["qb"]) + int(J["qlen"])], int(J["rb"]), int(J["rb"]) + int(J["tlen"]), int(J["w_"]))
+                for J in calls]
+        _check_calls(res, cig, md, want)
+    finally:
+        ctx.close()
+
+
+def test_reads_of_251_to_500_bases(tmp_path):
+    """Seeding admits reads of 500 bases; the other tests of this file stop at 250.  Bands from 1 to 600 (never below |tlen - qlen| + 3, as the workload does)."""
+    bands = (1, 3, 10, 30, 100, 200, 400, 600)
+    g, reads, jobs, seqs = gcig_workload(n=300, seed=311, read_len=(251, 501), bands=bands)
+    assert jobs.shape[0] == 400 and int(jobs["qlen"].min()) > 235 and int(jobs["qlen"].max()) > 490 and int(jobs["w"].max()) == 600
+    groups = _groups_on()
+    zc, _, cls, _ = _plan(jobs["qlen"], jobs["tlen"], jobs["w"], groups)
+    assert zc == _Z_LDS_WINDOW and (cls == 2).sum() > 0
+    ctx = _ctx_with_reads(tmp_path, g, reads)
+    try:
+        res, cig, _ = ctx.global_batch_host(jobs)
+        assert list(ctx.timings().gcig_class_jobs) == _class_counts(cls)
+        _check_global(res, cig, jobs, seqs, (1, 4, 6, 1, 6, 1))
+    finally:
+        ctx.close()
+    g, reads, calls = gencig_workload(n=300, seed=313, read_len=(251, 501), bands=(0,) + bands)
+    text = hipapi.fwd_rc_text(g)
+    w = _cjob_band(calls["qlen"], calls["tlen"], calls["w_"])
+    _, _, cls, _ = _plan(calls["qlen"], calls["tlen"], w, groups)
+    (tmp_path / "calls").mkdir()
+    ctx = _ctx_with_reads(tmp_path / "calls", g, reads)
+    try:
+        res, cig, md, _ = ctx.gen_cigar_batch_host(calls)
+        assert list(ctx.timings().gcig_class_jobs) == _class_counts(cls)
+        want = [O.gen_cigar2(text, g.shape[0], reads[int(J["read"])][int(J["qb"]):int(J["qb"]) + int(J["qlen"])], int(J["rb"]), int(J["rb"]) + int(J["tlen"]), int(J["w_"]))
+                for J in calls]
+        assert all(x is not None for x in want)
+        _check_calls(res, cig, md, want)
+    finally:
+        ctx.close()
+
+
+def test_one_long_target_switches_a_group_class_off_for_the_batch(tmp_path):
+    """The group classes' LDS is sized by the batch's longest query and target (grp_lds against GCIG_GRP's lds_max): one job of a 500-base read against a
+    1 300-base target -- admissible: the entry points take targets up to 65 535 bases inside the text, a band of at least |tlen - qlen| -- among 300 short
+    ones leaves k_gcig_grp<16> without a matrix, and its jobs go to the 32-lane class.  Every job against the oracle."""
+    g, reads, jobs, seqs = gcig_workload(n=225, seed=321, read_len=(40, 151), bands=(1, 3, 5, 7, 10, 30))
+    assert jobs.shape[0] == 300
+    rng = np.random.default_rng(5)
+    text = hipapi.fwd_rc_text(g)
+    big = rng.integers(0, 4, size=500).astype(np.uint8)
+    rb, tl = 20_000, 1300
+    big[:400] = text[rb + 100:rb + 500]                             # (related to its target: a real alignment with a long deletion at its end)
+    reads = reads + [big]
+    out = np.zeros(1, hipapi.GJOB)
+    out[0] = (rb, len(reads) - 1, 0, 500, tl, tl - 500 + 3, 0)
+    at = 137
+    jobs = np.concatenate([jobs[:at], out, jobs[at:]])
+    seqs = seqs[:at] + [(big.copy(), text[rb:rb + tl].copy())] + seqs[at:]
+    _, z_without, cls_without, _ = _plan(np.delete(jobs["qlen"], at), np.delete(jobs["tlen"], at), np.delete(jobs["w"], at), True)
+    zc, z_with, cls, _ = _plan(jobs["qlen"], jobs["tlen"], jobs["w"], _groups_on())
+    _, z_grp, cls_grp, _ = _plan(jobs["qlen"], jobs["tlen"], jobs["w"], True)
+    assert all(z > 0 for z in z_without) and (cls_without == 0).sum() > 50
+    assert z_grp[0] == 0 and z_grp[1] > 0 and z_grp[2] > 0 and (cls_grp == 0).sum() == 0 and (cls_grp == 1).sum() > 50     # the 16-lane class is off, its jobs are the 32-lane class's
+    ctx = _ctx_with_reads(tmp_path, g, reads)
+    try:
+        res, cig, _ = ctx.global_batch_host(jobs)
+        assert list(ctx.timings().gcig_class_jobs) == _class_counts(cls)
+        _check_global(res, cig, jobs, seqs, (1, 4, 6, 1, 6, 1))
+        calls = np.zeros(jobs.shape[0], hipapi.CJOB)
+        for f in ("rb", "read", "qb", "qlen", "tlen"):
+            calls[f] = jobs[f]
+        calls["w_"] = jobs["w"]
+        res, cig, md, _ = ctx.gen_cigar_batch_host(calls)
+        wc = _cjob_band(calls["qlen"], calls["tlen"], calls["w_"])
+        assert list(ctx.timings().gcig_class_jobs) == _class_counts(_plan(calls["qlen"], calls["tlen"], wc, _groups_on())[2])
+        want = [O.gen_cigar2(text, g.shape[0], reads[int(J["read"])][int(J["qb"]):int(J["qb"]) + int(J["qlen"])], int(J["rb"]), int(J["rb"]) + int(J["tlen"]), int(J["w_"]))
+                for J in calls]
+        assert all(x is not None for x in want)
+        _check_calls(res, cig, md, want)
+    finally:
+        ctx.close()
+
+
+def test_max_batch_refuses_more_jobs_and_takes_that_many(tmp_path):
+    """Tuning "max_batch" (what the bound aligner sets from its memory budget): both entry points refuse 11 jobs with MEME_E_CAPACITY -- the caller then feeds
+    pieces -- and give for 10 what an unrestricted ctx gives."""
+    g, reads, jobs, _ = gcig_workload(n=12, seed=331)
+    _, _, calls = gencig_workload(n=12, seed=331)
+    assert jobs.shape[0] >= 11 and calls.shape[0] >= 11
+    free = _ctx_with_reads(tmp_path, g, reads)
+    ctx = _ctx_with_reads(tmp_path, g, reads)
+    try:
+        ctx.set_tuning("max_batch", 10)
+        with pytest.raises(hipapi.MemeError, match="exceed the ctx's"):
+            ctx.global_batch_host(jobs[:11])
+        with pytest.raises(hipapi.MemeError, match="exceed the ctx's"):
+            ctx.gen_cigar_batch_host(calls[:11])
+        a, b = ctx.global_batch_host(jobs[:10]), free.global_batch_host(jobs[:10])
+        assert hipapi.records_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[0].shape[0] == 10
+        a, b = ctx.gen_cigar_batch_host(calls[:10]), free.gen_cigar_batch_host(calls[:10])
+        assert hipapi.records_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]) and a[0].shape[0] == 10
+    finally:
+        ctx.close()
+        free.close()

@@ -337,3 +337,70 @@ def test_plcp_table_equals_definition(tmp_path):
     bad = np.nonzero(got != plcp_by_pos)[0]
     assert bad.size == 0, (int(bad[0]), int(got[bad[0]]), int(plcp_by_pos[bad[0]]))
     assert (got == 255).sum() > 500 and (got < 30).sum() > n // 2
+
+
+# ---- persistent grids that go round: with seed_blocks = 1 / 3 (or one workgroup per CU) a group of k_seed<G> takes dozens of reads in sequence off the
+# ---- ticket counter, where the default grid and a test-sized batch give it one ----------------------------------------------------------------------------
+_mixed = {}
+
+
+def _mixed_length_batch(g1):
+    """~1 500 reads of 19-500 bases off the g1 genome, every number of 32-base words the packer lays out (1-16) among them, 5 % with N, + 40 reads shorter
+    than min_seed_len, shuffled; and the oracle's dump of them (once per module run)."""
+    if not _mixed:
+        idx = O.load_index_files(g1)
+        g = idx.text[:idx.text.shape[0] // 2]
+        rng = np.random.default_rng(901)
+        n = 1500
+        full, _, _ = synth.make_reads(g, n, 500, seed=902, sub_rate=0.02, indel_rate=0.003, n_frac=0.0)
+        lens = rng.integers(19, 501, size=n)
+        lens[:32] = [max(19, 32 * c - 31) for c in range(1, 17)] + [min(500, 32 * c) for c in range(1, 17)]
+        lens = np.concatenate([lens, rng.integers(1, 19, size=40)])
+        full = np.concatenate([full, full[:40]])
+        order = rng.permutation(lens.shape[0])
+        reads = []
+        for k in order:
+            r = full[k, :lens[k]].copy()
+            if rng.random() < 0.05:
+                r[rng.integers(0, r.shape[0], size=int(rng.integers(1, 4)))] = 4
+            reads.append(r)
+        off = np.zeros(len(reads) + 1, np.int64)
+        off[1:] = np.cumsum([r.shape[0] for r in reads])
+        flat = np.concatenate(reads)
+        sm, ns, hits, nh, _ = O.seed_batch(idx, flat, off, smem_cap=1024, hit_cap=1 << 13, threads=0)
+        _mixed.update(reads=flat, off=off, want=O.format_seed_dump(sm, ns, hits))
+    return _mixed["reads"], _mixed["off"], _mixed["want"]
+
+
+@pytest.mark.parametrize("lanes", [1, 4, 32])
+@pytest.mark.parametrize("key,value", [("seed_blocks", 1), ("seed_blocks", 3), ("seed_blocks_per_cu", 1)])
+def test_small_grids_hand_every_group_many_reads(g1, key, value, lanes):
+    """One and three workgroups (and one per CU) for the golden read sets and a mixed-length batch: a group runs through 6-200 reads in turn -- its state
+    machine, its LDS ring and the wavefront's ticket chunk carry over from read to read, groups leave while others still work, and with one lane per read a
+    wavefront's 64 groups draw from a ticket chunk of 32.  With re-seeding in and off the search kernel, and with 8 SMEM slots (the overflow tiers run from the
+    same small grid)."""
+    reads, off, want = _mixed_length_batch(g1)
+    n = off.shape[0] - 1
+    lens = np.diff(off)
+    assert set(((lens[lens >= 19] + 31) // 32).tolist()) == set(range(1, 17)) and (lens < 19).sum() == 40 and lens.max() == 500
+    has_n = np.array([(reads[off[r]:off[r + 1]] > 3).any() for r in range(n)])
+    assert 0.03 * n < has_n.sum() < 0.08 * n
+    groups = 256 // lanes
+    if (key, value) == ("seed_blocks", 1):
+        assert n // groups >= (6 if lanes == 1 else 20)            # reads per group, in sequence (a workgroup is 256 lanes)
+    c = hipapi.Context(0)
+    try:
+        c.load_index_files(g1)
+        c.set_tuning("group_lanes", lanes)
+        c.set_tuning(key, value)
+        for defer, cap in ((1, 128), (0, 128), (1, 8)):
+            c.set_tuning("seed_defer", defer)
+            c.set_tuning("smem_cap", cap)
+            for length in (150, 250, 60, 25):
+                r, o = read_fastq_codes(os.path.join(GOLDEN, "g1_reads_%d.fq" % length))
+                assert _gpu_dump(c, r, o) == open(os.path.join(GOLDEN, "g1_seeds_%d.txt" % length)).read(), (length, defer, cap)
+            assert _gpu_dump(c, reads, off) == want, (defer, cap)
+            if cap == 8:
+                assert c.timings().seed_launches >= 2
+    finally:
+        c.close()
