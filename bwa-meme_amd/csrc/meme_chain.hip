@@ -8,10 +8,15 @@
 //   k_chain_wave  one wavefront per read, the reference's B-tree (klib kbtree.h, t = 5) node for node: reads that put two chains on ONE
 //                 position (then the tree's shape decides their order and which one a query finds) and reads beyond 1 024 chains
 // What the reference sorts with klib's introsort is sorted by the same sequence of comparisons and swaps in every tier, because chains
-// of equal weight keep whatever order that algorithm leaves them in and the filter that follows depends on it.
+// of equal weight keep whatever order that algorithm leaves them in and the filter that follows depends on it: the sequential sort is
+// written once, in meme_ksort.h (the lane tier and the B-tree tier run it whole, the LDS tier its comb-sort fallback; that tier's partition
+// and closing rank are wave-parallel).  The rules of the reference a hit, a chain weight or a pair of chains is judged by -- test_and_merge,
+// mem_chain_weight's coverage, mem_chain_flt's overlap test, the SMEM order, frac_rep, max_occ, max_chain_extend -- are written once as well,
+// on plain values, in meme_chain_rules.h; a tier keeps only its own storage and control flow.  Both headers compile on the host.
 #include <string.h>
 #include <algorithm>
 
+#include "meme_chain_rules.h"
 #include "meme_common.h"
 
 namespace {
@@ -70,106 +75,39 @@ template <typename T> struct SPtr {
     __device__ T* operator->() const { return p; }
     __device__ T& operator[](int i) const { return p[(i64)i * 64]; }
     __device__ SPtr operator+(int i) const { return SPtr{p + (i64)i * 64}; }
-    __device__ SPtr operator-(int i) const { return SPtr{p - (i64)i * 64}; }
-    __device__ int operator-(SPtr o) const { return (int)((p - o.p) >> 6); }
-    __device__ SPtr& operator++() { p += 64; return *this; }
-    __device__ SPtr& operator--() { p -= 64; return *this; }
-    __device__ bool operator<(SPtr o) const { return p < o.p; }
-    __device__ bool operator<=(SPtr o) const { return p <= o.p; }
-    __device__ bool operator>(SPtr o) const { return p > o.p; }
-    __device__ bool operator==(SPtr o) const { return p == o.p; }
-    __device__ bool operator!=(SPtr o) const { return p != o.p; }
+    __device__ T get(int i) const { return p[(i64)i * 64]; }                 // (the array form meme_ksort.h sorts through)
+    __device__ void set(int i, const T& v) const { p[(i64)i * 64] = v; }
 };
 typedef SPtr<DChain> ChP;
 typedef SPtr<DSeed> SdP;
 
 __device__ inline int chain_weight(const DChain& c, SdP row) {   // mem_chain_weight, src/bwamem.cpp:522-541
-    i64 end = 0;
-    int w = 0;
-    for (int j = 0; j < c.n; ++j) {
-        const DSeed s = row[j];
-        if (s.qbeg >= end) w += s.len;
-        else if (s.qbeg + s.len > end) w += (int)(s.qbeg + s.len - end);
-        end = end > s.qbeg + s.len ? end : s.qbeg + s.len;
-    }
-    const int tmp = w;
-    w = 0; end = 0;
-    for (int j = 0; j < c.n; ++j) {
-        const DSeed s = row[j];
-        if (s.rbeg >= end) w += s.len;
-        else if (s.rbeg + s.len > end) w += (int)(s.rbeg + s.len - end);
-        end = end > s.rbeg + s.len ? end : s.rbeg + s.len;
-    }
-    w = w < tmp ? w : tmp;
-    return w < 1 << 30 ? w : (1 << 30) - 1;
+    i64 q_end = 0, r_end = 0;
+    int wq = 0, wr = 0;
+    for (int j = 0; j < c.n; ++j) { const DSeed s = row[j]; cover_step(wq, q_end, (i64)s.qbeg, s.len); cover_step(wr, r_end, s.rbeg, s.len); }
+    return chain_weight_of(wq, wr);
 }
 
-#define FLT_LT(a_, b_) ((a_).w > (b_).w)                                 // flt_lt, src/bwamem.cpp:80
-__device__ inline void swap_chain(DChain& a, DChain& b) { const DChain t = a; a = b; b = t; }
-
-// ks_introsort (klib ksort.h), restated: two elements are compared and swapped; otherwise quicksort around the median of first /
-// middle / last with an explicit stack, sub-ranges of at most 16 elements are left to the final insertion sort, comb sort takes
-// over when the depth budget is spent.  (Up to 16 elements this is ONE partition pass over the whole array + insertion sort.)
-__device__ inline void insert_sort(ChP s, ChP t) {
-    for (ChP i = s + 1; i < t; ++i)
-        for (ChP j = i; j > s && FLT_LT(*j, *(j - 1)); --j) swap_chain(*j, *(j - 1));
-}
-__device__ void comb_sort(int n, ChP a) {
-    const double shrink = 1.2473309501039786540366528676643;
-    bool do_swap;
-    int gap = n;
-    do {
-        if (gap > 2) { gap = (int)(gap / shrink); if (gap == 9 || gap == 10) gap = 11; }
-        do_swap = false;
-        for (ChP i = a; i < a + (n - gap); ++i) { ChP j = i + gap; if (FLT_LT(*j, *i)) { swap_chain(*i, *j); do_swap = true; } }
-    } while (do_swap || gap > 2);
-    if (gap != 1) insert_sort(a, a + n);
-}
-__device__ void sort_by_weight(ChP a, int n) {
-    if (n < 1) return;
-    if (n == 2) { if (FLT_LT(a[1], a[0])) swap_chain(a[0], a[1]); return; }
-    struct { ChP left, right; int depth; } stack[40], *top = stack;
-    int d;
-    for (d = 2; (1 << d) < n; ++d) {}
-    ChP s = a, t = a + (n - 1);
-    d <<= 1;
-    for (;;) {
-        if (s < t) {
-            if (--d == 0) { comb_sort((t - s) + 1, s); t = s; continue; }
-            ChP i = s, j = t, k = i + (((j - i) >> 1) + 1);
-            if (FLT_LT(*k, *i)) { if (FLT_LT(*k, *j)) k = j; }
-            else k = FLT_LT(*j, *i) ? i : j;
-            const DChain rp = *k;
-            if (k != t) swap_chain(*k, *t);
-            for (;;) {
-                do ++i; while (FLT_LT(*i, rp));
-                do --j; while (i <= j && FLT_LT(rp, *j));
-                if (j <= i) break;
-                swap_chain(*i, *j);
-            }
-            swap_chain(*i, *t);
-            if (i - s > t - i) {
-                if (i - s > 16) { top->left = s; top->right = i - 1; top->depth = d; ++top; }
-                s = t - i > 16 ? i + 1 : t;
-            } else {
-                if (t - i > 16) { top->left = i + 1; top->right = t; top->depth = d; ++top; }
-                t = i - s > 16 ? i - 1 : s;
-            }
-        } else {
-            if (top == stack) { insert_sort(a, a + n); return; }
-            --top; s = top->left; t = top->right; d = top->depth;
-        }
-    }
+struct ByChainWeight { __device__ bool operator()(const DChain& a, const DChain& b) const { return a.w > b.w; } };   // flt_lt, src/bwamem.cpp:80
+// ks_introsort pushes a range of more than 16 elements only: the lane tier's 16 chains are one partition pass + insertion sort, without a stack
+struct KsNoStack {
+    __device__ void push(int, int, int) {}
+    __device__ bool pop(int&, int&, int&) { return false; }
+};
+// bns_intv2rid searches the contig offsets twice per hit: a block keeps them in LDS, out of the dependent-load chain, when the reference has few enough
+constexpr int CONTIG_LDS = 256;
+__device__ __forceinline__ void contigs_to_lds(ChainArgs& A, i64* lds) {
+    if (A.n_contigs > CONTIG_LDS) return;
+    for (int i = threadIdx.x; i < A.n_contigs; i += 64) lds[i] = A.contig_off[i];
+    __syncthreads();
+    A.contig_off = lds;
 }
 
 template <int CC, int SC>
 __global__ void __launch_bounds__(64) k_chain(ChainArgs A) {
-    __shared__ i64 lds_contig1[256];                 // bns_intv2rid searches the contig offsets twice per hit: keep them out of the dependent-load chain
-    if (A.n_contigs <= 256) {
-        for (int i = threadIdx.x; i < A.n_contigs; i += 64) lds_contig1[i] = A.contig_off[i];
-        __syncthreads();
-        A.contig_off = lds_contig1;
-    }
+    static_assert(CC <= 17, "KsNoStack: no range of the sort may have more than 16 elements beside its pivot");
+    __shared__ i64 lds_contig1[CONTIG_LDS];
+    contigs_to_lds(A, lds_contig1);
     const i64 tid = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (tid >= A.nreads) return;
     const i64 r = tid;
@@ -199,22 +137,17 @@ __global__ void __launch_bounds__(64) k_chain(ChainArgs A) {
             int bi = -1, bs = 0, be = 0;
             for (int i = 0; i < ns; ++i) {
                 const int s = sm[i].start, en = sm[i].end;
-                const bool after = s > ps || (s == ps && (en > pe || (en == pe && i > pi)));
-                if (!after) continue;
-                if (bi < 0 || s < bs || (s == bs && (en < be || (en == be && i < bi)))) { bi = i; bs = s; be = en; }
+                if (!smem_before(ps, pe, pi, s, en, i)) continue;
+                if (bi < 0 || smem_before(s, en, i, bs, be, bi)) { bi = i; bs = s; be = en; }
             }
             ps = bs; pe = be; pi = bi;
             const meme_mem_tl p = sm[bi];
-            if (p.hitcount > o.max_occ) {
-                if (p.start > e) { l_rep += e - b; b = p.start; e = p.end; }
-                else e = e > p.end ? e : p.end;
-            }
+            if (p.hitcount > o.max_occ) rep_span_step(b, e, l_rep, p.start, p.end);
             const int slen = p.end - p.start;
-            const int step = p.hitcount > o.max_occ ? p.hitcount / o.max_occ : 1;
-            int count = 0;
-            for (i64 k = 0; k < p.hitcount && count < o.max_occ; k += step, ++count) {
+            const int step = occ_step(p.hitcount, o.max_occ), cnt = occ_count(p.hitcount, step, o.max_occ);
+            for (int hi = 0; hi < cnt; ++hi) {
                 DSeed s;
-                s.rbeg = (i64)ht[p.hitbeg + k];
+                s.rbeg = (i64)ht[p.hitbeg + (i64)hi * step];
                 s.qbeg = p.start;
                 s.len = slen;
                 const int rid = intv2rid(A, s.rbeg, s.rbeg + s.len);
@@ -226,26 +159,18 @@ __global__ void __launch_bounds__(64) k_chain(ChainArgs A) {
                     while (lo_i < hi_i) { const int mid = (lo_i + hi_i) >> 1; if (ch[mid].pos <= s.rbeg) lo_i = mid + 1; else hi_i = mid; }
                     lower = lo_i - 1;
                 }
-                bool merged = false;
+                int out = 2;
                 if (lower >= 0) {                                         // test_and_merge, src/bwamem.cpp:450-492
                     DChain& c = ch[lower];
                     const SdP row = sd + c.row * SC;
                     const DSeed last = row[c.n - 1], first = row[0];
-                    const i64 qend = last.qbeg + last.len, rend = last.rbeg + last.len;
-                    if (rid == c.rid) {
-                        if (s.qbeg >= first.qbeg && s.qbeg + s.len <= qend && s.rbeg >= first.rbeg && s.rbeg + s.len <= rend) merged = true;
-                        else if ((last.rbeg < o.l_pac || first.rbeg < o.l_pac) && s.rbeg >= o.l_pac) merged = false;
-                        else {
-                            const i64 x = s.qbeg - last.qbeg, y = s.rbeg - last.rbeg;
-                            if (y >= 0 && x - y <= o.w && y - x <= o.w && x - last.len < o.max_chain_gap && y - last.len < o.max_chain_gap) {
-                                if (c.n == SC) { H.fallback = 1; break; }
-                                row[c.n++] = s;
-                                merged = true;
-                            }
-                        }
+                    out = merge_outcome(c.rid, first.rbeg, first.qbeg, last.rbeg, last.qbeg, last.len, s.rbeg, s.qbeg, s.len, rid, o);
+                    if (out == 1) {
+                        if (c.n == SC) { H.fallback = 1; break; }
+                        row[c.n++] = s;
                     }
                 }
-                if (!merged) {                                            // a new chain (:1172-1191)
+                if (out == 2) {                                           // a new chain (:1172-1191)
                     if (lower >= 0 && ch[lower].pos == s.rbeg) { H.fallback = 1; break; }   // equal B-tree keys: the tier with the B-tree decides
                     if (nc == CC) { H.fallback = 1; break; }
                     for (int i = nc; i > lower + 1; --i) ch[i] = ch[i - 1];
@@ -276,7 +201,8 @@ __global__ void __launch_bounds__(64) k_chain(ChainArgs A) {
         }
         if (n == 0) n = 1;
         if (n > 0) {
-            sort_by_weight(ch, n);
+            KsNoStack no_stack;
+            ks_introsort(ch, n, ByChainWeight(), no_stack);
             int kept_idx[CC];
             int nk = 0;
             ch[0].kept = 3;
@@ -285,35 +211,24 @@ __global__ void __launch_bounds__(64) k_chain(ChainArgs A) {
                 bool large_ovlp = false;
                 int k = 0;
                 const SdP ri = sd + ch[i].row * SC;
-                const int beg_i = ri[0].qbeg, end_i = ri[ch[i].n - 1].qbeg + ri[ch[i].n - 1].len;
+                const int beg_i = ri[0].qbeg, end_i = ri[ch[i].n - 1].qbeg + ri[ch[i].n - 1].len, w_i = ch[i].w, alt_i = ch[i].is_alt;
                 for (; k < nk; ++k) {
                     const int j = kept_idx[k];
                     const SdP rj = sd + ch[j].row * SC;
                     const int beg_j = rj[0].qbeg, end_j = rj[ch[j].n - 1].qbeg + rj[ch[j].n - 1].len;
-                    const int b_max = beg_j > beg_i ? beg_j : beg_i;
-                    const int e_min = end_j < end_i ? end_j : end_i;
-                    if (e_min > b_max && (!ch[j].is_alt || ch[i].is_alt)) {
-                        const int li = end_i - beg_i, lj = end_j - beg_j;
-                        const int min_l = li < lj ? li : lj;
-                        if ((float)(e_min - b_max) >= (float)min_l * o.mask_level && min_l < o.max_chain_gap) {
-                            large_ovlp = true;
-                            if (ch[j].first < 0) ch[j].first = i;
-                            if ((float)ch[i].w < (float)ch[j].w * o.drop_ratio && ch[j].w - ch[i].w >= o.min_seed_len << 1) break;
-                        }
+                    const int ov = flt_overlap(beg_i, end_i, w_i, alt_i, beg_j, end_j, ch[j].w, ch[j].is_alt, o);
+                    if (ov) {
+                        large_ovlp = true;
+                        if (ch[j].first < 0) ch[j].first = i;
+                        if (ov & 2) break;
                     }
                 }
                 if (k == nk) { kept_idx[nk++] = i; ch[i].kept = large_ovlp ? 2 : 3; }
             }
             for (int i = 0; i < nk; ++i) { const int f = ch[kept_idx[i]].first; if (f >= 0) ch[f].kept = 1; }
-            int i = 0, k = 0;
-            for (; i < n; ++i) {                                          // at most max_chain_extend chains of kind 1 / 2
-                if (ch[i].kept == 0 || ch[i].kept == 3) continue;
-                if (++k >= o.max_chain_extend) break;
-            }
-            for (; i < n; ++i) if (ch[i].kept < 3) ch[i].kept = 0;
-            k = 0;
-            int nseeds = 0;
-            for (i = 0; i < n; ++i) if (ch[i].kept != 0) { const DChain c = ch[i]; ch[k++] = c; nseeds += c.n; }
+            cap_chain_extend([&](int i) -> short& { return ch[i].kept; }, n, o.max_chain_extend);
+            int k = 0, nseeds = 0;
+            for (int i = 0; i < n; ++i) if (ch[i].kept != 0) { const DChain c = ch[i]; ch[k++] = c; nseeds += c.n; }
             H.n_kept = k;
             H.n_seeds = nseeds;
         }
@@ -331,7 +246,6 @@ struct TNode { int n, internal; i64 key[T_MAXK]; int cid[T_MAXK]; int ptr[T_MAXK
 static_assert(sizeof(TNode) == 160, "TNode layout");
 // The kernel is built with 288 nodes (>= 1 150 chains) and 2 048 sort slots in LDS (63 KB per wavefront): a node or sort slot that spills to HBM
 // turns every step of the sequential parts from ~30 ns into ~1 us.
-constexpr int CONTIG_LDS = 256;    // contig offsets kept in LDS for bns_intv2rid (all of them when the reference has that few)
 
 struct C2 {                        // chain record (64 bytes), indexed by creation order
     i64 pos; int rid, n;
@@ -432,21 +346,39 @@ __device__ void tree_put(WTree& T, int id, i64 pos) {                        // 
     }
 }
 
-// what a hit does to the chain below it (test_and_merge, src/bwamem.cpp:450-492): 0 nothing (contained), 1 appended, 2 a new chain
+// what a hit does to the chain record below it (merge_outcome: 0 nothing, 1 appended, 2 a new chain)
 __device__ __forceinline__ int hit_outcome(const C2& c, i64 rbeg, int qbeg, int len, int rid, const meme_chain_opt& o) {
-    if (rid != c.rid) return 2;
-    const i64 qend = c.l_qbeg + c.l_len, rend = c.l_rbeg + c.l_len;
-    if (qbeg >= c.f_qbeg && qbeg + len <= qend && rbeg >= c.f_rbeg && rbeg + len <= rend) return 0;
-    if ((c.l_rbeg < o.l_pac || c.f_rbeg < o.l_pac) && rbeg >= o.l_pac) return 2;
-    const i64 x = qbeg - c.l_qbeg, y = rbeg - c.l_rbeg;
-    if (y >= 0 && x - y <= o.w && y - x <= o.w && x - c.l_len < o.max_chain_gap && y - c.l_len < o.max_chain_gap) return 1;
-    return 2;
+    return merge_outcome(c.rid, c.f_rbeg, c.f_qbeg, c.l_rbeg, c.l_qbeg, c.l_len, rbeg, qbeg, len, rid, o);
 }
 
 // every lane stores through its own view of shared state below ("uniform" code: all 64 lanes execute the same stores with the same
 // values), so a later load by any lane is an ordinary read-after-write of that lane; where ONE lane produces what others read, the
 // wavefront passes this fence
 __device__ __forceinline__ void wave_fence() { __threadfence(); __syncthreads(); }
+
+// the SMEMs of a read in (start, end, index) order by one wavefront: ia[rank] = index, the rank by counting
+__device__ __forceinline__ void smem_order(const meme_mem_tl* sm, int ns, int* ia, int lane) {
+    for (int i = lane; i < ns; i += 64) {
+        const int s = sm[i].start, e = sm[i].end;
+        int rank = 0;
+        for (int j = 0; j < ns; ++j) rank += smem_before(sm[j].start, sm[j].end, j, s, e, i) ? 1 : 0;
+        ia[rank] = i;
+    }
+    wave_fence();
+}
+// the header a wavefront tier leaves for its read t of list W (lane 0): done (fallback 0) or, the LDS tier, for the B-tree tier (3)
+__device__ __forceinline__ void wave_hdr(const ChainArgs& A, const WaveArgs& W, i64 t, i64 r, int tree_size, int n_kept, int n_seeds, int fallback) {
+    ReadHdr H;
+    H.tree_size = tree_size; H.n_kept = n_kept; H.n_seeds = n_seeds; H.fallback = fallback; H.slot = t | ((i64)W.set << 60); H.work = W.woff[t + 1] - W.woff[t];
+    A.hdr[r] = H;
+}
+
+// ks_introsort's stack in the B-tree tier's two int arrays in LDS: (left, right, depth) of entry k at x[k], i[k], x[k + 20]
+struct LdsSortStack {
+    int *x, *i, top;
+    __device__ void push(int l, int r, int d) { x[top] = l; i[top] = r; x[top + 20] = d; ++top; }
+    __device__ bool pop(int& l, int& r, int& d) { if (top == 0) return false; --top; l = x[top]; r = i[top]; d = x[top + 20]; return true; }
+};
 
 template <int NODE_LDS, int SRT_LDS>
 __global__ void __launch_bounds__(64) k_chain_wave(ChainArgs A, WaveArgs W, i64 t_first) {
@@ -458,11 +390,7 @@ __global__ void __launch_bounds__(64) k_chain_wave(ChainArgs A, WaveArgs W, i64 
     const i64 t = W.sub ? W.sub[blockIdx.x] : t_first + blockIdx.x;
     if (t >= W.nlist) return;
     const int lane = threadIdx.x;
-    if (A.n_contigs <= CONTIG_LDS) {                 // bns_intv2rid searches the contig offsets twice per hit
-        for (int i = lane; i < A.n_contigs; i += 64) lds_contig[i] = A.contig_off[i];
-        __syncthreads();
-        A.contig_off = lds_contig;
-    }
+    contigs_to_lds(A, lds_contig);
     const i64 r = W.list[t];
     const i64 base = W.woff[t];
     const meme_chain_opt& o = A.o;
@@ -483,30 +411,16 @@ __global__ void __launch_bounds__(64) k_chain_wave(ChainArgs A, WaveArgs W, i64 
     T.root = T.fresh();
     // ---- the SMEMs in (start, end) order (ks_introsort at src/bwamem.cpp:1397; equal keys describe the same substring, hence the
     //      same hits: their order cannot matter): rank of every SMEM by counting
-    for (int i = lane; i < ns; i += 64) {
-        const int s = sm[i].start, e = sm[i].end;
-        int rank = 0;
-        for (int j = 0; j < ns; ++j) {
-            const int sj = sm[j].start, ej = sm[j].end;
-            rank += (sj < s || (sj == s && (ej < e || (ej == e && j < i)))) ? 1 : 0;
-        }
-        ia[rank] = i;
-    }
-    wave_fence();
+    smem_order(sm, ns, ia, lane);
     // ---- mem_chain_Learned (src/bwamem.cpp:1149-1193)
     int nchain = 0, nseed = 0;
     bool has_dups = false;
     int fb = 0, fe = 0, l_rep = 0;
     for (int si = 0; si < ns; ++si) {
         const meme_mem_tl p = sm[ia[si]];
-        if (p.hitcount > o.max_occ) {                                     // frac_rep (:1140-1147)
-            if (p.start > fe) { l_rep += fe - fb; fb = p.start; fe = p.end; }
-            else fe = fe > p.end ? fe : p.end;
-        }
+        if (p.hitcount > o.max_occ) rep_span_step(fb, fe, l_rep, p.start, p.end);
         const int slen = p.end - p.start;
-        const int step = p.hitcount > o.max_occ ? p.hitcount / o.max_occ : 1;
-        int cnt = (p.hitcount + step - 1) / step;
-        if (cnt > o.max_occ) cnt = o.max_occ;
+        const int step = occ_step(p.hitcount, o.max_occ), cnt = occ_count(p.hitcount, step, o.max_occ);
         for (int cb = 0; cb < cnt; cb += 64) {
             const int c = cb + lane;
             bool valid = c < cnt;
@@ -583,24 +497,10 @@ __global__ void __launch_bounds__(64) k_chain_wave(ChainArgs A, WaveArgs W, i64 
     // ---- mem_chain_flt (src/bwamem.cpp:599-717): weights, one chain per lane
     for (int c = lane; c < nchain; c += 64) {
         const int id = ib[c];
-        i64 end = 0;
-        int w = 0;
-        for (int k = C[id].head; k >= 0; k = S[k].next) {
-            const S2 s = S[k];
-            if (s.qbeg >= end) w += s.len;
-            else if (s.qbeg + s.len > end) w += (int)(s.qbeg + s.len - end);
-            end = end > s.qbeg + s.len ? end : s.qbeg + s.len;
-        }
-        const int tmp = w;
-        w = 0; end = 0;
-        for (int k = C[id].head; k >= 0; k = S[k].next) {
-            const S2 s = S[k];
-            if (s.rbeg >= end) w += s.len;
-            else if (s.rbeg + s.len > end) w += (int)(s.rbeg + s.len - end);
-            end = end > s.rbeg + s.len ? end : s.rbeg + s.len;
-        }
-        w = w < tmp ? w : tmp;
-        C[id].w = w < 1 << 30 ? w : (1 << 30) - 1;
+        i64 q_end = 0, r_end = 0;
+        int wq = 0, wr = 0;
+        for (int k = C[id].head; k >= 0; k = S[k].next) { const S2 s = S[k]; cover_step(wq, q_end, (i64)s.qbeg, s.len); cover_step(wr, r_end, s.rbeg, s.len); }
+        C[id].w = chain_weight_of(wq, wr);
     }
     wave_fence();
     // chains of at least min_chain_weight, in tree order, as (weight, id) pairs
@@ -623,61 +523,8 @@ __global__ void __launch_bounds__(64) k_chain_wave(ChainArgs A, WaveArgs W, i64 
     int n_kept = 0, n_seeds = 0;
     if (n > 0) {
         // ks_introsort(mem_flt) by weight, descending: the same comparisons and swaps, so that chains of equal weight end up where klib leaves them
-#define W_LT(a_, b_) (((a_) >> 32) > ((b_) >> 32))
-#define W_SWAP(a_, b_) do { const u64 t_ = (a_); (a_) = (b_); (b_) = t_; } while (0)
-#define W_INSERT(s_, t_) do { for (u64* i_ = (s_) + 1; i_ < (t_); ++i_) for (u64* j_ = i_; j_ > (s_) && W_LT(*j_, *(j_ - 1)); --j_) W_SWAP(*j_, *(j_ - 1)); } while (0)
-        if (n == 2) { if (W_LT(srt[1], srt[0])) W_SWAP(srt[0], srt[1]); }
-        else if (n > 2) {
-            int d;
-            for (d = 2; (1 << d) < n; ++d) {}
-            d <<= 1;
-            u64 *s = srt, *tt = srt + (n - 1);
-            // explicit stack of (left, right, depth) in the int stack arrays: ranges as offsets into srt
-            int top = 0;
-            for (;;) {
-                if (s < tt) {
-                    if (--d == 0) {                                       // comb sort (ks_combsort)
-                        const int cn = (int)(tt - s) + 1;
-                        const double shrink = 1.2473309501039786540366528676643;
-                        bool do_swap;
-                        int gap = cn;
-                        do {
-                            if (gap > 2) { gap = (int)(gap / shrink); if (gap == 9 || gap == 10) gap = 11; }
-                            do_swap = false;
-                            for (u64* i = s; i < s + cn - gap; ++i) { u64* j = i + gap; if (W_LT(*j, *i)) { W_SWAP(*i, *j); do_swap = true; } }
-                        } while (do_swap || gap > 2);
-                        if (gap != 1) W_INSERT(s, s + cn);
-                        tt = s;
-                        continue;
-                    }
-                    u64 *i = s, *j = tt, *k = i + ((j - i) >> 1) + 1;
-                    if (W_LT(*k, *i)) { if (W_LT(*k, *j)) k = j; }
-                    else k = W_LT(*j, *i) ? i : j;
-                    const u64 rp = *k;
-                    if (k != tt) W_SWAP(*k, *tt);
-                    for (;;) {
-                        do ++i; while (W_LT(*i, rp));
-                        do --j; while (i <= j && W_LT(rp, *j));
-                        if (j <= i) break;
-                        W_SWAP(*i, *j);
-                    }
-                    W_SWAP(*i, *tt);
-                    if (i - s > tt - i) {
-                        if (i - s > 16) { stk_x[top] = (int)(s - srt); stk_i[top] = (int)(i - 1 - srt); stk_x[top + 20] = d; ++top; }
-                        s = tt - i > 16 ? i + 1 : tt;
-                    } else {
-                        if (tt - i > 16) { stk_x[top] = (int)(i + 1 - srt); stk_i[top] = (int)(tt - srt); stk_x[top + 20] = d; ++top; }
-                        tt = i - s > 16 ? i - 1 : s;
-                    }
-                } else {
-                    if (top == 0) { W_INSERT(srt, srt + n); break; }
-                    --top; s = srt + stk_x[top]; tt = srt + stk_i[top]; d = stk_x[top + 20];
-                }
-            }
-        }
-#undef W_LT
-#undef W_SWAP
-#undef W_INSERT
+        LdsSortStack stack{stk_x, stk_i, 0};
+        ks_introsort(KsPtr<u64>{srt}, n, [](u64 a, u64 b) { return (a >> 32) > (b >> 32); }, stack);
         // the filter's view of the sorted chains
         for (int i = lane; i < n; i += 64) {
             const int id = (int)(unsigned)srt[i];
@@ -703,16 +550,8 @@ __global__ void __launch_bounds__(64) k_chain_wave(ChainArgs A, WaveArgs W, i64 
                 if (in) {
                     const FRec fj = F[j];
                     first_j = fj.first;
-                    const int b_max = fj.beg > fi.beg ? fj.beg : fi.beg;
-                    const int e_min = fj.end < fi.end ? fj.end : fi.end;
-                    if (e_min > b_max && (!fj.is_alt || fi.is_alt)) {
-                        const int li = fi.end - fi.beg, lj = fj.end - fj.beg;
-                        const int min_l = li < lj ? li : lj;
-                        if ((float)(e_min - b_max) >= (float)min_l * o.mask_level && min_l < o.max_chain_gap) {
-                            lo = true;
-                            br = (float)fi.w < (float)fj.w * o.drop_ratio && fj.w - fi.w >= o.min_seed_len << 1;
-                        }
-                    }
+                    const int ov = flt_overlap(fi.beg, fi.end, fi.w, fi.is_alt, fj.beg, fj.end, fj.w, fj.is_alt, o);
+                    lo = ov & 1; br = ov & 2;
                 }
                 const u64 lom = __ballot(lo), brm = __ballot(br);
                 u64 upto = ~(u64)0;
@@ -724,32 +563,27 @@ __global__ void __launch_bounds__(64) k_chain_wave(ChainArgs A, WaveArgs W, i64 
         }
         for (int k = lane; k < nk; k += 64) { const int f = F[ia[k]].first; if (f >= 0) F[f].kept = 1; }
         wave_fence();
-        int i = 0, k = 0;
-        for (; i < n; ++i) {                                              // at most max_chain_extend chains of kind 1 / 2
-            const int kp = F[i].kept;
-            if (kp == 0 || kp == 3) continue;
-            if (++k >= o.max_chain_extend) break;
-        }
-        for (; i < n; ++i) if (F[i].kept < 3) F[i].kept = 0;
-        for (i = 0; i < n; ++i) {
+        cap_chain_extend([&](int i) -> int& { return F[i].kept; }, n, o.max_chain_extend);
+        for (int i = 0; i < n; ++i) {
             const FRec f = F[i];
             if (f.kept == 0) continue;
             F[n_kept++] = f;
             n_seeds += C[f.id].n;
         }
     }
-    if (lane == 0) {
-        ReadHdr H;
-        H.tree_size = nchain; H.n_kept = n_kept; H.n_seeds = n_seeds; H.fallback = 0; H.slot = t | ((i64)W.set << 60); H.work = W.woff[t + 1] - base;
-        A.hdr[r] = H;
-        A.frac_rep[r] = (float)l_rep / len;
-    }
+    if (lane == 0) { wave_hdr(A, W, t, r, nchain, n_kept, n_seeds, 0); A.frac_rep[r] = (float)l_rep / len; }
 }
 
 // klib's ks_introsort (src/ksort.h) by descending weight on (EW, EID)[0 .. n) in LDS, executed by one wavefront: every Hoare partition
 // step from the two lists of scan stops (ballots), the swaps in parallel, the closing insertion sort as a stable rank by counting
 // (tests/test_introsort_model.py checks this formulation against the sequential algorithm).  LIDX / RIDX: scratch of n ints each;
 // stk: 60 ints.  All lanes call it together.
+struct WId { int w, id; };
+struct WIdArrays {                                              // (weight, id) elements kept as two arrays: the form meme_ksort.h sorts through
+    int *w, *id;
+    __device__ WId get(int i) const { return WId{w[i], id[i]}; }
+    __device__ void set(int i, WId v) const { w[i] = v.w; id[i] = v.id; }
+};
 __device__ void wave_introsort_lds(int* EW, int* EID, int n, int* LIDX, int* RIDX, int* stk, int lane) {
     const u64 below = ((u64)1 << lane) - 1;
 #define L_SWAP(i_, j_) do { const int i__ = (i_), j__ = (j_); const int wi_ = EW[i__], di_ = EID[i__], wj_ = EW[j__], dj_ = EID[j__]; \
@@ -762,17 +596,8 @@ __device__ void wave_introsort_lds(int* EW, int* EID, int n, int* LIDX, int* RID
         int s = 0, tt = n - 1, top = 0;
         for (;;) {
             if (s < tt) {
-                if (--d == 0) {                               // ks_combsort, as written (rare: the depth budget is 2 log2 n)
-                    const int cnn = tt - s + 1;
-                    const double shrink = 1.2473309501039786540366528676643;
-                    bool do_swap;
-                    int gap = cnn;
-                    do {
-                        if (gap > 2) { gap = (int)(gap / shrink); if (gap == 9 || gap == 10) gap = 11; }
-                        do_swap = false;
-                        for (int i = s; i < s + cnn - gap; ++i) { const int j = i + gap; if (EW[j] > EW[i]) { L_SWAP(i, j); do_swap = true; } }
-                    } while (do_swap || gap > 2);
-                    if (gap != 1) for (int i = s + 1; i < s + cnn; ++i) for (int j = i; j > s && EW[j] > EW[j - 1]; --j) L_SWAP(j, j - 1);
+                if (--d == 0) {                               // ks_combsort, as written: every lane the whole of it (rare: the depth budget is 2 log2 n)
+                    ks_combsort(WIdArrays{EW, EID}, s, tt - s + 1, [](WId a, WId b) { return a.w > b.w; });
                     tt = s;
                     continue;
                 }
@@ -915,11 +740,7 @@ __global__ void __launch_bounds__(64) k_chain_lds(ChainArgs A, WaveArgs W) {
     if (t >= W.nlist) return;
     const int lane = threadIdx.x;
     const u64 below = ((u64)1 << lane) - 1;
-    if (A.n_contigs <= CONTIG_LDS) {
-        for (int i = lane; i < A.n_contigs; i += 64) lds_contig[i] = A.contig_off[i];
-        __syncthreads();
-        A.contig_off = lds_contig;
-    }
+    contigs_to_lds(A, lds_contig);
     PROF_T0;
     const i64 r = W.list[t];
     const i64 base = W.woff[t];
@@ -932,29 +753,31 @@ __global__ void __launch_bounds__(64) k_chain_lds(ChainArgs A, WaveArgs W) {
     S2* S = W.S + base;
     FRec* F = W.F + base;
     int* ia = W.ia + base;
-    for (int i = lane; i < ns; i += 64) {                       // SMEMs in (start, end) order (src/bwamem.cpp:1397)
-        const int s = sm[i].start, e = sm[i].end;
-        int rank = 0;
-        for (int j = 0; j < ns; ++j) {
-            const int sj = sm[j].start, ej = sm[j].end;
-            rank += (sj < s || (sj == s && (ej < e || (ej == e && j < i)))) ? 1 : 0;
-        }
-        ia[rank] = i;
-    }
-    wave_fence();
+    smem_order(sm, ns, ia, lane);
     PROF(8);
     int nchain = 0, nseed = 0, bail = 0;
     int fb = 0, fe = 0, l_rep = 0;
+    // chain c lives at position cpos = its first seed's; its last seed's is kept relative to that.  What the hit (rb, rid, qb, len) does to it (test_and_merge):
+    auto outcome = [&](int c, i64 cpos, i64 rb, int rid, int qb, int len) {
+        return merge_outcome(RID[c], cpos, FQB[c], cpos + LRB[c], LQB[c], LLN[c], rb, qb, len, rid, o);
+    };
+    auto append = [&](int c, i64 cpos, i64 rb, int qb, int len, int sid) {     // the hit, seed sid, becomes chain c's last; the two coverage sums take it in
+        const int rel = (int)(rb - cpos);
+        int wq = WQ[c], q_e = EQ[c], wr = WR[c], r_e = ER[c];
+        cover_step(wq, q_e, qb, len);
+        cover_step(wr, r_e, rel, len);
+        CN[c] += 1; LRB[c] = rel; LQB[c] = qb; LLN[c] = len; TAIL[c] = sid;
+        WQ[c] = wq; EQ[c] = q_e; WR[c] = wr; ER[c] = r_e;
+    };
+    auto open_chain = [&](int id, i64 rb, int rid, int qb, int len, int sid) {     // chain id of the one seed sid
+        s_pos[id] = rb; RID[id] = rid; CN[id] = 1; FQB[id] = qb; LRB[id] = 0; LQB[id] = qb; LLN[id] = len; TAIL[id] = sid;
+        WQ[id] = len; EQ[id] = qb + len; WR[id] = len; ER[id] = len;
+    };
     for (int si = 0; si < ns && !bail; ++si) {
         const meme_mem_tl p = sm[ia[si]];
-        if (p.hitcount > o.max_occ) {
-            if (p.start > fe) { l_rep += fe - fb; fb = p.start; fe = p.end; }
-            else fe = fe > p.end ? fe : p.end;
-        }
+        if (p.hitcount > o.max_occ) rep_span_step(fb, fe, l_rep, p.start, p.end);
         const int slen = p.end - p.start, qb = p.start;
-        const int step = p.hitcount > o.max_occ ? p.hitcount / o.max_occ : 1;
-        int cnt = (p.hitcount + step - 1) / step;
-        if (cnt > o.max_occ) cnt = o.max_occ;
+        const int step = occ_step(p.hitcount, o.max_occ), cnt = occ_count(p.hitcount, step, o.max_occ);
         for (int cb = 0; cb < cnt && !bail; cb += 64) {
             const int c = cb + lane;
             const bool have = c < cnt;
@@ -991,37 +814,18 @@ __global__ void __launch_bounds__(64) k_chain_lds(ChainArgs A, WaveArgs W) {
                     ow = (int)(M & 2047);
                     mp = M >> 11;
                 }
-                if (mp >= 0) {
-                    const int c_rid = RID[ow], c_fqb = FQB[ow], c_lrb = LRB[ow], c_lqb = LQB[ow], c_lln = LLN[ow];
-                    const i64 l_rbeg = mp + c_lrb;
-                    if (hr == c_rid) {                          // test_and_merge (:450-492)
-                        const i64 qend = c_lqb + c_lln, rend = l_rbeg + c_lln;
-                        if (qb >= c_fqb && qb + slen <= qend && rb >= mp && rb + slen <= rend) out = 0;
-                        else if ((l_rbeg < o.l_pac || mp < o.l_pac) && rb >= o.l_pac) out = 2;
-                        else {
-                            const i64 x = qb - c_lqb, y = rb - l_rbeg;
-                            if (y >= 0 && x - y <= o.w && y - x <= o.w && x - c_lln < o.max_chain_gap && y - c_lln < o.max_chain_gap) out = 1;
-                        }
-                    }
-                }
+                if (mp >= 0) out = outcome(ow, mp, rb, hr, qb, slen);
                 if (out == 0) continue;
                 const int sid = nseed++;
                 if (lane == 0) { S2 sn; sn.rbeg = rb; sn.qbeg = qb; sn.len = slen; sn.next = -1; sn.pad = 0; S[sid] = sn; }
                 if (out == 1) {                                 // (every lane stores the same values: later reads are the reader's own writes)
                     if (lane == 0) S[TAIL[ow]].next = sid;
-                    const int rel = (int)(rb - mp);
-                    CN[ow] += 1; LRB[ow] = rel; LQB[ow] = qb; LLN[ow] = slen; TAIL[ow] = sid;
-                    const int q_e = EQ[ow], r_e = ER[ow];
-                    if (qb >= q_e) WQ[ow] += slen; else if (qb + slen > q_e) WQ[ow] += qb + slen - q_e;
-                    EQ[ow] = q_e > qb + slen ? q_e : qb + slen;
-                    if (rel >= r_e) WR[ow] += slen; else if (rel + slen > r_e) WR[ow] += rel + slen - r_e;
-                    ER[ow] = r_e > rel + slen ? r_e : rel + slen;
+                    append(ow, mp, rb, qb, slen, sid);
                 } else {
                     if (mp == rb || nchain == N) { bail = 1; break; }
                     const int id = nchain++;
                     if (lane == 0) C[id].head = sid;
-                    s_pos[id] = rb; RID[id] = hr; CN[id] = 1; FQB[id] = qb; LRB[id] = 0; LQB[id] = qb; LLN[id] = slen; TAIL[id] = sid;
-                    WQ[id] = slen; EQ[id] = qb + slen; WR[id] = slen; ER[id] = slen;
+                    open_chain(id, rb, hr, qb, slen, sid);
                 }
             }
             };
@@ -1034,20 +838,7 @@ __global__ void __launch_bounds__(64) k_chain_lds(ChainArgs A, WaveArgs W) {
                 int bs = 0;
                 for (int s2 = 0; s2 < nchain; ++s2) { const i64 ps = s_pos[s2]; if (ps <= rbj && ps > bp) { bp = ps; bs = s2; } }
                 // 2. test_and_merge against it (:450-492)
-                int out = 2;
-                if (bp >= 0) {
-                    const int c_rid = RID[bs], c_fqb = FQB[bs], c_lrb = LRB[bs], c_lqb = LQB[bs], c_lln = LLN[bs];
-                    const i64 l_rbeg = bp + c_lrb;
-                    if (h_rid == c_rid) {
-                        const i64 qend = c_lqb + c_lln, rend = l_rbeg + c_lln;
-                        if (qb >= c_fqb && qb + slen <= qend && rbj >= bp && rbj + slen <= rend) out = 0;
-                        else if ((l_rbeg < o.l_pac || bp < o.l_pac) && rbj >= o.l_pac) out = 2;
-                        else {
-                            const i64 x = qb - c_lqb, y = rbj - l_rbeg;
-                            if (y >= 0 && x - y <= o.w && y - x <= o.w && x - c_lln < o.max_chain_gap && y - c_lln < o.max_chain_gap) out = 1;
-                        }
-                    }
-                }
+                int out = bp >= 0 ? outcome(bs, bp, rbj, h_rid, qb, slen) : 2;
                 // 3. in hit order: which outcomes stand
                 const bool mine = (rem >> lane) & 1;
                 i64 mp = bp;
@@ -1078,17 +869,10 @@ __global__ void __launch_bounds__(64) k_chain_lds(ChainArgs A, WaveArgs W) {
                 if (in && out != 0) { S2 sn; sn.rbeg = rbj; sn.qbeg = qb; sn.len = slen; sn.next = -1; sn.pad = 0; S[sid] = sn; }
                 if (in && out == 1) {
                     S[TAIL[bs]].next = sid;
-                    const int rel = (int)(rbj - bp);
-                    CN[bs] += 1; LRB[bs] = rel; LQB[bs] = qb; LLN[bs] = slen; TAIL[bs] = sid;
-                    const int q_e = EQ[bs], r_e = ER[bs];
-                    if (qb >= q_e) WQ[bs] += slen; else if (qb + slen > q_e) WQ[bs] += qb + slen - q_e;
-                    EQ[bs] = q_e > qb + slen ? q_e : qb + slen;
-                    if (rel >= r_e) WR[bs] += slen; else if (rel + slen > r_e) WR[bs] += rel + slen - r_e;
-                    ER[bs] = r_e > rel + slen ? r_e : rel + slen;
+                    append(bs, bp, rbj, qb, slen, sid);
                 } else if (in && out == 2) {
                     C[id].head = sid;
-                    s_pos[id] = rbj; RID[id] = h_rid; CN[id] = 1; FQB[id] = qb; LRB[id] = 0; LQB[id] = qb; LLN[id] = slen; TAIL[id] = sid;
-                    WQ[id] = slen; EQ[id] = qb + slen; WR[id] = slen; ER[id] = slen;
+                    open_chain(id, rbj, h_rid, qb, slen, sid);
                 }
                 nseed += __popcll(nzm); nchain += __popcll(newm);
                 rem &= ~com;
@@ -1107,14 +891,13 @@ __global__ void __launch_bounds__(64) k_chain_lds(ChainArgs A, WaveArgs W) {
     PROF(9);
     l_rep += fe - fb;
     if (bail) {
-        if (lane == 0) { ReadHdr H; H.tree_size = 0; H.n_kept = 0; H.n_seeds = 0; H.fallback = 3; H.slot = t | ((i64)W.set << 60); H.work = W.woff[t + 1] - base; A.hdr[r] = H; }
+        if (lane == 0) wave_hdr(A, W, t, r, 0, 0, 0, 3);
         return;
     }
     // ---- chain records for the pack kernel; weight, query end and ALT flag per chain
     __syncthreads();
     for (int s = lane; s < nchain; s += 64) {
-        int w = WQ[s] < WR[s] ? WQ[s] : WR[s];
-        w = w < 1 << 30 ? w : (1 << 30) - 1;
+        const int w = chain_weight_of(WQ[s], WR[s]);
         const int alt = A.contig_alt[RID[s]] ? 1 : 0;
         C2* c = &C[s];
         c->pos = s_pos[s]; c->rid = RID[s]; c->n = CN[s]; c->w = w; c->is_alt = (short)alt; c->tail = TAIL[s];
@@ -1158,17 +941,7 @@ __global__ void __launch_bounds__(64) k_chain_lds(ChainArgs A, WaveArgs W) {
                 int brk = -1;
                 {
                     bool lo = false, br = false;
-                    if (lane < i && kept0 != 0) {
-                        const int b_max = be0 > bi ? be0 : bi, e_min = ee0 < ei ? ee0 : ei;
-                        if (e_min > b_max && (!alt0 || ai)) {
-                            const int li = ei - bi, lj = ee0 - be0;
-                            const int min_l = li < lj ? li : lj;
-                            if ((float)(e_min - b_max) >= (float)min_l * o.mask_level && min_l < o.max_chain_gap) {
-                                lo = true;
-                                br = (float)wi < (float)we0 * o.drop_ratio && we0 - wi >= o.min_seed_len << 1;
-                            }
-                        }
-                    }
+                    if (lane < i && kept0 != 0) { const int ov = flt_overlap(bi, ei, wi, ai, be0, ee0, we0, alt0, o); lo = ov & 1; br = ov & 2; }
                     const u64 lom = __ballot(lo), brm = __ballot(br);
                     u64 upto = ~(u64)0;
                     if (brm) { const int kx = __builtin_ctzll(brm); brk = kx; upto = ((u64)2 << kx) - 1; }
@@ -1178,18 +951,7 @@ __global__ void __launch_bounds__(64) k_chain_lds(ChainArgs A, WaveArgs W) {
                 for (int cb = 64; cb < i && brk < 0; cb += 64) {
                     const int e = cb + lane;
                     bool lo = false, br = false;
-                    if (e < i && EKEPT[e] != 0) {
-                        const int be = EBEG[e], ee = EEND[e], we = EW[e];
-                        const int b_max = be > bi ? be : bi, e_min = ee < ei ? ee : ei;
-                        if (e_min > b_max && (!EALT[e] || ai)) {
-                            const int li = ei - bi, lj = ee - be;
-                            const int min_l = li < lj ? li : lj;
-                            if ((float)(e_min - b_max) >= (float)min_l * o.mask_level && min_l < o.max_chain_gap) {
-                                lo = true;
-                                br = (float)wi < (float)we * o.drop_ratio && we - wi >= o.min_seed_len << 1;
-                            }
-                        }
-                    }
+                    if (e < i && EKEPT[e] != 0) { const int ov = flt_overlap(bi, ei, wi, ai, EBEG[e], EEND[e], EW[e], EALT[e], o); lo = ov & 1; br = ov & 2; }
                     const u64 lom = __ballot(lo), brm = __ballot(br);
                     u64 upto = ~(u64)0;
                     if (brm) { const int kx = __builtin_ctzll(brm); brk = cb + kx; upto = ((u64)2 << kx) - 1; }
@@ -1211,15 +973,7 @@ __global__ void __launch_bounds__(64) k_chain_lds(ChainArgs A, WaveArgs W) {
         __syncthreads();
         int n12 = 0;                                                    // chains of kind 1 / 2: at most max_chain_extend of them are kept (default: no limit)
         for (int cb = 0; cb < n; cb += 64) { const int e = cb + lane; n12 += __popcll(__ballot(e < n && (EKEPT[e] == 1 || EKEPT[e] == 2))); }
-        if (n12 >= o.max_chain_extend) {
-            int i = 0, k = 0;
-            for (; i < n; ++i) {
-                const int kp = EKEPT[i];
-                if (kp == 0 || kp == 3) continue;
-                if (++k >= o.max_chain_extend) break;
-            }
-            for (; i < n; ++i) if (EKEPT[i] < 3) EKEPT[i] = 0;
-        }
+        if (n12 >= o.max_chain_extend) cap_chain_extend([&](int i) -> int& { return EKEPT[i]; }, n, o.max_chain_extend);
         int before = 0;
         for (int cb = 0; cb < n; cb += 64) {
             const int e = cb + lane;
@@ -1239,12 +993,7 @@ __global__ void __launch_bounds__(64) k_chain_lds(ChainArgs A, WaveArgs W) {
         n_kept = before;
     }
     PROF(14);
-    if (lane == 0) {
-        ReadHdr H;
-        H.tree_size = nchain; H.n_kept = n_kept; H.n_seeds = n_seeds; H.fallback = 0; H.slot = t | ((i64)W.set << 60); H.work = W.woff[t + 1] - base;
-        A.hdr[r] = H;
-        A.frac_rep[r] = (float)l_rep / len;
-    }
+    if (lane == 0) { wave_hdr(A, W, t, r, nchain, n_kept, n_seeds, 0); A.frac_rep[r] = (float)l_rep / len; }
 }
 
 // the kept chains and their seeds, densely packed in read order (from the scratch of the tier that finished the read)

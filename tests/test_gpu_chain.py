@@ -130,6 +130,53 @@ def _assert_dup_golden(R, G):
     assert np.array_equal(R["frac_rep"].view(np.uint32)[has], G["frac_rep_bits"][has])
 
 
+def _one_hit_chains(weights, spacing, dup):
+    """A read of len(weights) SMEMs of one hit each: SMEM i starts at query base i (2 i for 40 and fewer), is 19 + weights[i] long and hits position
+    1 000 + i * spacing, so that every hit opens a chain of its own and the chains in tree order weigh 19 + weights.  dup: one more SMEM far
+    behind them in the query whose hit lies ON chain 0's position and opens a second chain there."""
+    n, k = len(weights), 2 if len(weights) <= 40 else 1
+    sm = np.zeros(n + (1 if dup else 0), hipapi.MEM_TL)
+    sm["start"][:n] = k * np.arange(n); sm["end"][:n] = sm["start"][:n] + 19 + np.asarray(weights)
+    hits = (1000 + spacing * np.arange(n)).astype(np.uint64)
+    if dup:
+        sm["start"][n] = n + 65; sm["end"][n] = n + 90          # (chain 0's seed starts at 0: more than the band w = 100 behind it, so it cannot be appended)
+        hits = np.append(hits, hits[0])
+    sm["hitbeg"] = np.arange(sm.shape[0]); sm["hitcount"] = 1
+    return sm, hits
+
+
+def test_tied_monotone_weights_take_the_sort_fallback_in_both_wavefront_tiers():
+    """The comb-sort branch of the shared sort (bwa-meme_amd/csrc/meme_ksort.h) on the device: monotone chain weights full of ties spend klib's depth
+    budget, and where its comb sort leaves equal weights differs from a stable sort.  Read A of each pair has more chains than the lane tier
+    holds and is sorted by the LDS tier (wave_introsort_lds); read B also puts two chains on one position and is sorted by the B-tree tier
+    (k_chain_wave).  The lane tier never has more than 16 chains: the sort is one partition pass there, which the goldens cover."""
+    import test_introsort_model as M
+    pairs = [([(40 - i) // 2 for i in range(40)], 1000, 150), ([i // 2 for i in range(100)], 600, 250)]
+    for weights, _, _ in pairs:                                  # what the model makes of these weights (ids in tree order)
+        arr = [(19 + w, i) for i, w in enumerate(weights)]
+        M.COMB_CALLS[0] = 0
+        assert M.klib(arr) != M.stable(arr) and M.COMB_CALLS[0] > 0, len(weights)
+    reads = [_one_hit_chains(w, spacing, dup) for w, spacing, _ in pairs for dup in (False, True)]
+    read_len = np.array([rl for _, _, rl in pairs for _ in (0, 1)], np.int32)
+    smem_off = np.zeros(5, np.int64); hit_off = np.zeros(5, np.int64)
+    smem_off[1:] = np.cumsum([sm.shape[0] for sm, _ in reads]); hit_off[1:] = np.cumsum([h.shape[0] for _, h in reads])
+    smems = np.concatenate([sm for sm, _ in reads]); hits = np.concatenate([h for _, h in reads])
+    assert int(smems["end"].max()) <= 250 and int(smems["end"][:smem_off[2]].max()) <= 150
+    contig_off, contig_alt, oo = np.array([0, 70_000, 150_000], np.int64), np.array([0, 0, 1], np.uint8), O.default_chain_opt(200_000)
+    trees = [O.chain_read(sm, h, rl, contig_off, contig_alt, oo)[3] for (sm, h), rl in zip(reads, read_len)]
+    assert trees == [40, 41, 100, 101]
+    assert O.chain_read(reads[0][0], reads[0][1], 150, contig_off, contig_alt, oo)[0] == 40          # default options drop none of read A's chains
+    ctx = hipapi.Context(0)
+    try:
+        R = ctx.chain_batch_host(smems, smem_off, hits, hit_off, read_len, _contigs3(), hipapi.default_chain_opt(200_000))
+        tier3 = int(ctx.timings().chain_tier3_reads)
+    finally:
+        ctx.close()
+    assert R["n_fallback"] == 0 and list(R["tree_size"]) == trees
+    assert tier3 == 2 and R["n_tier2"] == 4                      # both B reads reached the B-tree tier, through the LDS tier that sorts the A reads
+    assert O.chain_compare_batch(smems, smem_off, hits, hit_off, read_len, contig_off, contig_alt, oo, R) == (0, -1)
+
+
 def _adversarial(n, seed):
     import chain_gen
     reads = chain_gen.workload(seed, n, l_pac=200_000)
