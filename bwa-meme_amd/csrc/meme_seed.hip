@@ -197,6 +197,7 @@ struct SeedRun {
     i64 n_todo = 0;                    // reads the last tier left to the next one
     float ms_total = 0.f, ms_reseed = 0.f;
     i64 launches = 0, searches = 0, windows = 0, lane_searches = 0;
+    unsigned long long h_early[SEED_CTRS];   // the early tier-1 launch's counters (n_early >= 0), read back together with tier 0's
 };
 
 // pack the reads: 2 bits/base, both strands, N masks (k_pack_reads)
@@ -294,9 +295,10 @@ int launch_tier(SeedRun& R, int tier, i64 n_todo, const i64* pending, int cset, 
     }
 }
 
-// the counters a tier's launch left, on the host (waits for ctx->stream); then its share of the call's tallies
-int fetch_counters(SeedRun& R, int cset, unsigned long long* h) {
-    HIP_TRY(hipMemcpyAsync(h, R.ctx->seed.counter_set(cset), SEED_CTRS * sizeof(unsigned long long), hipMemcpyDeviceToHost, R.ctx->stream));
+// the counters a tier's launch left, on the host (waits for ctx->stream); then its share of the call's tallies.  `nsets` = 2: both sets (they
+// are contiguous) in one copy and one wait, h[SEED_CTRS..] = set cset + 1
+int fetch_counters(SeedRun& R, int cset, unsigned long long* h, int nsets = 1) {
+    HIP_TRY(hipMemcpyAsync(h, R.ctx->seed.counter_set(cset), (size_t)nsets * SEED_CTRS * sizeof(unsigned long long), hipMemcpyDeviceToHost, R.ctx->stream));
     HIP_TRY(hipStreamSynchronize(R.ctx->stream));
     return MEME_OK;
 }
@@ -391,8 +393,10 @@ int seed_tier0(SeedRun& R) {
         HIP_TRY(hipStreamWaitEvent(ctx->stream, S.emit_ev[1], 0));
     }
     HIP_TRY(hipEventRecord(S.ev[SEED_EV_SEARCH1], ctx->stream));
-    unsigned long long h[SEED_CTRS];
-    if ((rc = fetch_counters(R, 0, h))) return rc;
+    // (ctx->stream waits for the early tier-1 launch above: its counter set is final too, and is read in the same copy)
+    unsigned long long h[2 * SEED_CTRS];
+    if ((rc = fetch_counters(R, 0, h, R.n_early >= 0 ? 2 : 1))) return rc;
+    if (R.n_early >= 0) memcpy(R.h_early, h + SEED_CTRS, sizeof(R.h_early));
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, S.ev[SEED_EV_SEARCH0], S.ev[SEED_EV_SEARCH1]));
     R.ms_total += ms;
@@ -421,8 +425,8 @@ int seed_overflow_tiers(SeedRun& R) {
         }
         const int cset = tier & 1;
         if (tier == 1 && R.n_early == R.n_todo) {
-            // the launch beside the re-seeding kernels took them all: only its counters are left to read
-            if ((rc = fetch_counters(R, cset, h))) return rc;
+            // the launch beside the re-seeding kernels took them all: its counters came with tier 0's
+            memcpy(h, R.h_early, sizeof(h));
         } else {
             // (tier 1 after an early launch that did not see every overflowed read: all of them again -- rare, and simple)
             HIP_TRY(hipEventRecord(S.ev[SEED_EV_SEARCH0], ctx->stream));

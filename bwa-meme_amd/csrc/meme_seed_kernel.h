@@ -1045,9 +1045,9 @@ __device__ __forceinline__ void lane_compare(const DevIndex& I, const LaneQuery&
 }
 
 // mem_search / right_smem_search with an occurrence floor (mode 1 of k_seed): L = the largest l <= maxLCP whose suffix-array interval
-// holds >= min_intv suffixes; [start, start + count) = that interval.  One lane, single-entry probes.
-// The common case costs two round trips: the model record, then LANE_W consecutive entries around its prediction fetched together; their
-// LCPs are parked in the lane's LDS column (lw: 16-bit values, two per dword, dword j of lane L at [j * 256 + L]) and both the partition
+// holds >= min_intv suffixes; [start, start + count) = that interval.  One lane per search, single-entry probes.
+// The common case costs two round trips: the model record, then LANE_W consecutive entries around its prediction fetched together (by the
+// lane's quad, see lane_search); their LCPs are parked in the lane's LDS column (lw: 16-bit values, two per dword, dword j of lane L at [j * 256 + L]) and both the partition
 // point and the interval usually lie inside.  Anything beyond that window is probed entry by entry (gallop, then bisection).
 constexpr int LANE_W = 16;
 struct LaneWin {
@@ -1065,36 +1065,86 @@ __device__ __forceinline__ int lane_lcp(const DevIndex& I, const LaneQuery& q, c
     return lc;
 }
 
-__device__ __forceinline__ void lane_search(const DevIndex& I, const LaneQuery& q, int min_intv, uint32_t* lw, int& r_L, i64& r_start, i64& r_count) {
+// The first window is fetched by the QUAD: a lane that asks for 256 bytes by itself with sixteen 16-byte loads gets ~9.6 G lines/s out of the
+// memory system, two to eight lanes per line 48 G (profiles/r02_seed_v2_experiment.md).  The four lanes of a quad serve each other in four
+// sub-rounds (owner = quad lane J): the owner's window base and query travel by DPP quad_perm, lane t loads entries base + 4 i + t (every load
+// instruction covers 64 contiguous bytes per quad), compares them with the owner's query and parks the LCPs in the owner's column; the "sorts
+// before" bits are OR-reduced over the quad.  All sixteen loads of a lane are in flight together, as before.
+// CONVERGENCE RULE: lane_search and stage_plcp_windows are entered by the whole wavefront, `active` = false in lanes that have nothing to fetch
+// (a DPP read from a lane that is not executing yields 0, not the lane's value).  Callers keep their loops wave-uniform (`while (__any(need))`).
+template <int J> __device__ __forceinline__ int quad_bcast(int v) { return __builtin_amdgcn_update_dpp(0, v, J * 0x55, 0xF, 0xF, true); }   // quad_perm [J,J,J,J]
+template <int J> __device__ __forceinline__ u64 quad_bcast64(u64 v) {
+    return ((u64)(unsigned)quad_bcast<J>((int)(v >> 32)) << 32) | (u64)(unsigned)quad_bcast<J>((int)(unsigned)v);
+}
+// LDS written by one lane, read by another of the same wavefront (k_seed's LDS_HANDOFF)
+__device__ __forceinline__ void lds_handoff() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// sub-round J, loads: this lane's four entries of the owner's window
+template <int J>
+__device__ __forceinline__ void quad_window_load(const SaEnt* __restrict__ sa, i64 base, int t, SaEnt (&ent)[LANE_W / 4]) {
+    const i64 bo = (i64)quad_bcast64<J>((u64)base);
+#pragma unroll
+    for (int i = 0; i < LANE_W / 4; ++i) ent[i] = sa[bo + 4 * i + t];
+}
+// sub-round J, compares: LCPs into the owner's column (`lwq`: column of quad lane 0), returns the window's 16 "sorts before the query" bits
+template <int J>
+__device__ __forceinline__ unsigned quad_window_compare(const DevIndex& I, const LaneQuery& q, bool active, int t, const SaEnt (&ent)[LANE_W / 4], uint32_t* lwq) {
+    LaneQuery qo;
+    qo.s = reinterpret_cast<const u64*>(quad_bcast64<J>((u64)reinterpret_cast<uintptr_t>(q.s)));
+    const int ov = quad_bcast<J>(q.off | (q.vlen << 16));
+    qo.off = ov & 0xffff; qo.vlen = (int)((unsigned)ov >> 16);
+    qo.wq = quad_bcast64<J>(q.wq);
+    const bool ao = quad_bcast<J>(active ? 1 : 0) != 0;
+    unsigned m = 0;
+    if (ao) {
+        unsigned short* col = reinterpret_cast<unsigned short*>(lwq + J) + (t & 1);       // entry k = 4 i + t: dword k >> 1, half k & 1
+#pragma unroll
+        for (int i = 0; i < LANE_W / 4; ++i) {
+            int lc; bool ls;
+            lane_compare_ent(I, qo, qo.vlen, ent[i], lc, ls);
+            m |= (ls ? 1u : 0u) << (4 * i + t);
+            col[(2 * i + (t >> 1)) * 512] = (unsigned short)lc;
+        }
+    }
+    return (unsigned)group_or<4>((int)m);
+}
+
+__device__ __forceinline__ void lane_search(const DevIndex& I, const LaneQuery& q, bool active, int min_intv, uint32_t* lw, int& r_L, i64& r_start, i64& r_count) {
     const i64 n = I.n;
-    u64 key = q.wq;
-    if (q.vlen < 32) key |= (~0ull) >> (2 * q.vlen);
-    u64 err;
-    const i64 p = rmi_lookup((glb_rmi)I.l2, (glb_rmi)I.l1, I.n_l1, I.shift, n, key, err);
-    LaneWin C; C.lw = lw; C.base = -1;
+    const int t = threadIdx.x & 3;
+    i64 p = 0, base = 0;
+    if (active) {
+        u64 key = q.wq;
+        if (q.vlen < 32) key |= (~0ull) >> (2 * q.vlen);
+        u64 err;
+        p = rmi_lookup((glb_rmi)I.l2, (glb_rmi)I.l1, I.n_l1, I.shift, n, key, err);
+        // first window, placed by the model's error bounds like k_seed's
+        const i64 below = (i64)((err >> 32) & 0x3fffffffull) + 1, above = (i64)(err & 0x7fffffffull);
+        const i64 span = below + above + 1;
+        base = span <= LANE_W ? p - below - (LANE_W - span) / 2 : p - (below * LANE_W) / span;
+        if (base < 0) base = 0;
+        if (base > n - LANE_W) base = n - LANE_W;
+    }
+    unsigned lessm;
+    {
+        lds_handoff();                              // the columns' readers of the previous search are done
+        SaEnt e0[LANE_W / 4], e1[LANE_W / 4], e2[LANE_W / 4], e3[LANE_W / 4];
+        quad_window_load<0>(I.sa, base, t, e0); quad_window_load<1>(I.sa, base, t, e1);
+        quad_window_load<2>(I.sa, base, t, e2); quad_window_load<3>(I.sa, base, t, e3);
+        uint32_t* lwq = lw - t;
+        const unsigned m0 = quad_window_compare<0>(I, q, active, t, e0, lwq), m1 = quad_window_compare<1>(I, q, active, t, e1, lwq);
+        const unsigned m2 = quad_window_compare<2>(I, q, active, t, e2, lwq), m3 = quad_window_compare<3>(I, q, active, t, e3, lwq);
+        lessm = t == 0 ? m0 : (t == 1 ? m1 : (t == 2 ? m2 : m3));
+        lds_handoff();
+    }
+    if (!active) return;
+    LaneWin C; C.lw = lw; C.base = base;
     int L = 0;
     i64 s = 0, e = 0;
     bool located = false;
     int lc; bool ls;
     {
-        // first window, placed by the model's error bounds like k_seed's
-        const i64 below = (i64)((err >> 32) & 0x3fffffffull) + 1, above = (i64)(err & 0x7fffffffull);
-        const i64 span = below + above + 1;
-        i64 base = span <= LANE_W ? p - below - (LANE_W - span) / 2 : p - (below * LANE_W) / span;
-        if (base < 0) base = 0;
-        if (base > n - LANE_W) base = n - LANE_W;
-        SaEnt ent[LANE_W];
-#pragma unroll
-        for (int k = 0; k < LANE_W; ++k) ent[k] = I.sa[base + k];
-        unsigned lessm = 0;
-        int prev = 0;
-#pragma unroll
-        for (int k = 0; k < LANE_W; ++k) {
-            lane_compare_ent(I, q, q.vlen, ent[k], lc, ls);
-            lessm |= (ls ? 1u : 0u) << k;
-            if (k & 1) lw[(k >> 1) * 256] = (uint32_t)prev | ((uint32_t)lc << 16); else prev = lc;
-        }
-        C.base = base;
         const int P = __popc(lessm);
         if (lessm == ((1u << P) - 1u) && ((P > 0 && P < LANE_W) || (P == 0 && base == 0) || (P == LANE_W && base + LANE_W == n))) {
             const int lm = P > 0 ? C.get(base + P - 1) : -1, lp = P < LANE_W ? C.get(base + P) : -1;
@@ -1301,18 +1351,35 @@ __device__ __forceinline__ void region_apply(RegionState& S, int msl, int r_L, i
     }
 }
 
-// the two table windows of a region into the lane's LDS column: eight aligned 16-byte loads in flight together
-__device__ __forceinline__ void stage_plcp_windows(const uint8_t* __restrict__ plcp, const PlcpView& V, uint32_t* win) {
-    uint4 v[2 * (PLCP_WIN / 16)];
-#pragma unroll
-    for (int q = 0; q < PLCP_WIN / 16; ++q) {
-        v[q] = *reinterpret_cast<const uint4*>(plcp + V.F0 + 16 * q);
-        v[PLCP_WIN / 16 + q] = *reinterpret_cast<const uint4*>(plcp + V.R0 + 16 * q);
-    }
-#pragma unroll
-    for (int q = 0; q < 2 * (PLCP_WIN / 16); ++q) {
-        win[(4 * q + 0) * 256] = v[q].x; win[(4 * q + 1) * 256] = v[q].y; win[(4 * q + 2) * 256] = v[q].z; win[(4 * q + 3) * 256] = v[q].w;
-    }   // (all eight loads in flight together: staging in two halves saves 16 VGPRs but adds a round trip per region)
+// the two table windows of a region into the lane's LDS column (`win`), fetched by the quad like lane_search's first window: in sub-round J
+// lane t loads the 16-byte pieces F0 + 16 t and R0 + 16 t of the owner's windows -- one 64-byte request per window -- and writes them into the
+// owner's column.  Eight aligned 16-byte loads per lane in flight together, as when every lane fetched its own.  Entered by the whole
+// wavefront (the convergence rule at lane_search); the column of a lane that is not `active` is left alone.
+template <int J>
+__device__ __forceinline__ void quad_plcp_load(const uint8_t* __restrict__ plcp, i64 F0, i64 R0, int t, uint4& vf, uint4& vr) {
+    vf = *reinterpret_cast<const uint4*>(plcp + (i64)quad_bcast64<J>((u64)F0) + 16 * t);
+    vr = *reinterpret_cast<const uint4*>(plcp + (i64)quad_bcast64<J>((u64)R0) + 16 * t);
+}
+template <int J>
+__device__ __forceinline__ void quad_plcp_store(bool active, int t, const uint4& vf, const uint4& vr, uint32_t* winq) {
+    if (quad_bcast<J>(active ? 1 : 0) == 0) return;
+    uint32_t* f = winq + J + (4 * t) * 256;                      // dwords 4 t .. 4 t + 3 of the forward window, of the mirror one behind it
+    uint32_t* r = f + (PLCP_WIN / 4) * 256;
+    f[0] = vf.x; f[256] = vf.y; f[512] = vf.z; f[768] = vf.w;
+    r[0] = vr.x; r[256] = vr.y; r[512] = vr.z; r[768] = vr.w;
+}
+__device__ __forceinline__ void stage_plcp_windows(const uint8_t* __restrict__ plcp, i64 F0, i64 R0, bool active, uint32_t* win) {
+    static_assert(PLCP_WIN == 64, "four 16-byte pieces per window, one per quad lane");
+    const int t = threadIdx.x & 3;
+    if (!active) { F0 = 0; R0 = 0; }
+    lds_handoff();                                                // the columns' readers of the previous region are done
+    uint4 vf[4], vr[4];
+    quad_plcp_load<0>(plcp, F0, R0, t, vf[0], vr[0]); quad_plcp_load<1>(plcp, F0, R0, t, vf[1], vr[1]);
+    quad_plcp_load<2>(plcp, F0, R0, t, vf[2], vr[2]); quad_plcp_load<3>(plcp, F0, R0, t, vf[3], vr[3]);
+    uint32_t* winq = win - t;
+    quad_plcp_store<0>(active, t, vf[0], vr[0], winq); quad_plcp_store<1>(active, t, vf[1], vr[1], winq);
+    quad_plcp_store<2>(active, t, vf[2], vr[2], winq); quad_plcp_store<3>(active, t, vf[3], vr[3], winq);
+    lds_handoff();
 }
 
 constexpr int BLK_PER_READ = 1;      // blocked regions a read may leave behind in the first pass; its last record takes the rest of the read with it
@@ -1336,31 +1403,42 @@ __global__ void __launch_bounds__(256) k_reseed(ReseedArgs A) {
         unsigned hops = 0, lsearches = 0;
         int n_pend = 0, n_blk = 0, pend_ns = 0;
         BlkRec held[BLK_PER_READ];
-        if (r < A.nreads) {
-            const int c0 = A.slot_cnt[r];
+        {
+            const bool have = r < A.nreads;
+            const int c0 = have ? A.slot_cnt[r] : 0;
             const int c = c0 > DEFER_MAX_K ? DEFER_MAX_K : c0;
-            SlotRec* sl = A.slots + r * cap;
-            const u64* rec = A.packed + r * A.geo.stride;           // fw[W] rc[W] nfw[MW] nrc[MW] len
+            SlotRec* sl = A.slots + (have ? r : 0) * cap;
+            const u64* rec = A.packed + (have ? r : 0) * A.geo.stride;   // fw[W] rc[W] nfw[MW] nrc[MW] len
             SmemAppender<true> ap;
             ap.sl = sl; ap.cap = cap; ap.hps = A.opt.hits_per_smem; ap.ns = c0; ap.hits_add = 0; ap.rid = r;
             int l_seq = 0;
             // the lanes of a wavefront take their j-th region together (a loop over the slot index would run the region code once per
-            // slot position with a few lanes each)
+            // slot position with a few lanes each), and stay in the loop until the last of them has none left: the table windows are
+            // fetched by the quad
             int k = -1;
+            bool live = have;
             for (;;) {
                 i64 f = 0;
-                for (++k; k < c; ++k) { f = sl[k].sa_start; if (f & SLOT_DEFER) break; }
-                if (k >= c) break;
-                if (l_seq == 0) { const u64 lw = rec[A.geo.stride - 1]; l_seq = (int)(lw & 0x7fffffffull); }
-                const int qbeg = sl[k].start, qend = sl[k].end;
-                const i64 T0 = (f & SLOT_VAL) - qbeg;
+                if (live) {
+                    for (++k; k < c; ++k) { f = sl[k].sa_start; if (f & SLOT_DEFER) break; }
+                    if (k >= c) live = false;
+                }
+                if (!__any(live)) break;
+                int qbeg = 0, qend = 0;
+                i64 T0 = 0;
                 PlcpView V;
-                V.plcp = plcp; V.win = win + threadIdx.x;
+                V.plcp = plcp; V.win = win + threadIdx.x; V.F0 = 0; V.R0 = 0;
                 RegionState S;
-                S.pivot = (qbeg + qend) >> 1; S.next = 0; S.guard = 0; S.stage = 0;
-                V.F0 = plcp_win_fwd(T0, S.pivot); V.R0 = plcp_win_rev(T0, S.pivot, n);
-                stage_plcp_windows(plcp, V, win + threadIdx.x);
-                if (region_walk<true>(V, n, T0, qbeg, qend, l_seq, msl, S, hops, ap, n_pend)) {
+                S.pivot = 0; S.next = 0; S.guard = 0; S.stage = 0;
+                if (live) {
+                    if (l_seq == 0) { const u64 lw = rec[A.geo.stride - 1]; l_seq = (int)(lw & 0x7fffffffull); }
+                    qbeg = sl[k].start; qend = sl[k].end;
+                    T0 = (f & SLOT_VAL) - qbeg;
+                    S.pivot = (qbeg + qend) >> 1;
+                    V.F0 = plcp_win_fwd(T0, S.pivot); V.R0 = plcp_win_rev(T0, S.pivot, n);
+                }
+                stage_plcp_windows(plcp, V.F0, V.R0, live, win + threadIdx.x);
+                if (live && region_walk<true>(V, n, T0, qbeg, qend, l_seq, msl, S, hops, ap, n_pend)) {
                     // blocked: to the batch search (k_reseed_search), resumed by k_reseed_resume.  This kernel does no search itself (it
                     // lives on its occupancy); a read's last record takes the read's remaining regions along.
                     BlkRec b;
@@ -1368,10 +1446,10 @@ __global__ void __launch_bounds__(256) k_reseed(ReseedArgs A) {
                     b.stage = S.stage | (n_blk == BLK_PER_READ - 1 ? BLK_MORE : 0);
 #pragma unroll
                     for (int i = 0; i < BLK_PER_READ; ++i) if (i == n_blk) held[i] = b;
-                    if (++n_blk == BLK_PER_READ) break;
+                    if (++n_blk == BLK_PER_READ) live = false;
                 }
             }
-            if (ap.ns != c0) {
+            if (have && ap.ns != c0) {
                 if (ap.ns > cap) {            // more SMEMs than the read's slots hold: the whole read goes to the next tier, as in k_seed
                     A.slot_cnt[r] = 0; A.slot_hits[r] = 0;
                     A.ovf_list[atomicAdd(&A.counters[SEED_CTR_OVERFLOW], 1ull)] = r;
@@ -1409,28 +1487,39 @@ __global__ void __launch_bounds__(256) k_reseed(ReseedArgs A) {
 __global__ void __launch_bounds__(256) k_reseed_emit(ReseedArgs A) {
     __shared__ uint32_t lwin[(LANE_W / 2) * 256];
     const i64 n_list = (i64)A.counters[SEED_CTR_PEND];
-    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n_list; i += (i64)gridDim.x * blockDim.x) {
+    for (i64 i0 = (i64)blockIdx.x * blockDim.x; i0 < n_list; i0 += (i64)gridDim.x * blockDim.x) {
         // (runs beside the blocked regions' passes, which append to the same reads: only the slots the first pass filled are looked
         // at, and the hit count is bumped atomically)
-        const i64 ent = A.pend_list[i];
+        const i64 i = i0 + threadIdx.x;
+        const bool have = i < n_list;
+        const i64 ent = have ? A.pend_list[i] : 0;
         const i64 r = ent & ((1ll << 40) - 1);
         const int c = (int)(ent >> 40);
         SlotRec* sl = A.slots + r * A.cap;
         const u64* rec = A.packed + r * A.geo.stride;
         i64 hits_add = 0;
         int k = -1;
-        for (;;) {
-            for (++k; k < c; ++k) if (sl[k].sa_start & SLOT_PEND) break;
-            if (k >= c) break;
+        bool live = have;
+        for (;;) {                                   // wave-uniform: a lane without a pending slot left serves its quad until the last one is done
+            if (live) {
+                for (++k; k < c; ++k) if (sl[k].sa_start & SLOT_PEND) break;
+                if (k >= c) live = false;
+            }
+            if (!__any(live)) break;
             LaneQuery q;
-            q.s = rec; q.off = sl[k].start; q.vlen = sl[k].end - sl[k].start;
-            q.wq = ext_g(q.s, q.off);
-            int r_L; i64 r_start, r_count;
-            lane_search(A.I, q, 1, lwin + threadIdx.x, r_L, r_start, r_count);
-            sl[k].sa_start = r_start; sl[k].count = r_count;
-            hits_add += (A.opt.hits_per_smem > 0 && r_count > A.opt.hits_per_smem) ? (i64)A.opt.hits_per_smem : r_count;
+            q.s = rec; q.off = 0; q.vlen = 0; q.wq = 0;
+            if (live) {
+                q.off = sl[k].start; q.vlen = sl[k].end - sl[k].start;
+                q.wq = ext_g(q.s, q.off);
+            }
+            int r_L = 0; i64 r_start = 0, r_count = 0;
+            lane_search(A.I, q, live, 1, lwin + threadIdx.x, r_L, r_start, r_count);
+            if (live) {
+                sl[k].sa_start = r_start; sl[k].count = r_count;
+                hits_add += (A.opt.hits_per_smem > 0 && r_count > A.opt.hits_per_smem) ? (i64)A.opt.hits_per_smem : r_count;
+            }
         }
-        atomicAdd(reinterpret_cast<unsigned long long*>(A.slot_hits + r), (unsigned long long)hits_add);
+        if (have) atomicAdd(reinterpret_cast<unsigned long long*>(A.slot_hits + r), (unsigned long long)hits_add);
     }
 }
 
@@ -1439,23 +1528,32 @@ __global__ void __launch_bounds__(256) k_reseed_search(ReseedArgs A) {
     __shared__ uint32_t lwin[(LANE_W / 2) * 256];
     i64 n_blk = (i64)A.counters[A.blk_ctr];
     if (n_blk > A.blk_cap) n_blk = A.blk_cap;
-    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n_blk; i += (i64)gridDim.x * blockDim.x) {
-        BlkRec b = A.blk[i];
-        const u64* rec = A.packed + b.rid * A.geo.stride;
-        const u64 lw = rec[A.geo.stride - 1];
-        RegionState S;
-        S.pivot = b.pivot; S.next = b.next; S.guard = b.guard; S.stage = b.stage & ~BLK_MORE;
-        const LaneQuery q = region_query(rec, A.geo, (int)(lw & 0x7fffffffull), ((lw >> 31) & 1ull) != 0, S);
-        lane_search(A.I, q, 2, lwin + threadIdx.x, b.r_L, b.r_start, b.r_count);
-        A.blk[i].r_L = b.r_L; A.blk[i].r_start = b.r_start; A.blk[i].r_count = b.r_count;
+    for (i64 i0 = (i64)blockIdx.x * blockDim.x; i0 < n_blk; i0 += (i64)gridDim.x * blockDim.x) {
+        const i64 i = i0 + threadIdx.x;
+        const bool have = i < n_blk;                  // (the list's last wavefront: lanes without a region serve their quad)
+        LaneQuery q;
+        q.s = A.packed; q.off = 0; q.vlen = 0; q.wq = 0;
+        if (have) {
+            const BlkRec b = A.blk[i];
+            const u64* rec = A.packed + b.rid * A.geo.stride;
+            const u64 lw = rec[A.geo.stride - 1];
+            RegionState S;
+            S.pivot = b.pivot; S.next = b.next; S.guard = b.guard; S.stage = b.stage & ~BLK_MORE;
+            q = region_query(rec, A.geo, (int)(lw & 0x7fffffffull), ((lw >> 31) & 1ull) != 0, S);
+        }
+        int r_L = 0; i64 r_start = 0, r_count = 0;
+        lane_search(A.I, q, have, 2, lwin + threadIdx.x, r_L, r_start, r_count);
+        if (have) { A.blk[i].r_L = r_L; A.blk[i].r_start = r_start; A.blk[i].r_count = r_count; }
     }
 }
 
 // Pass 2 (and 3, 4): one lane per blocked region: the search's result, then on with the table.  A region that blocks again goes to the
 // next list (and the next batch search) -- except in the LAST pass, which does its searches itself.  Two regions of one read may be in
 // different lanes here: SMEMs are appended with atomic counters.
+// (three wavefronts per SIMD, which the 40 KB of LDS of the LAST instantiation allow, also in registers: the quad-wide search holds the
+// other three lanes' entries, and without the bound the LAST pass takes 171 VGPRs -- two wavefronts per SIMD, and no faster than before)
 template <bool LAST>
-__global__ void __launch_bounds__(256) k_reseed_resume(ReseedArgs A) {
+__global__ void __launch_bounds__(256, 3) k_reseed_resume(ReseedArgs A) {
     __shared__ uint32_t win[2 * (PLCP_WIN / 4) * 256];
     __shared__ uint32_t lwin[(LANE_W / 2) * 256];
     __shared__ unsigned long long acc_total, acc_lane, out_base;
@@ -1473,12 +1571,17 @@ __global__ void __launch_bounds__(256) k_reseed_resume(ReseedArgs A) {
         const i64 i = i0 + threadIdx.x;
         bool blocked = false;
         BlkRec nb;
-        if (i < n_blk) {
-            const BlkRec b = A.blk[i];
+        {
+            // Every loop below is wave-uniform: the table windows and a search's first window are fetched by the quad, so a lane whose region
+            // is finished (or that has none) stays with its wavefront until the last lane is done.
+            const bool have = i < n_blk;
+            BlkRec b;
+            b.rid = 0; b.k = 0; b.pivot = 0; b.next = 0; b.guard = 0; b.stage = 0; b.r_L = 0; b.r_start = 0; b.r_count = 0;
+            if (have) b = A.blk[i];
             const i64 r = b.rid;
             SlotRec* sl = A.slots + r * A.cap;
             const u64* rec = A.packed + r * A.geo.stride;
-            const u64 lw = rec[A.geo.stride - 1];
+            const u64 lw = have ? rec[A.geo.stride - 1] : 0;
             const int l_seq = (int)(lw & 0x7fffffffull);
             const bool has_n = ((lw >> 31) & 1ull) != 0;
             SmemAppender<false> ap;
@@ -1486,42 +1589,60 @@ __global__ void __launch_bounds__(256) k_reseed_resume(ReseedArgs A) {
             ap.hps = A.opt.hits_per_smem; ap.ns = 0; ap.hits_add = 0;
             unsigned hops = 1;                   // the search k_reseed_search did
             int k = b.k;
-            const int c = (b.stage & BLK_MORE) ? (A.slot_cnt[r] > DEFER_MAX_K ? DEFER_MAX_K : A.slot_cnt[r]) : 0;   // (SMEMs appended meanwhile are not deferred ones)
+            const int c = (have && (b.stage & BLK_MORE)) ? (A.slot_cnt[r] > DEFER_MAX_K ? DEFER_MAX_K : A.slot_cnt[r]) : 0;   // (SMEMs appended meanwhile are not deferred ones)
             bool first = true;
-            for (;;) {
-                const int qbeg = sl[k].start, qend = sl[k].end;
-                const i64 T0 = (sl[k].sa_start & SLOT_VAL) - qbeg;
+            bool live = have;                    // the lane has a region to start at slot k
+            while (__any(live)) {
+                int qbeg = 0, qend = 0;
+                i64 T0 = 0;
                 PlcpView V;
-                V.plcp = plcp; V.win = win + threadIdx.x;
-                V.F0 = plcp_win_fwd(T0, (qbeg + qend) >> 1); V.R0 = plcp_win_rev(T0, (qbeg + qend) >> 1, n);
-                stage_plcp_windows(plcp, V, win + threadIdx.x);
+                V.plcp = plcp; V.win = win + threadIdx.x; V.F0 = 0; V.R0 = 0;
+                if (live) {
+                    qbeg = sl[k].start; qend = sl[k].end;
+                    T0 = (sl[k].sa_start & SLOT_VAL) - qbeg;
+                    V.F0 = plcp_win_fwd(T0, (qbeg + qend) >> 1); V.R0 = plcp_win_rev(T0, (qbeg + qend) >> 1, n);
+                }
+                stage_plcp_windows(plcp, V.F0, V.R0, live, win + threadIdx.x);
                 RegionState S;
-                if (first) {
+                S.pivot = (qbeg + qend) >> 1; S.next = 0; S.guard = 0; S.stage = 0;
+                if (live && first) {
                     S.pivot = b.pivot; S.next = b.next; S.guard = b.guard; S.stage = b.stage & ~BLK_MORE;
                     region_apply<false>(S, msl, b.r_L, b.r_start, b.r_count, ap);
                     first = false;
-                } else { S.pivot = (qbeg + qend) >> 1; S.next = 0; S.guard = 0; S.stage = 0; }
-                while (S.stage != 3) {
-                    int n_pend = 0;
-                    if (!region_walk<false>(V, n, T0, qbeg, qend, l_seq, msl, S, hops, ap, n_pend)) break;
-                    if (!LAST) {
-                        nb.rid = r; nb.k = k; nb.pivot = S.pivot; nb.next = S.next; nb.guard = S.guard; nb.stage = S.stage | (b.stage & BLK_MORE);
-                        nb.r_L = 0; nb.r_start = 0; nb.r_count = 0;
-                        blocked = true;
-                        break;
-                    }
-                    const LaneQuery q = region_query(rec, A.geo, l_seq, has_n, S);
-                    int r_L; i64 r_start, r_count;
-                    lane_search(A.I, q, 2, lwin + threadIdx.x, r_L, r_start, r_count);
-                    ++lsearches; ++hops;
-                    region_apply<false>(S, msl, r_L, r_start, r_count, ap);
                 }
-                if (blocked) break;
-                // the read's later regions, if this record carries them
-                for (++k; k < c; ++k) if ((sl[k].sa_start & (SLOT_DEFER | SLOT_POS)) == (SLOT_DEFER | SLOT_POS)) break;
-                if (k >= c) break;
+                bool walking = live;             // the lane is inside this region
+                for (;;) {
+                    bool need = false;           // the region stands at a search the table cannot answer
+                    if (walking) {
+                        int n_pend = 0;
+                        if (S.stage == 3 || !region_walk<false>(V, n, T0, qbeg, qend, l_seq, msl, S, hops, ap, n_pend)) walking = false;
+                        else if (!LAST) {
+                            nb.rid = r; nb.k = k; nb.pivot = S.pivot; nb.next = S.next; nb.guard = S.guard; nb.stage = S.stage | (b.stage & BLK_MORE);
+                            nb.r_L = 0; nb.r_start = 0; nb.r_count = 0;
+                            blocked = true;
+                            walking = false;
+                        } else need = true;
+                    }
+                    if (!LAST || !__any(need)) break;
+                    LaneQuery q;
+                    q.s = rec; q.off = 0; q.vlen = 0; q.wq = 0;
+                    if (need) q = region_query(rec, A.geo, l_seq, has_n, S);
+                    int r_L = 0; i64 r_start = 0, r_count = 0;
+                    lane_search(A.I, q, need, 2, lwin + threadIdx.x, r_L, r_start, r_count);
+                    if (need) {
+                        ++lsearches; ++hops;
+                        region_apply<false>(S, msl, r_L, r_start, r_count, ap);
+                    }
+                }
+                if (live) {
+                    if (blocked) live = false;
+                    else {                       // the read's later regions, if this record carries them
+                        for (++k; k < c; ++k) if ((sl[k].sa_start & (SLOT_DEFER | SLOT_POS)) == (SLOT_DEFER | SLOT_POS)) break;
+                        if (k >= c) live = false;
+                    }
+                }
             }
-            total += hops;
+            if (have) total += hops;
         }
         unsigned my = 0;
         if (blocked) my = atomicAdd(&out_n, 1u);
