@@ -144,6 +144,8 @@ struct ResidentBatch {
     DevBuf reads, read_off, packed, smems, hits, smem_off, hit_off;
     i64 last_seed_reads = 0;           // reads of the batch whose seeds are in smems / hits (input of meme_chain_last_batch_host)
     i64 last_seed_max_len = 0;         // longest read of that batch
+    i64 packed_reads = 0;              // reads in `packed` and their layout (PackGeom: W, MW, stride), for meme_debug_packed_reads
+    int packed_geom[3] = {0, 0, 0};
     bool reads_resident = false;       // reads holds the bases of that batch (false after meme_chain_batch_host: seeds brought by the caller)
 };
 // a seeding counter set (u64): slot cursor of the tier, searches, reads left for the next tier (the length of its overflow list), window loads, eight SEED_PROF sums,
@@ -212,6 +214,7 @@ struct meme_ctx {
     SideStreams side;
     // tuning
     i64 seed_blocks = 0;               // 0 = auto
+    i64 helper_blocks = 0;             // cap on the grids of the read packer, the offsets scan and the hit gather (0 = none)
     i64 smem_cap = 128;                // per-read SMEM slots in the search kernel's scratch (tier 0; 3 KB per read.  With 64 a handful of
                                        // the benchmark's 10 M reads overflowed and their sequential re-run cost every step 1.9 ms)
     i64 group_lanes = 4;               // lanes per read in the search kernel (4, 8, 16, 32)

@@ -43,8 +43,9 @@ __device__ __forceinline__ i64 block_scan_excl(i64 v, i64* total) {
 
 // pass 1: per-tile sums of (smem count, hit count)
 __global__ void __launch_bounds__(SCAN_BLOCK) k_tile_sums(const int* __restrict__ cnt, const i64* __restrict__ hits, i64 n,
-                                                          i64* __restrict__ tile_sums) {
-    i64 base = (i64)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
+                                                          i64 ntiles, i64* __restrict__ tile_sums) {
+  for (i64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    i64 base = tile * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
     i64 a = 0, b = 0;
     for (int k = 0; k < SCAN_ITEMS; ++k) {
         i64 i = base + k;
@@ -57,7 +58,8 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_tile_sums(const int* __restrict_
     i64 ta, tb;
     block_scan_excl(a, &ta);
     block_scan_excl(b, &tb);
-    if (threadIdx.x == 0) { tile_sums[2 * blockIdx.x] = ta; tile_sums[2 * blockIdx.x + 1] = tb; }
+    if (threadIdx.x == 0) { tile_sums[2 * tile] = ta; tile_sums[2 * tile + 1] = tb; }
+  }
 }
 
 // pass 2: one block scans the tile sums in place (exclusive); totals to out[0..1]
@@ -78,9 +80,10 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan_tiles(i64* __restrict__ til
 
 // pass 3: per-read offsets
 __global__ void __launch_bounds__(SCAN_BLOCK) k_offsets(const int* __restrict__ cnt, const i64* __restrict__ hits, i64 n,
-                                                        const i64* __restrict__ tile_sums, i64* __restrict__ smem_off,
+                                                        i64 ntiles, const i64* __restrict__ tile_sums, i64* __restrict__ smem_off,
                                                         i64* __restrict__ hit_off) {
-    i64 base = (i64)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
+  for (i64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    i64 base = tile * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
     i64 va[SCAN_ITEMS], vb[SCAN_ITEMS], a = 0, b = 0;
     for (int k = 0; k < SCAN_ITEMS; ++k) {
         i64 i = base + k;
@@ -94,15 +97,16 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_offsets(const int* __restrict__ 
         b += vb[k];
     }
     i64 ta, tb;
-    i64 ea = block_scan_excl(a, &ta) + tile_sums[2 * blockIdx.x];
-    i64 eb = block_scan_excl(b, &tb) + tile_sums[2 * blockIdx.x + 1];
+    i64 ea = block_scan_excl(a, &ta) + tile_sums[2 * tile];
+    i64 eb = block_scan_excl(b, &tb) + tile_sums[2 * tile + 1];
     for (int k = 0; k < SCAN_ITEMS; ++k) {
         i64 i = base + k;
         if (i < n) { smem_off[i] = ea; hit_off[i] = eb; }
         ea += va[k];
         eb += vb[k];
     }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == SCAN_BLOCK - 1) { smem_off[n] = ea; hit_off[n] = eb; }
+    if (tile == ntiles - 1 && threadIdx.x == SCAN_BLOCK - 1) { smem_off[n] = ea; hit_off[n] = eb; }
+  }
 }
 
 // ---- compaction + hit gather: one 16-lane group per read --------------------------------------------------
@@ -200,6 +204,21 @@ struct SeedRun {
     unsigned long long h_early[SEED_CTRS];   // the early tier-1 launch's counters (n_early >= 0), read back together with tier 0's
 };
 
+// grids of the helper kernels (packer, scan, gather): tuning key helper_blocks caps them, so that a small batch goes round their loops
+i64 helper_grid(const meme_ctx* ctx, i64 blocks) {
+    if (ctx->helper_blocks > 0 && blocks > ctx->helper_blocks) blocks = ctx->helper_blocks;
+    return blocks < 1 ? 1 : blocks;
+}
+// workgroups of a kernel that are resident on the device together: the grid of a kernel whose workgroups share the work out evenly and go
+// round (more would run as a second, thinner wave of workgroups)
+template <typename K>
+int resident_grid(const meme_ctx* ctx, K kernel, int threads, i64* blocks) {
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0));
+    *blocks = (i64)ctx->n_cus * (per_cu < 1 ? 1 : per_cu);
+    return MEME_OK;
+}
+
 // pack the reads: 2 bits/base, both strands, N masks (k_pack_reads)
 int seed_pack(SeedRun& R, const uint8_t* d_reads, i64 max_len, i64 total_bytes) {
     meme_ctx* ctx = R.ctx;
@@ -216,16 +235,17 @@ int seed_pack(SeedRun& R, const uint8_t* d_reads, i64 max_len, i64 total_bytes) 
     int rc;
     if ((rc = meme_buf_reserve(ctx, ctx->batch.packed, (size_t)R.nreads * geo.stride * 8))) return rc;
     HIP_TRY(hipEventRecord(ctx->seed.ev[SEED_EV_PACK0], ctx->stream));
-    int rb = (int)((48 * 1024) / max_len);                        // reads per workgroup: <= 48 KB of staged bytes
-    if (rb > 32) rb = 32;
-    if (rb < 1) rb = 1;
-    i64 pblocks = (R.nreads + rb - 1) / rb;
-    if (pblocks > (i64)ctx->n_cus * 16) pblocks = (i64)ctx->n_cus * 16;   // grid-stride beyond that
-    size_t plds = ((size_t)rb * (size_t)max_len + 16 + 48 + 3) & ~(size_t)3;   // + the packer's 9-dword reads past a read's last word
-    hipLaunchKernelGGL(k_pack_reads, dim3((unsigned)pblocks), dim3(256), plds, ctx->stream, d_reads,
-                       R.d_read_off, R.nreads, total_bytes, geo, rb, (u64*)ctx->batch.packed.p);
+    const int rw = pack_chunk_reads(max_len);                      // reads per wavefront and chunk
+    const i64 nchunks = (R.nreads + rw - 1) / rw;
+    i64 pblocks = (nchunks + 3) / 4, pmax = 0;                     // four wavefronts per workgroup, a chunk each; they go round beyond a full device
+    if ((rc = resident_grid(ctx, k_pack_reads, 256, &pmax))) return rc;
+    pblocks = helper_grid(ctx, pblocks > pmax ? pmax : pblocks);
+    hipLaunchKernelGGL(k_pack_reads, dim3((unsigned)pblocks), dim3(256), 0, ctx->stream, d_reads,
+                       R.d_read_off, R.nreads, total_bytes, geo, rw, (u64*)ctx->batch.packed.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ctx->seed.ev[SEED_EV_PACK1], ctx->stream));
+    ctx->batch.packed_reads = R.nreads;
+    ctx->batch.packed_geom[0] = geo.W; ctx->batch.packed_geom[1] = geo.MW; ctx->batch.packed_geom[2] = geo.stride;
     return MEME_OK;
 }
 
@@ -456,11 +476,12 @@ int seed_gather(SeedRun& R, meme_seed_result* out) {
     i64* tiles = (i64*)ctx->scan_tmp.p;
     i64* totals = tiles + 2 * ntiles;
     HIP_TRY(hipEventRecord(S.ev[SEED_EV_GATHER0], ctx->stream));
-    hipLaunchKernelGGL(k_tile_sums, dim3((unsigned)ntiles), dim3(SCAN_BLOCK), 0, ctx->stream, (const int*)S.slot_cnt.p,
-                       (const i64*)S.slot_hits.p, nreads, tiles);
+    const i64 sblocks = helper_grid(ctx, ntiles);                  // a tile per workgroup unless helper_blocks says fewer
+    hipLaunchKernelGGL(k_tile_sums, dim3((unsigned)sblocks), dim3(SCAN_BLOCK), 0, ctx->stream, (const int*)S.slot_cnt.p,
+                       (const i64*)S.slot_hits.p, nreads, ntiles, tiles);
     hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(SCAN_BLOCK), 0, ctx->stream, tiles, ntiles, totals);
-    hipLaunchKernelGGL(k_offsets, dim3((unsigned)ntiles), dim3(SCAN_BLOCK), 0, ctx->stream, (const int*)S.slot_cnt.p,
-                       (const i64*)S.slot_hits.p, nreads, (const i64*)tiles, (i64*)B.smem_off.p, (i64*)B.hit_off.p);
+    hipLaunchKernelGGL(k_offsets, dim3((unsigned)sblocks), dim3(SCAN_BLOCK), 0, ctx->stream, (const int*)S.slot_cnt.p,
+                       (const i64*)S.slot_hits.p, nreads, ntiles, (const i64*)tiles, (i64*)B.smem_off.p, (i64*)B.hit_off.p);
     HIP_TRY(hipGetLastError());
     i64 h_tot[2];
     HIP_TRY(hipMemcpyAsync(h_tot, totals, sizeof(h_tot), hipMemcpyDeviceToHost, ctx->stream));
@@ -469,7 +490,7 @@ int seed_gather(SeedRun& R, meme_seed_result* out) {
     if ((rc = meme_buf_reserve(ctx, B.hits, (size_t)(h_tot[1] + 1) * sizeof(u64)))) return rc;
     i64 gblocks = (nreads + 15) / 16;
     if (gblocks > (i64)ctx->n_cus * 8) gblocks = (i64)ctx->n_cus * 8;
-    if (gblocks < 1) gblocks = 1;
+    gblocks = helper_grid(ctx, gblocks);
     hipLaunchKernelGGL(k_gather, dim3((unsigned)gblocks), dim3(BLOCK), 0, ctx->stream, ctx->idx.sa, R.tiers,
                        (const i64*)S.slot_loc.p, (const int*)S.slot_cnt.p, nreads, R.opt->hits_per_smem,
                        (const i64*)B.smem_off.p, (const i64*)B.hit_off.p, (meme_mem_tl*)B.smems.p, (u64*)B.hits.p);
@@ -598,6 +619,21 @@ extern "C" int meme_seed_batch(meme_ctx* ctx, const uint8_t* reads, const int64_
     }
     HIP_TRY(hipMemcpyAsync(smems, res.d_smems, (size_t)res.total_smems * sizeof(meme_mem_tl), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(hits, res.d_hits, (size_t)res.total_hits * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return MEME_OK;
+}
+
+extern "C" int meme_debug_packed_reads(meme_ctx* ctx, uint64_t* out, int64_t capacity_words, int32_t* geom, int64_t* nreads) {
+    if (!ctx || !geom || !nreads) return MEME_E_ARG;
+    const ResidentBatch& B = ctx->batch;
+    if (B.packed_reads <= 0 || !B.packed.p) { meme_set_error("meme_debug_packed_reads: no batch was packed on this ctx"); return MEME_E_STATE; }
+    for (int k = 0; k < 3; ++k) geom[k] = B.packed_geom[k];
+    *nreads = B.packed_reads;
+    if (!out) return MEME_OK;
+    const i64 words = B.packed_reads * B.packed_geom[2];
+    if (capacity_words < words) { meme_set_error("meme_debug_packed_reads: %lld words needed", (long long)words); return MEME_E_CAPACITY; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(out, B.packed.p, (size_t)words * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return MEME_OK;
 }

@@ -86,126 +86,142 @@ struct SeedArgs {
 };
 
 // ---- read packing -------------------------------------------------------------------------------------
-// Layout per read: fw[W] rc[W] nfw[MW] nrc[MW] len.  A workgroup packs PACK_RB consecutive reads: their bytes are
-// contiguous in the input, so they are staged in LDS with aligned, coalesced dword loads and the 2-bit words are then
-// assembled from LDS bytes (the first version issued 32 scattered byte loads per output word: 11.7 ms per 10 M reads).
+// Layout per read: fw[W] rc[W] nfw[MW] nrc[MW] len|hasN<<31.  A WAVEFRONT packs a run of `rw` consecutive reads (a chunk) and never meets
+// a workgroup barrier: the chunk's bytes are contiguous in the input and its packed words are contiguous in the output.
+//   1. convert: every lane takes 16 input bytes with one 16-byte-aligned load and turns them into 32 bits of forward codes, 32 bits of
+//      complemented codes (N = byte & 0xFC != 0 is code 0 in both) and 16 N bits, first base in the top bit.  These three bit streams of the
+//      chunk go to the wavefront's own slice of LDS: every input byte is looked at once, not once per strand and mask.
+//   2. emit: lane i of pass p owns the chunk's output word 64 p + i, so a pass stores one 512-byte run.  Whatever the word is -- fw, rc, a
+//      mask or the length word -- it is 64 bits cut out of one stream at the read's offset (three LDS dwords, a funnel shift), reversed
+//      for the rc strand and the forward mask, and trimmed to the read's length: one path without a branch on "has this read an N".  The
+//      has-N flag of the length word is the OR of the read's forward mask words as they are emitted.
+// (The second version staged 32 reads per WORKGROUP behind four barriers, scanned for N on 32 of 256 threads and converted every byte
+// once per word it lands in: 2.31 ms per 10 M reads of 150 bp, 1.4 TB/s.)
+constexpr int PACK_CAP = 5120;                     // input bytes a wavefront stages per chunk (16 per lane, PACK_IT rounds)
+constexpr int PACK_IT = PACK_CAP / (64 * 16);
+constexpr int PACK_MAX_RW = 32;                    // reads per chunk: their offsets live one per lane
+constexpr int PACK_FWC = 0, PACK_RCC = PACK_CAP / 16 + 2, PACK_NM = 2 * PACK_RCC, PACK_FLAG = PACK_NM + PACK_CAP / 32 + 2;
+constexpr int PACK_SLICE = PACK_FLAG + PACK_MAX_RW;   // dwords of LDS per wavefront (3.3 KB)
+// reads per chunk for a batch whose longest read has max_len bases: the chunk starts up to 15 bytes before its first read
+inline int pack_chunk_reads(i64 max_len) {
+    i64 rw = (PACK_CAP - 16) / (max_len < 1 ? 1 : max_len);
+    return (int)(rw > PACK_MAX_RW ? PACK_MAX_RW : (rw < 1 ? 1 : rw));
+}
+
+// lanes of one wavefront hand data to each other through LDS: order the accesses, no workgroup barrier
+__device__ __forceinline__ void pack_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// four input bytes -> 8 bits of forward codes, 8 bits of complemented codes, 4 N bits (first byte in the top bits of each)
+__device__ __forceinline__ void pack_dword(uint32_t a, uint32_t& fw, uint32_t& rc, uint32_t& nm) {
+    const uint32_t e = ((((a & 0xFCFCFCFCu) >> 2) + 0x3F3F3F3Fu) >> 6) & 0x01010101u;   // 1 per byte that is not 0..3
+    const uint32_t keep = 0x03030303u & ~(e * 3u);
+    const uint32_t c = a & keep;                                                        // N packed as A (src/bwamem.cpp:1293-1294)
+    fw = (fw << 8) | ((c * 0x40100401u) >> 24);
+    rc = (rc << 8) | (((c ^ 0x03030303u) & keep) * 0x40100401u >> 24);                  // ... on both strands
+    nm = (nm << 4) | ((e * 0x08040201u) >> 24);
+}
+
 __global__ void __launch_bounds__(256) k_pack_reads(const uint8_t* __restrict__ reads, const i64* __restrict__ read_off,
-                                                     i64 nreads, i64 total_bytes, PackGeom g, int PACK_RB,
+                                                     i64 nreads, i64 total_bytes, PackGeom g, int rw,
                                                      u64* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char pk_raw[];
-    uint32_t* stage = reinterpret_cast<uint32_t*>(pk_raw);
-    const uint8_t* sb = pk_raw;
-    __shared__ int has_n[64];                                   // per read of the group (PACK_RB <= 64)
-    for (i64 r0 = (i64)blockIdx.x * PACK_RB; r0 < nreads; r0 += (i64)gridDim.x * PACK_RB) {
-        const int nr = (int)(nreads - r0 < PACK_RB ? nreads - r0 : PACK_RB);
-        const i64 b0 = read_off[r0], b1 = read_off[r0 + nr];
-        const i64 a0 = b0 & ~3ll;                              // dword-aligned start (reads + a0 is 4-byte aligned)
-        const int ndw = (int)((b1 - a0 + 3) >> 2);
-        __syncthreads();                                       // previous iteration's readers are done
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(reads + a0);
-        for (int k = threadIdx.x; k < ndw; k += blockDim.x) {
-            uint32_t v;
-            if (a0 + 4 * (i64)k + 4 <= total_bytes) v = src[k];
-            else {                                              // last dword of the buffer: never read past its end
-                v = 0;
-                for (int bb = 0; bb < 4; ++bb)
-                    if (a0 + 4 * (i64)k + bb < total_bytes) v |= (uint32_t)reads[a0 + 4 * (i64)k + bb] << (8 * bb);
-            }
-            stage[k] = v;
+    __shared__ uint32_t pk_lds[4 * PACK_SLICE];
+    const int lane = threadIdx.x & 63;
+    uint32_t* S = pk_lds + (threadIdx.x >> 6) * PACK_SLICE;
+    unsigned short* S16 = reinterpret_cast<unsigned short*>(S + PACK_NM);
+    const int stride = g.stride, nw = stride - 1;
+    const int k0 = lane % stride, rr0 = lane / stride, dk = 64 % stride, drr = 64 / stride;   // word 64 p + lane is word k of read rr
+    const int mis = (int)(reinterpret_cast<uintptr_t>(reads) & 15);                          // 16-byte alignment is of the address
+    const i64 nchunks = (nreads + rw - 1) / rw, nwaves = (i64)gridDim.x * 4;
+    i64 ch = (i64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    i64 off_next = 0;                                                                         // offsets of the next chunk, in flight
+    if (ch < nchunks && ch * rw + lane <= nreads && lane <= rw) off_next = read_off[ch * rw + lane];
+    for (; ch < nchunks; ch += nwaves) {
+        const i64 r0 = ch * rw;
+        const int nr = (int)(nreads - r0 < rw ? nreads - r0 : rw);
+        const i64 off_l = off_next;
+        {
+            const i64 rn = (ch + nwaves) * rw + lane;
+            if (ch + nwaves < nchunks && rn <= nreads && lane <= rw) off_next = read_off[rn];
         }
-        __syncthreads();
-        const int shift = (int)(b0 - a0);
-        const int nw = g.stride - 1;                            // data words per read; the length word follows them
-        // does the read contain an ambiguous base?  (dword-wide scan of the staged bytes; almost always "no", and then
-        // its N-mask words are zero without looking at the bases again)
-        for (int rr = threadIdx.x; rr < nr; rr += blockDim.x) {
-            const i64 ro = read_off[r0 + rr];
-            const int len = (int)(read_off[r0 + rr + 1] - ro);
-            uint32_t acc = 0;
-            if (len > 0 && len <= MAX_READ_LEN) {
-                const int o = shift + (int)(ro - b0), last = o + len - 1;
-                const int d0 = o >> 2, d1 = last >> 2;
-                for (int d = d0; d <= d1; ++d) {
-                    uint32_t m = 0xFCFCFCFCu;
-                    if (d == d0) m &= 0xFFFFFFFFu << (8 * (o & 3));
-                    if (d == d1) m &= 0xFFFFFFFFu >> (8 * (3 - (last & 3)));
-                    acc |= stage[d] & m;
+        const i64 b0 = __shfl(off_l, 0), b1 = __shfl(off_l, nr);
+        const i64 a0 = ((b0 + mis) & ~15ll) - mis;                       // may lie before the buffer: guarded below
+        const int rel = (int)(off_l - a0);                                // (lanes beyond nr: unused)
+        const i64 span = b1 - a0;
+        // 1. convert
+        uint4 v[PACK_IT];
+#pragma unroll
+        for (int it = 0; it < PACK_IT; ++it) {
+            const i64 p = a0 + 16 * (it * 64 + lane);
+            v[it] = make_uint4(0, 0, 0, 0);
+            if (16 * (it * 64 + lane) < span) {
+                if (p >= 0 && p + 16 <= total_bytes) v[it] = *reinterpret_cast<const uint4*>(reads + p);
+                else {                                                    // the buffer's first and last bytes: nothing outside it is read
+                    uint32_t q[4] = {0, 0, 0, 0};
+                    for (int bb = 0; bb < 16; ++bb)
+                        if (p + bb >= 0 && p + bb < total_bytes) q[bb >> 2] |= (uint32_t)reads[p + bb] << (8 * (bb & 3));
+                    v[it] = make_uint4(q[0], q[1], q[2], q[3]);
                 }
             }
-            has_n[rr] = acc != 0;
         }
-        __syncthreads();
-        for (int wk = threadIdx.x; wk < nr * nw; wk += blockDim.x) {
-            const int rr = wk / nw, k = wk - rr * nw;
-            const i64 r = r0 + rr;
-            const i64 ro = read_off[r];
-            int len = (int)(read_off[r + 1] - ro);
-            u64 v = 0;
-            if (len > MAX_READ_LEN) len = 0;
-            const int po = shift + (int)(ro - b0);              // the read's first byte in the staged area
-            const uint8_t* p = sb + po;
-            if (k < 2 * g.W) {
-                const bool rc = k >= g.W;
-                const int w = rc ? k - g.W : k;
-                const int nvalid = len - 32 * w;                // bases of this word
-                if (nvalid <= 0) v = 0;
-                else if (!has_n[rr]) {
-                    // Every byte of the read is 0..3: 32 bases = 8 staged dwords (re-aligned with v_alignbyte), four bases
-                    // of a dword gathered into one byte by a multiplication, no per-base loop.  Forward: bases 32w..32w+31;
-                    // reverse complement: the same for the 32 bases that END at len-1-32w, bytes and dwords in reverse
-                    // order, complemented.  Bytes beyond the read (the neighbours' bases) are shifted / masked away.
-                    const int s0 = rc ? (nvalid >= 32 ? nvalid - 32 : 0) : 32 * w;
-                    const int o = po + s0, dwi = o >> 2;
-                    const unsigned sh = (unsigned)(o & 3);
-                    uint32_t a[9];
+        pack_wave_sync();                                                 // the previous chunk's readers are done
+        if (lane < PACK_MAX_RW) S[PACK_FLAG + lane] = 0;
 #pragma unroll
-                    for (int q = 0; q < 9; ++q) a[q] = stage[dwi + q];
-                    if (!rc) {
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) {
-                            const uint32_t x = __builtin_amdgcn_alignbyte(a[q + 1], a[q], sh) & 0x03030303u;
-                            v = (v << 8) | ((x * 0x40100401u) >> 24);          // first base of the dword in the top two bits
-                        }
-                        if (nvalid < 32) v &= ~0ull << (2 * (32 - nvalid));
-                    } else {
-#pragma unroll
-                        for (int q = 7; q >= 0; --q) {
-                            const uint32_t x = (__builtin_amdgcn_alignbyte(a[q + 1], a[q], sh) & 0x03030303u) ^ 0x03030303u;
-                            v = (v << 8) | ((x * 0x01041040u) >> 24);          // last base of the dword in the top two bits
-                        }
-                        if (nvalid < 32) v <<= 2 * (32 - nvalid);
-                    }
-                } else {
-#pragma unroll 16
-                    for (int j = 0; j < 32; ++j) {
-                        const int i = 32 * w + j;
-                        u64 c = 0;
-                        if (i < len) {
-                            const uint8_t bb = rc ? p[len - 1 - i] : p[i];
-                            c = bb < 4 ? (rc ? 3 - bb : bb) : 0;   // N packed as A (src/bwamem.cpp:1293-1294)
-                        }
-                        v = (v << 2) | c;
-                    }
-                }
-            } else if (has_n[rr]) {
-                int m = k - 2 * g.W;
-                const bool rc = m >= g.MW;
-                if (rc) m -= g.MW;
-                for (int j = 0; j < 64; ++j) {
-                    const int i = 64 * m + j;
-                    if (i < len) {
-                        const uint8_t bb = rc ? p[len - 1 - i] : p[i];
-                        if (bb >= 4) v |= 1ull << j;
-                    }
-                }
+        for (int it = 0; it < PACK_IT; ++it) {
+            const int i = it * 64 + lane;
+            if (16 * i < span) {
+                uint32_t fw = 0, rc = 0, nm = 0;
+                pack_dword(v[it].x, fw, rc, nm);
+                pack_dword(v[it].y, fw, rc, nm);
+                pack_dword(v[it].z, fw, rc, nm);
+                pack_dword(v[it].w, fw, rc, nm);
+                S[PACK_FWC + i] = fw;
+                S[PACK_RCC + i] = rc;
+                S16[i ^ 1] = (unsigned short)nm;                          // little-endian halves: bases 32 j .. 32 j + 15 in the top half
             }
-            out[r * g.stride + k] = v;
         }
-        __syncthreads();
-        for (int rr = threadIdx.x; rr < nr; rr += blockDim.x) {  // length word: length | (read has an N) << 31
-            const i64 r = r0 + rr;
-            const int len = (int)(read_off[r + 1] - read_off[r]);
-            out[r * g.stride + nw] = (u64)(unsigned)len | (has_n[rr] ? (1ull << 31) : 0ull);
+        pack_wave_sync();
+        // 2. emit
+        u64* o64 = out + r0 * stride;
+        const int nwords = nr * stride;
+        int rr = rr0, k = k0;
+        for (int wk = lane; wk - lane < nwords; wk += 64) {
+            const bool in = wk < nwords;
+            const int rs = in ? rr : 0;
+            const int o = __shfl(rel, rs), e = __shfl(rel, rs + 1);
+            const int len = e - o;
+            const int lenx = (len > MAX_READ_LEN || e > PACK_CAP) ? 0 : len;       // (the host refuses such batches)
+            const bool code = k < 2 * g.W;
+            const int kk = code ? k : k - 2 * g.W, per = code ? g.W : g.MW;
+            const bool second = kk >= per;                                // the reverse-complement strand (the length word: as an empty mask word)
+            const int w = second ? kk - per : kk;
+            const int span_b = code ? 32 : 64;
+            int nvalid = lenx - span_b * w;                               // bases of this word
+            if (nvalid > span_b) nvalid = span_b;
+            if (nvalid < 0 || k == nw) nvalid = 0;
+            int s0 = second ? lenx - span_b * w - span_b : span_b * w;    // rc: the bases that END at len - 1 - span w
+            if (s0 < 0 || nvalid == 0) s0 = 0;
+            const int bit = (nvalid == 0 ? 0 : o + s0) << (code ? 1 : 0);
+            const int idx = (code ? (second ? PACK_RCC : PACK_FWC) : PACK_NM) + (bit >> 5);
+            const unsigned sh = (unsigned)bit & 31u;
+            const uint32_t d0 = S[idx], d1 = S[idx + 1], d2 = S[idx + 2];
+            u64 u = ((u64)__funnelshift_l(d1, d0, sh) << 32) | __funnelshift_l(d2, d1, sh);
+            if (code == second) u = __brevll(u);                          // rc codes and the forward mask (bit j = base 64 m + j) run backwards
+            if (code) { if (second) u = ((u >> 1) & 0x5555555555555555ull) | ((u & 0x5555555555555555ull) << 1); }
+            const int cut = (span_b - nvalid) << (code ? 1 : 0);          // bits that lie beyond the read (0..64)
+            u64 val;
+            if (code) val = second ? u << (cut & 63) : u & (~0ull << (cut & 63));
+            else val = second ? u >> (cut & 63) : u & (~0ull >> (cut & 63));
+            if (nvalid == 0) val = 0;
+            if (in && !code && !second && val != 0) S[PACK_FLAG + rs] = 1;
+            pack_wave_sync();                                             // a read's mask words come before its length word
+            if (k == nw) val = (u64)(unsigned)len | (S[PACK_FLAG + rs] ? (1ull << 31) : 0ull);
+            if (in) o64[wk] = val;
+            rr += drr; k += dk;
+            if (k >= stride) { k -= stride; ++rr; }
         }
     }
 }

@@ -157,7 +157,7 @@ EXPORTS = ["meme_device_count", "meme_ctx_create", "meme_ctx_destroy", "meme_las
            "meme_index_attach", "meme_index_describe", "meme_index_share", "meme_index_replicate", "meme_host_alloc",
            "meme_host_free", "meme_stage_pack_text", "meme_stage_pos5_from_sa", "meme_stage_build_entries", "meme_stage_build_plcp",
            "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_seed_batch_device",
-           "meme_bsw_batch", "meme_bsw_batch_device", "meme_get_timings", "meme_set_tuning"]
+           "meme_bsw_batch", "meme_bsw_batch_device", "meme_get_timings", "meme_set_tuning", "meme_debug_packed_reads"]
 
 _lib = None
 
@@ -339,6 +339,14 @@ class Context:
         _check(lib().meme_seed_batch_resident_ascii(C.c_void_p(self.h), _p(reads), _p(read_off), C.c_int64(read_off.shape[0] - 1), C.byref(opt),
                                                     C.byref(ts), C.byref(th)))
         return ts.value, th.value
+
+    def debug_packed_reads(self):
+        """meme_debug_packed_reads: the last seeded batch as the search kernels read it.  Returns (words[nreads, stride] uint64, W, MW)."""
+        geom, n = (C.c_int32 * 3)(), C.c_int64(0)
+        _check(lib().meme_debug_packed_reads(C.c_void_p(self.h), None, C.c_int64(0), geom, C.byref(n)))
+        words = np.zeros((n.value, geom[2]), dtype=np.uint64)
+        _check(lib().meme_debug_packed_reads(C.c_void_p(self.h), _p(words), C.c_int64(words.size), geom, C.byref(n)))
+        return words, int(geom[0]), int(geom[1])
 
     def seed_reserve(self, nreads, total_bases):
         _check(lib().meme_seed_reserve(C.c_void_p(self.h), C.c_int64(nreads), C.c_int64(total_bases)))
