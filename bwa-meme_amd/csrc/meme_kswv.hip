@@ -307,6 +307,10 @@ int meme_kswv_run(meme_ctx* ctx, const meme_kswv_job* jobs, int64_t njobs, const
     if (njobs == 0) return MEME_OK;
     if (njobs > 0x7fffffff / 2) { meme_set_error("meme_kswv_batch_host: too many jobs in one call"); return MEME_E_ARG; }
     if (opt->a < 1 || opt->b < 0 || opt->e_del < 0 || opt->e_ins < 0 || opt->o_del < 0 || opt->o_ins < 0) { meme_set_error("meme_kswv_batch_host: bad scoring parameters"); return MEME_E_ARG; }
+    if (opt->a > 127 || opt->b > 127) {                 // (the row's scores are a table of signed bytes, as in meme_seedsw_launch)
+        meme_set_error("meme_kswv_batch_host: match score %d / mismatch penalty %d beyond the kernel's limits (both <= 127)", opt->a, opt->b);
+        return MEME_E_ARG;
+    }
     const int n = (int)njobs;
     // classes and order: LDS size class, then padded query length, then window length (descending inside a class, so a wavefront's
     // lanes run about the same number of rows)

@@ -305,7 +305,101 @@ KSWV_GOLDEN_SETS = (
     ("default", dict(n=2500, seed=91), {}),
     ("long", dict(n=1500, seed=5, read_len=(200, 420)), {}),
     ("other", dict(n=1500, seed=6, read_len=(30, 300), a=2), dict(a=2, b=3, o_del=4, e_del=2, o_ins=5, e_ins=1)),
+    # int8 lanes that saturate (score + mismatch penalty >= 255: score 255, no second-best score, no start): what -B 6 and up does to 245-249-base reads
+    ("sat_b20", dict(n=2000, seed=50, read_len=(236, 250)), dict(b=20)),
+    ("sat_a2", dict(n=2000, seed=51, read_len=(110, 125), a=2), dict(a=2, b=30, o_del=4, e_del=2, o_ins=5, e_ins=1)),
+    ("sat_gaps1", dict(n=2000, seed=52, read_len=(200, 250)), dict(b=60, o_del=1, e_del=1, o_ins=1, e_ins=1)),
 )
+KSWV_SAT_SETS = ("sat_b20", "sat_a2", "sat_gaps1")
+# match 7 / mismatch 120: shift 120, so an int8 lane holds at most 135 and 30-base jobs saturate (20 matches)
+KSWV_A7_WORKLOAD, KSWV_A7_PEN = dict(n=600, seed=53, read_len=(22, 36), a=7), dict(a=7, b=120)
+
+
+def _kswv_pack(items):
+    """(window, query, xtra) triples -> (jobs, ref bytes, query bytes): every job with bytes of its own, 8 spare bytes behind both buffers."""
+    from oracle_py import KSWV_JOB_DTYPE
+    jobs = np.zeros(len(items), KSWV_JOB_DTYPE)
+    ro = qo = 0
+    for k, (win, q, x) in enumerate(items):
+        jobs[k] = (ro, qo, win.shape[0], q.shape[0], x, 0)
+        ro += win.shape[0]; qo += q.shape[0]
+    pad = np.zeros(8, np.uint8)
+    return jobs, np.concatenate([w for w, _, _ in items] + [pad]).astype(np.uint8), np.concatenate([q for _, q, _ in items] + [pad]).astype(np.uint8)
+
+
+# query lengths on both sides of every LDS size class of k_kswv (64, 128, 160, 256, 384, 528 padded columns; stripe 16 for int8 jobs, 8 for int16 jobs)
+KSWV_CLASS_EDGE_BOTH = (1, 7, 8, 9, 15, 16, 17, 56, 57, 63, 64, 65, 72, 120, 121, 127, 128, 129, 136, 152, 153, 159, 160, 161, 168, 248, 249, 255)
+KSWV_CLASS_EDGE_I16 = (256, 257, 264, 376, 377, 384, 385, 392, 496, 497, 504, 505, 511, 512)
+
+
+def kswv_class_edge_jobs():
+    """70 jobs whose query lengths lie on both sides of every size class of the mate-rescue kernel: KSWV_CLASS_EDGE_BOTH each as an int16 and as an int8
+    job (interleaved: int16, int8), then KSWV_CLASS_EDGE_I16 as int16 jobs.  The read is taken 60 bases into a window of L + 120 bases (70 into L + 150
+    from 256 bases up), with one substitution in its middle when L > 20.  int8 jobs below 19 bases carry no threshold (they could never reach it)."""
+    from oracle_py import KSW_XBYTE, KSW_XSUBO, KSW_XSTART
+    rng = np.random.default_rng(7)
+    g = rng.integers(0, 4, size=6000, dtype=np.uint8)
+    items = []
+    for L, kinds in [(L, (0, 1)) for L in KSWV_CLASS_EDGE_BOTH] + [(L, (0,)) for L in KSWV_CLASS_EDGE_I16]:
+        for is8 in kinds:
+            W, off = (L + 120, 60) if L < 256 else (L + 150, 70)
+            p = int(rng.integers(0, g.shape[0] - W))
+            win = g[p:p + W].copy()
+            q = win[off:off + L].copy()
+            if L > 20:
+                q[L // 2] = (q[L // 2] + 1) & 3
+            x = KSW_XSUBO | KSW_XSTART | 19
+            if is8:
+                x = (x | KSW_XBYTE) if L >= 19 else (KSW_XSTART | KSW_XBYTE)
+            items.append((win, q, x))
+    return _kswv_pack(items)
+
+
+KSWV_LIMIT_PEN = dict(a=8, b=4)
+
+
+def kswv_limit_jobs():
+    """Jobs at the kernel's limits, meant for KSWV_LIMIT_PEN (match 8, mismatch 4): scores at the top of the 12-bit H / F fields (a 511-base perfect match
+    = 4 088, the same with two substitutions, a 500-base match; 700-base windows; int16), thresholds an int8 lane cannot hold (KSW_XSUBO | 256,
+    KSW_XSUBO | 255, KSW_XSTOP | 300, 30-base reads), an empty window and an empty query."""
+    from oracle_py import KSW_XBYTE, KSW_XSTOP, KSW_XSUBO, KSW_XSTART
+    rng = np.random.default_rng(8)
+    g = rng.integers(0, 4, size=6000, dtype=np.uint8)
+    X16 = KSW_XSUBO | KSW_XSTART | 19 * 8
+    items = []
+    for L, nsub in ((511, 0), (511, 2), (500, 0)):
+        p = int(rng.integers(0, g.shape[0] - 700))
+        win = g[p:p + 700].copy()
+        q = win[90:90 + L].copy()
+        for s in range(nsub):
+            q[(s + 1) * L // 3] = (q[(s + 1) * L // 3] + 1) & 3
+        items.append((win, q, X16))
+    for x in (KSW_XSUBO | KSW_XSTART | KSW_XBYTE | 256, KSW_XSUBO | KSW_XSTART | KSW_XBYTE | 255, KSW_XSTOP | KSW_XBYTE | 300, KSW_XSTOP | KSW_XSTART | KSW_XBYTE | 300):
+        p = int(rng.integers(0, g.shape[0] - 200))
+        win = g[p:p + 150].copy()
+        items.append((win, win[60:90].copy(), x))
+    p = int(rng.integers(0, g.shape[0] - 200))
+    for x in (KSW_XSUBO | KSW_XSTART | KSW_XBYTE | 19, KSW_XSUBO | KSW_XSTART | 19):
+        items.append((g[p:p].copy(), g[p + 60:p + 90].copy(), x))              # len1 = 0
+        items.append((g[p:p + 150].copy(), g[p:p].copy(), x))                  # len2 = 0
+    return _kswv_pack(items)
+
+
+def kswv_saturated_jobs(n, n_live=0):
+    """n int8 jobs of one length: perfect 249-base matches in 400-base windows -- every one saturates under a mismatch penalty of 6 or more (249 + b >= 255).
+    The last n_live of them carry 40 substitutions instead and do not saturate (score + b < 255 for b <= 40)."""
+    from oracle_py import KSW_XBYTE, KSW_XSUBO, KSW_XSTART
+    rng = np.random.default_rng(9)
+    g = rng.integers(0, 4, size=6000, dtype=np.uint8)
+    items = []
+    for k in range(n):
+        p = int(rng.integers(0, g.shape[0] - 400))
+        win = g[p:p + 400].copy()
+        q = win[70:319].copy()
+        if k >= n - n_live:
+            q[3::6] = (q[3::6] + 1) & 3
+        items.append((win, q, KSW_XSUBO | KSW_XSTART | KSW_XBYTE | 19))
+    return _kswv_pack(items)
 
 
 def kswv_edge_jobs():

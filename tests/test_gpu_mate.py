@@ -89,9 +89,13 @@ def test_mate_rescue_on_the_device_equals_the_reference_golden(tag):
 
 
 @pytest.mark.parametrize("seed,pes,kw", [(321, [(10, 2000, 0)] * 4, {}), (322, [(0, 0, 1)] * 4, {}), (323, [(50, 500, 0), (120, 680, 0), (100, 900, 0), (0, 0, 1)], dict(max_matesw=2, pen_unpaired=40)),
-                                         (324, None, dict(min_seed_len=40, a=2, b=5)), (325, [(0, 0, 1), (200, 260, 0), (0, 0, 1), (150, 151, 0)], dict(batch_reads=64))])
+                                         (324, None, dict(min_seed_len=40, a=2, b=5)), (325, [(0, 0, 1), (200, 260, 0), (0, 0, 1), (150, 151, 0)], dict(batch_reads=64)),
+                                         # 236-249-base mates under mismatch 70: every job is an int8 job and the well-matching ones saturate (score 255) on the staged path
+                                         (326, [(10, 2000, 0)] * 4, dict(b=70, read_len=(236, 250)))])
 def test_mate_rescue_on_the_device_equals_the_oracle(seed, pes, kw):
-    W = matesw_pose_workload(seed=seed, pes=pes, n_pairs=700)
+    kw = dict(kw)
+    read_len = kw.pop("read_len", None)
+    W = matesw_pose_workload(seed=seed, pes=pes, n_pairs=700, **({} if read_len is None else dict(read_len=read_len)))
     ctx = hipapi.Context(0)
     try:
         keep = _stage(ctx, W["genome"], W["reads"], W["read_off"])
@@ -105,7 +109,10 @@ def test_mate_rescue_on_the_device_equals_the_oracle(seed, pes, kw):
                 assert np.array_equal(R["gar"][R["gar_off"][b]:R["gar_off"][b + 1]], gar), b
                 assert R["job_off"][b + 1] - R["job_off"][b] == jobs.shape[0]
         else:
-            _check(ctx, W, **kw)
+            R = _check(ctx, W, **kw)
+            if kw.get("b", 4) >= 70:
+                assert ((R["jobs"]["xtra"] & 0x10000) != 0).all()                 # (KSW_XBYTE: a score of 255 is a saturated lane)
+                assert int((R["res"]["score"] == 255).sum()) >= 50                # (the oracle gives 104)
         # reads beyond the batch on the ctx, or an odd first read, are refused
         n = W["read_len"].shape[0]
         with pytest.raises(hipapi.MemeError):

@@ -169,18 +169,25 @@ def test_gen_cigar2_oracle_equals_reference_on_other_penalties():
 @needs_stage
 def test_kswv_oracle_equals_reference_live():
     """orc_kswv_batch == the compiled reference's mate-rescue batch (ref_kswv_batch: sort_classify + mem_sam_pe_batch, AVX-512 kswv kernels) on
-    fresh job sets: other seeds, short reads, extreme penalties (free gap opens; mismatch 9), windows shorter than the read."""
-    from common import kswv_workload
+    fresh job sets: other seeds, short reads, extreme penalties (free gap opens; mismatch 9), windows shorter than the read, saturating int8 lanes."""
+    from common import KSWV_A7_PEN, KSWV_A7_WORKLOAD, kswv_workload
     if ref_py.stage_lib().ref_kswv_batch(None, 0, None, 0, None, 0, 1, 4, 6, 1, 6, 1, None) != 0:
         pytest.skip("the compiled reference is not an AVX-512 build (no batched kswv kernels)")
     for kw, pen in ((dict(n=1200, seed=17), {}), (dict(n=800, seed=18, read_len=(19, 140)), dict(a=1, b=9, o_del=1, e_del=1, o_ins=1, e_ins=1)),
                     (dict(n=800, seed=19, read_len=(240, 260)), dict(a=1, b=1, o_del=0, e_del=1, o_ins=0, e_ins=1)),
-                    (dict(n=600, seed=20, read_len=(100, 500), a=3), dict(a=3, b=5, o_del=7, e_del=2, o_ins=3, e_ins=3))):
+                    (dict(n=600, seed=20, read_len=(100, 500), a=3), dict(a=3, b=5, o_del=7, e_del=2, o_ins=3, e_ins=3)),
+                    # int8 lanes that saturate (the sat_b20, sat_a2 and sat_gaps1 sets of the fixture) and match 7 / mismatch 120, which saturates 30-base jobs
+                    (dict(n=2000, seed=50, read_len=(236, 250)), dict(b=20)),
+                    (dict(n=2000, seed=51, read_len=(110, 125), a=2), dict(a=2, b=30, o_del=4, e_del=2, o_ins=5, e_ins=1)),
+                    (dict(n=2000, seed=52, read_len=(200, 250)), dict(b=60, o_del=1, e_del=1, o_ins=1, e_ins=1)),
+                    (KSWV_A7_WORKLOAD, KSWV_A7_PEN)):
         jobs, ref, qer = kswv_workload(**kw)
         want = ref_py.kswv_batch(jobs, ref, qer, **pen).view(np.int32).reshape(-1, 7)
         got = O.kswv_batch(jobs, ref, qer, threads=4, **pen)[0].view(np.int32).reshape(-1, 7)
         bad = np.nonzero((got != want).any(axis=1))[0]
         assert bad.size == 0, (kw, pen, int(bad[0]), got[bad[0]].tolist(), want[bad[0]].tolist())
+        if pen.get("b", 4) >= 20:
+            assert int((want[:, 0] == 255).sum()) >= 100, (kw, pen, "saturated records", int((want[:, 0] == 255).sum()))
 
 
 @needs_stage
@@ -193,6 +200,44 @@ def test_kswv_edge_jobs_reference_live():
     want = ref_py.kswv_batch(jobs, rb, qb).view(np.int32).reshape(-1, 7)
     assert np.array_equal(want, np.array(KSWV_EDGE_WANT, np.int32))
     assert np.array_equal(O.kswv_batch(jobs, rb, qb)[0].view(np.int32).reshape(-1, 7), want)
+
+
+@needs_stage
+def test_kswv_class_edge_and_limit_jobs_reference_live():
+    """Compiled reference == oracle, all seven fields, on the inputs the GPU tests of the kernel's size classes and limits use (tests/common.py):
+    kswv_class_edge_jobs() under the default penalties and under mismatch 9; kswv_limit_jobs() (scores up to 4 088, thresholds an int8 lane cannot
+    hold, an empty window, an empty query) under match 8 / mismatch 4; 63 saturating jobs and one live one in the same vector."""
+    from common import KSWV_LIMIT_PEN, kswv_class_edge_jobs, kswv_limit_jobs, kswv_saturated_jobs
+    if ref_py.stage_lib().ref_kswv_batch(None, 0, None, 0, None, 0, 1, 4, 6, 1, 6, 1, None) != 0:
+        pytest.skip("the compiled reference is not an AVX-512 build (no batched kswv kernels)")
+    for what, (jobs, rb, qb), pen in (("class edges", kswv_class_edge_jobs(), {}), ("class edges", kswv_class_edge_jobs(), dict(b=9)), ("limits", kswv_limit_jobs(), KSWV_LIMIT_PEN),
+                                      ("63 + 1", kswv_saturated_jobs(64, n_live=1), dict(b=9)), ("63 + 1", kswv_saturated_jobs(64, n_live=1), dict(b=6))):
+        want = ref_py.kswv_batch(jobs, rb, qb, **pen).view(np.int32).reshape(-1, 7)
+        got = O.kswv_batch(jobs, rb, qb, **pen)[0].view(np.int32).reshape(-1, 7)
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert bad.size == 0, (what, pen, int(bad[0]), jobs[bad[0]].tolist(), got[bad[0]].tolist(), want[bad[0]].tolist())
+        if what == "limits":
+            assert int(want[:, 0].max()) == 4088
+        if what == "63 + 1":
+            assert int((want[:, 0] == 255).sum()) == 63 and (want[:63, 3:] == -1).all()
+
+
+@needs_stage
+def test_kswv_all_saturated_vectors_reference_live():
+    """64 and 130 int8 jobs of one length that ALL saturate (perfect 249-base matches, mismatch 9 and 6): compiled reference == oracle on score, te, qe,
+    tb, qb.  score2 / te2 are NOT compared: with every lane of a 64-lane vector saturated, getScores8 returns at live == 0 (src/kswv.cpp:607) before it
+    writes them, and the reference hands back uninitialised memory there (values like 66306 were seen).  The oracle -- and the device -- give -1 / -1,
+    which is what the reference gives as soon as one lane of the vector is live (test_kswv_class_edge_and_limit_jobs_reference_live: 63 + 1)."""
+    from common import kswv_saturated_jobs
+    if ref_py.stage_lib().ref_kswv_batch(None, 0, None, 0, None, 0, 1, 4, 6, 1, 6, 1, None) != 0:
+        pytest.skip("the compiled reference is not an AVX-512 build (no batched kswv kernels)")
+    for n in (64, 130):
+        jobs, rb, qb = kswv_saturated_jobs(n)
+        for b in (9, 6):
+            want = ref_py.kswv_batch(jobs, rb, qb, b=b).view(np.int32).reshape(-1, 7)
+            got = O.kswv_batch(jobs, rb, qb, b=b)[0].view(np.int32).reshape(-1, 7)
+            assert (got[:, 0] == 255).all() and (got[:, 3:] == -1).all()
+            assert np.array_equal(got[:, [0, 1, 2, 5, 6]], want[:, [0, 1, 2, 5, 6]]), (n, b)
 
 
 needs_aligner = pytest.mark.skipif(not (ref_py.have("bwa-meme_mode3") and ref_py.cpu_can_run()), reason="compiled reference (bwa-meme_mode3) not available")
