@@ -26,7 +26,8 @@
 #include <stdlib.h>
 #include <chrono>
 
-#include "meme_common.h"
+#include "meme_bsw_rules.h"
+#include "meme_colword.h"
 
 namespace {
 
@@ -119,47 +120,23 @@ __global__ void __launch_bounds__(BSW_BLOCK) k_bsw(BswArgs A) {
         }
         // ---- first row (:143-145) and query staging ---------------------------------------------------
         for (int j = gl; j <= qlen + 1; j += LP) {
-            int v = 0;
-            if (j == 0) v = h0;
-            else if (j <= qlen) {
-                // eh[1] = max(h0-oe_ins,0); eh[j] = eh[j-1]-e_ins while eh[j-1] > e_ins
-                int first = h0 > oe_ins ? h0 - oe_ins : 0;
-                int x = first - (j - 1) * e_ins;
-                int prev = first - (j - 2) * e_ins;
-                v = (j == 1) ? first : (prev > e_ins ? x : 0);
-            }
-            H[j] = v;
+            H[j] = j <= qlen ? bsw_row0(h0, oe_ins, e_ins, j) : 0;
             E[j] = 0;
             if (j < qlen) Q[j] = query[j];
         }
-        // band cap (:148-156)
-        int w = A.w;
-        {
-            int mx = sa > 0 ? sa : 0;
-            int max_ins = (int)((double)(qlen * mx + A.o.end_bonus - o_ins) / e_ins + 1.);
-            if (max_ins < 1) max_ins = 1;
-            if (w > max_ins) w = max_ins;
-            int max_del = (int)((double)(qlen * mx + A.o.end_bonus - o_del) / e_del + 1.);
-            if (max_del < 1) max_del = 1;
-            if (w > max_del) w = max_del;
-        }
+        const int w = bsw_band_cap(A.o, qlen, A.w);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        int max = h0, max_i = -1, max_j = -1, max_ie = -1, gscore = -1, max_off = 0;
+        BswBest best(h0);
         int beg = 0, end = qlen;
         int tchunk = 0;                 // lane k of the group holds target[LP*(i/LP) + k]
         for (int i = 0; i < tlen; ++i) {
             if ((i & (LP - 1)) == 0) tchunk = (i + gl < tlen) ? target[i + gl] : 4;
             // the row index is per group (groups of one wavefront may be at different rows after a divergent exit)
             const int tb = __builtin_amdgcn_ds_bpermute((gbase + (i & (LP - 1))) << 2, tchunk);
-            if (beg < i - w) beg = i - w;
-            if (end > i + w + 1) end = i + w + 1;
-            if (end > qlen) end = qlen;
-            int h1;
-            if (beg == 0) { h1 = h0 - (o_del + e_del * (i + 1)); if (h1 < 0) h1 = 0; }
-            else h1 = 0;
-            int carry_g = NEG;          // running max of M(k) - oe_ins + k*e_ins over finished chunks
+            int h1 = bsw_row_head(i, w, qlen, h0, o_del, e_del, beg, end);
+            int carry_g = NEG;         // running max of M(k) - oe_ins + k*e_ins over finished chunks
             int left_h = h1;            // H(i, j0-1) for the first column of the chunk
             int bh = -1, bj = -1;       // this lane's best cell of the row: score, rightmost column among equal scores
             for (int j0 = beg; j0 < end; j0 += LP) {
@@ -207,23 +184,7 @@ __global__ void __launch_bounds__(BSW_BLOCK) k_bsw(BswArgs A) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if ((beg < end ? end : beg) == qlen) {          // "if (j == qlen)" after the column loop, :202-205
-                max_ie = gscore > h1 ? max_ie : i;
-                gscore = gscore > h1 ? gscore : h1;
-            }
-            if (m == 0) break;                             // :206
-            if (m > max) {
-                max = m; max_i = i; max_j = mj;
-                int off = mj - i;
-                if (off < 0) off = -off;
-                max_off = max_off > off ? max_off : off;
-            } else if (zdrop > 0) {
-                if (i - max_i > mj - max_j) {
-                    if (max - m - ((i - max_i) - (mj - max_j)) * e_del > zdrop) break;
-                } else {
-                    if (max - m - ((mj - max_j) - (i - max_i)) * e_ins > zdrop) break;
-                }
-            }
+            if (bsw_row_end(best, i, m, mj, h1, beg, end, qlen, e_del, e_ins, zdrop)) break;
             // band trimming (:217-221): drop leading / trailing columns whose H and E are both zero
             int nbeg = end;
             for (int j0 = beg; j0 < end; j0 += LP) {
@@ -240,28 +201,20 @@ __global__ void __launch_bounds__(BSW_BLOCK) k_bsw(BswArgs A) {
                 if (b) { jl = hi - (LP - 1) + (63 - __clzll((long long)b)); break; }
             }
             beg = nbeg;
-            end = jl + 2 < qlen ? jl + 2 : qlen;
+            end = bsw_next_end(jl, qlen);
         }
-        if (gl == 0) {
-            P->score = max;
-            P->qle = max_j + 1;
-            P->tle = max_i + 1;
-            P->gtle = max_ie + 1;
-            P->gscore = gscore;
-            P->max_off = max_off;
-        }
+        if (gl == 0) best.store(P);
         __builtin_amdgcn_wave_barrier();
     }
 }
 
-// ---- lane-per-pair kernel ---------------------------------------------------------------------------------------------
+// ---- lane-per-pair kernels --------------------------------------------------------------------------------------------
 // The same inter-task parallelism the reference's SIMD code uses (one pair per SIMD lane, pairs sorted by length so that
 // the lanes of a vector finish together: sortPairsLenExt, src/bwamem.cpp:2430-2527), at wavefront width: each of the 64
 // lanes runs scalarBandedSWA on its own pair.  No cross-lane traffic at all; per DP cell a lane issues one LDS read,
 // one LDS write and ~16 integer ops.  The row state {H(i-1,j-1), E(i,j)} and the query base of column j share one
-// 32-bit LDS word (query code in the low byte, then 12 + 12 bits), laid out [column][lane] so every access is bank-conflict free whatever column
-// each lane is at.  Pairs whose scores could exceed 12 bits or whose query exceeds LANE_QMAX go to the
-// lanes-per-pair kernel above.
+// column word (meme_colword.h: query code in the low byte, then 12 + 12 bits).  Pairs whose scores could exceed 12 bits or
+// whose query exceeds LANE_QMAX go to the lanes-per-pair kernel above.
 constexpr int LANE_QMAX = 600;
 constexpr int LANE_SCORE_LIMIT = 1 << 12;
 constexpr int N_LANE_CLS = 8;                                        // LDS = (q + 2) * 256 B per wavefront: 8 KB ... 150 KB
@@ -283,190 +236,24 @@ struct LaneArgs {
     int key_first, key_last;
 };
 
-__device__ __forceinline__ unsigned he_pack(int h, int e, unsigned qbits) { return ((unsigned)h << 8) | ((unsigned)e << 20) | qbits; }
-// the same for the inner loop, two instructions: (e << 12 | h), then its three low bytes above the low byte of the old word
-__device__ __forceinline__ unsigned he_repack(int h, int e, unsigned old) {
-    unsigned x, w;
-    asm("v_lshl_or_b32 %0, %1, 12, %2" : "=v"(x) : "v"(e), "v"(h));
-    asm("v_perm_b32 %0, %1, %2, %3" : "=v"(w) : "v"(x), "v"(old), "s"(0x06050400u));
-    return w;
-}
-__device__ __forceinline__ int max3_i32(int a, int b, int c) { int d; asm("v_max3_i32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
-
-__global__ void __launch_bounds__(64) k_bsw_lane(LaneArgs A) {
-    extern __shared__ __attribute__((aligned(16))) unsigned int he_raw[];
-    typedef __attribute__((address_space(3))) unsigned int* lds_u32;
-    const int lane = threadIdx.x;
-    const lds_u32 he = (lds_u32)he_raw + lane;           // column j of this lane's pair: he[j * 64]
-    const int o_del = A.o.o_del, e_del = A.o.e_del, o_ins = A.o.o_ins, e_ins = A.o.e_ins;
-    const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins, zdrop = A.o.zdrop;
-    const int sa = A.o.a, sb = -A.o.b;
-    constexpr unsigned HE_MASK = 0xffffff00u, QMASK = 0xffu;
-    if (A.offs) { A.first = A.offs[A.key_first]; A.count = A.offs[A.key_last] - A.first; }
-    for (;;) {
-        unsigned int tk = 0;
-        if (lane == 0) tk = atomicAdd(A.ticket, 64u);
-        tk = __shfl(tk, 0);
-        if (tk >= (unsigned)A.count) break;
-        const bool active = tk + lane < (unsigned)A.count;
-        meme_seqpair* P = &A.pairs[A.order[A.first + (active ? tk + lane : tk)]];
-        const int qlen = active ? P->len2 : 0, tlen = active ? P->len1 : 0, h0 = P->h0;
-        const uint8_t* query = A.qer + P->idq;
-        const uint8_t* target = A.ref + P->idr;
-        // ---- first row (:143-145) with the query bases folded in -----------------------------------------
-        {
-            const int first = h0 > oe_ins ? h0 - oe_ins : 0;
-            // query bytes in batches of 8 independent loads (a lane's bytes are consecutive: same cache line)
-            for (int j0 = 0; j0 <= qlen; j0 += 8) {
-                unsigned qb[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) qb[u] = j0 + u < qlen ? (unsigned)query[j0 + u] : 0u;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int j = j0 + u;
-                    if (j > qlen) break;
-                    int v;
-                    if (j == 0) v = h0;
-                    else if (j == 1) v = first;
-                    else { const int prev = first - (j - 2) * e_ins; v = prev > e_ins ? prev - e_ins : 0; }
-                    he[j * 64] = he_pack(v, 0, qb[u] > 4u ? 4u : qb[u]);
-                }
-            }
-        }
-        // band cap (:148-156)
-        int w = A.w;
-        {
-            const int mx = sa > 0 ? sa : 0;
-            int max_ins = (int)((double)(qlen * mx + A.o.end_bonus - o_ins) / e_ins + 1.);
-            if (max_ins < 1) max_ins = 1;
-            if (w > max_ins) w = max_ins;
-            int max_del = (int)((double)(qlen * mx + A.o.end_bonus - o_del) / e_del + 1.);
-            if (max_del < 1) max_del = 1;
-            if (w > max_del) w = max_del;
-        }
-        int max = h0, max_i = -1, max_j = -1, max_ie = -1, gscore = -1, max_off = 0;
-        int beg = 0, end = qlen;
-        int tb_next = tlen > 0 ? (int)target[0] : 4;
-        for (int i = 0; i < tlen; ++i) {
-            const int tb = tb_next;
-            if (i + 1 < tlen) tb_next = target[i + 1];        // in flight during the row
-            int f = 0, h1, m = 0, mj = -1;
-            if (beg < i - w) beg = i - w;
-            if (end > i + w + 1) end = i + w + 1;
-            if (end > qlen) end = qlen;
-            if (beg == 0) { h1 = h0 - (o_del + e_del * (i + 1)); if (h1 < 0) h1 = 0; }
-            else h1 = 0;
-            // the row's substitution scores as a byte table indexed by the query code (v_perm_b32 picks byte q of {hi, lo}): codes 0..3 in
-            // tab_lo (the target base's own slot holds the match score), code 4 = N in byte 0 of tab_hi; a row on an N scores -1 throughout
-            const unsigned sb4 = (unsigned)(sb & 0xff) * 0x01010101u;
-            const unsigned tab_lo = tb > 3 ? 0xffffffffu : (sb4 & ~(0xffu << (8 * tb))) | ((unsigned)(sa & 0xff) << (8 * tb));
-            const unsigned tab_hi = 0xffffffffu;
-            // Four cells per trip with rotating registers for the column state: the next column's LDS word is
-            // requested before the current cell is computed and first touched a whole cell later (a single rotating
-            // register made the compiler wait for the prefetch in the middle of the cell).  The row maximum and its rightmost
-            // column travel as one key (h << 10 | column), one accumulator per unrolled position (mk_ + its position, joined below).
-#define BSW_CELL(cur_, nxt_, j_, mk_, jb_)                                                                    \
-            {                                                                                                  \
-                nxt_ = he[((j_) + 1) * 64];                    /* (j+1 <= qlen: inside the row) */              \
-                int M = (int)((cur_ >> 8) & 0xfffu), e = (int)(cur_ >> 20);                                     \
-                /* (selector byte 0 = the query code; the other result bytes are not looked at) */             \
-                const int sc = (int)(signed char)(__builtin_amdgcn_perm(tab_hi, tab_lo, cur_) & 0xffu);         \
-                M = M ? M + sc : 0;                            /* :184 */                                      \
-                const int h = max3_i32(M, e, f);                                                               \
-                const int key = (h << 10) + (jb_);                                                             \
-                mk_ = mk_ > key ? mk_ : key;                   /* rightmost column among equal maxima */       \
-                e = max3_i32(M - oe_del, e - e_del, 0);        /* E(i+1,j) (:190-194) */                       \
-                he[(j_) * 64] = he_repack(h1, e, cur_);        /* H(i,j-1) for the next row (:183) */          \
-                h1 = h;                                                                                        \
-                f = max3_i32(M - oe_ins, f - e_ins, 0);        /* F(i,j+1) (:195-198) */                       \
-            }
-            unsigned wa = beg < end ? he[beg * 64] : 0u, wb = 0u, wc = 0u, wd = 0u;
-            int mk0 = -8, mk1 = -8, mk2 = -8, mk3 = -8;
-            int j = beg;
-            for (; j + 3 < end; j += 4) {
-                BSW_CELL(wa, wb, j, mk0, j)
-                BSW_CELL(wb, wc, j + 1, mk1, j)
-                BSW_CELL(wc, wd, j + 2, mk2, j)
-                BSW_CELL(wd, wa, j + 3, mk3, j)
-            }
-            for (; j < end; ++j) {
-                BSW_CELL(wa, wb, j, mk0, j)
-                wa = wb;
-            }
-#undef BSW_CELL
-            {
-                mk1 += 1; mk2 += 2; mk3 += 3;
-                const int ka = mk0 > mk1 ? mk0 : mk1, kb = mk2 > mk3 ? mk2 : mk3;
-                const int key = ka > kb ? ka : kb;
-                m = key < 0 ? 0 : key >> 10;
-                mj = key < 0 ? -1 : key & 1023;
-            }
-            he[end * 64] = he_pack(h1, 0, he[end * 64] & QMASK);    // :201
-            const unsigned w_front = he[beg * 64];             // (for the band trimming below: requested here, used after the row's bookkeeping)
-            if ((beg < end ? end : beg) == qlen) {             // "if (j == qlen)" after the column loop, :202-205
-                max_ie = gscore > h1 ? max_ie : i;
-                gscore = gscore > h1 ? gscore : h1;
-            }
-            if (m == 0) break;                                 // :206
-            if (m > max) {
-                max = m; max_i = i; max_j = mj;
-                int off = mj - i;
-                if (off < 0) off = -off;
-                max_off = max_off > off ? max_off : off;
-            } else if (zdrop > 0) {
-                if (i - max_i > mj - max_j) {
-                    if (max - m - ((i - max_i) - (mj - max_j)) * e_del > zdrop) break;
-                } else {
-                    if (max - m - ((mj - max_j) - (i - max_i)) * e_ins > zdrop) break;
-                }
-            }
-            // band trimming (:217-221): drop leading / trailing columns whose H and E are both zero
-            int jt = beg;
-            if (jt < end && (w_front & HE_MASK) == 0u) {
-                ++jt;
-                while (jt < end && (he[jt * 64] & HE_MASK) == 0u) ++jt;
-            }
-            beg = jt;
-            jt = end;
-            if (h1 == 0) {                                     // (column `end` was just written as {h1, 0}: only a zero there asks for the scan)
-                --jt;
-                while (jt >= beg && (he[jt * 64] & HE_MASK) == 0u) --jt;
-            }
-            end = jt + 2 < qlen ? jt + 2 : qlen;
-        }
-        if (active) {
-            P->score = max;
-            P->qle = max_j + 1;
-            P->tle = max_i + 1;
-            P->gtle = max_ie + 1;
-            P->gscore = gscore;
-            P->max_off = max_off;
-        }
-    }
-}
-
-// ---- lane-per-pair kernel with a CIRCULAR band buffer (round 6) -----------------------------------------------------------------
-// Row i of the function touches columns [beg, end] with i - w <= beg and end <= i + w + 1 (:151-156, :171-175): at most 2w + 2 columns, and
-// beg never decreases.  The linear kernel above keeps a word for every column of the query -- (q + 2) * 256 bytes of LDS per wavefront: 57 KB
-// for queries up to 222 bases (two wavefronts per CU), 82 KB up to 318 and 154 KB up to 600 (ONE per CU): the classes that hold 36 % of the
-// extension jobs of 250-bp reads.  Here column j lives in slot j mod C of a ring of C >= 2w + 2 columns (C = 208 for w = 100: 53 KB, three
-// wavefronts per CU whatever the query length).  What makes that exact:
+// One body, two ways to address a column's word.
+//  * !RING (k_bsw_lane): column j of a lane's pair is word j -- (q + 2) * 256 bytes of LDS per wavefront: 57 KB for queries up to 222 bases (two
+//    wavefronts per CU), 82 KB up to 318 and 154 KB up to 600 (ONE per CU): the classes that hold 36 % of the extension jobs of 250-bp reads.
+//  * RING (k_bsw_lane_circ, round 6): a CIRCULAR band buffer.  Row i of the function touches columns [beg, end] with i - w <= beg and end <= i + w + 1
+//    (:151-156, :171-175): at most 2w + 2 columns, and beg never decreases.  Column j lives in slot j mod C of a ring of C >= 2w + 2 columns (C = 204
+//    for w = 100: 52 KB, three wavefronts per CU whatever the query length).  What makes that exact:
 //   * a slot is reused for column j + C only at a row where i + w + 1 >= j + C, i.e. beg >= i - w > j: column j has left the band for good;
 //   * a column the band reaches for the first time must hold the FIRST ROW's value (the "stale cells" the function reads when its band grows,
 //     :143-145 with :183-201): columns enter in increasing order, one per row (end <= i + w + 1), so the ring is topped up with
 //     {H(-1, j), E = 0, query base j} for j = i + w + 1 at the head of row i -- the query byte requested a row ahead;
 //   * columns the band re-reads after shrinking (end = jt + 2 can fall and rise again) are still in the ring: they are above beg.
-// The cell, the row bookkeeping, the trimming and the tie rules are the linear kernel's, statement for statement; only addresses differ.  A
-// row's columns are walked in runs that do not cross the ring's seam (at most one seam per row: one cell computed on its own).
-struct LaneCircArgs { LaneArgs L; int C; };
-
-__global__ void __launch_bounds__(64) k_bsw_lane_circ(LaneCircArgs AC) {
+//    Only addresses differ (`slot`), plus the statements under `if (RING)`: the top-up, and a row's columns walked in runs that do not cross the
+//    ring's seam (at most one seam per row: one cell computed on its own).
+template <bool RING>
+__device__ __forceinline__ void bsw_lane_pairs(LaneArgs& A, const int C) {
     extern __shared__ __attribute__((aligned(16))) unsigned int he_raw[];
-    typedef __attribute__((address_space(3))) unsigned int* lds_u32;
-    LaneArgs& A = AC.L;
-    const int C = AC.C;
     const int lane = threadIdx.x;
-    const lds_u32 he = (lds_u32)he_raw + lane;           // slot s of this lane's pair: he[s * 64]
+    const lds_u32 he = (lds_u32)he_raw + lane;           // column j (RING: slot s) of this lane's pair: he[j * 64]
     const int o_del = A.o.o_del, e_del = A.o.e_del, o_ins = A.o.o_ins, e_ins = A.o.e_ins;
     const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins, zdrop = A.o.zdrop;
     const int sa = A.o.a, sb = -A.o.b;
@@ -482,10 +269,11 @@ __global__ void __launch_bounds__(64) k_bsw_lane_circ(LaneCircArgs AC) {
         const int qlen = active ? P->len2 : 0, tlen = active ? P->len1 : 0, h0 = P->h0;
         const uint8_t* query = A.qer + P->idq;
         const uint8_t* target = A.ref + P->idr;
-        const int first = h0 > oe_ins ? h0 - oe_ins : 0;
-        // H(-1, j) of the first row (:143-145)
-#define BSW_ROW0(j_) ((j_) == 0 ? h0 : ((j_) == 1 ? first : ((first - ((j_) - 2) * e_ins) > e_ins ? (first - ((j_) - 2) * e_ins) - e_ins : 0)))
-        int hi = qlen < C - 1 ? qlen : C - 1;                 // highest column the ring holds so far
+        int cb = 0;                                           // RING: multiple of C with cb <= beg < cb + C: column j sits in slot j - cb (- C beyond the seam)
+        auto slot = [&](int j) { if (!RING) return j; const int s = j - cb; return s >= C ? s - C : s; };
+        // ---- first row with the query bases folded in: every column (RING: the first C), query bytes in batches of 8 independent loads (a lane's
+        // bytes are consecutive: same cache line)
+        int hi = RING && C - 1 < qlen ? C - 1 : qlen;        // highest column the storage holds so far
         for (int j0 = 0; j0 <= hi; j0 += 8) {
             unsigned qb[8];
 #pragma unroll
@@ -494,141 +282,110 @@ __global__ void __launch_bounds__(64) k_bsw_lane_circ(LaneCircArgs AC) {
             for (int u = 0; u < 8; ++u) {
                 const int j = j0 + u;
                 if (j > hi) break;
-                he[j * 64] = he_pack(BSW_ROW0(j), 0, qb[u] > 4u ? 4u : qb[u]);
+                he[j * 64] = cw_pack(bsw_row0(h0, oe_ins, e_ins, j), 0, qb[u] > 4u ? 4u : qb[u]);
             }
         }
-        int w = A.w;
-        {
-            const int mx = sa > 0 ? sa : 0;
-            int max_ins = (int)((double)(qlen * mx + A.o.end_bonus - o_ins) / e_ins + 1.);
-            if (max_ins < 1) max_ins = 1;
-            if (w > max_ins) w = max_ins;
-            int max_del = (int)((double)(qlen * mx + A.o.end_bonus - o_del) / e_del + 1.);
-            if (max_del < 1) max_del = 1;
-            if (w > max_del) w = max_del;
-        }
-        int max = h0, max_i = -1, max_j = -1, max_ie = -1, gscore = -1, max_off = 0;
+        const int w = bsw_band_cap(A.o, qlen, A.w);
+        BswBest best(h0);
         int beg = 0, end = qlen;
-        int cb = 0;                                           // multiple of C with cb <= beg < cb + C: column j sits in slot j - cb (- C beyond the seam)
-#define BSW_SLOT(j_) (((j_) - cb) >= C ? ((j_) - cb - C) : ((j_) - cb))
         int tb_next = tlen > 0 ? (int)target[0] : 4;
-        unsigned q_next = hi + 1 < qlen ? (unsigned)query[hi + 1] : 0u;        // base of the next column to enter the ring
+        unsigned q_next = RING && hi + 1 < qlen ? (unsigned)query[hi + 1] : 0u;        // base of the next column to enter the ring
         for (int i = 0; i < tlen; ++i) {
             const int tb = tb_next;
-            if (i + 1 < tlen) tb_next = target[i + 1];
-            int f = 0, h1, m = 0, mj = -1;
-            if (beg < i - w) beg = i - w;
-            if (end > i + w + 1) end = i + w + 1;
-            if (end > qlen) end = qlen;
-            while (beg - cb >= C) cb += C;
-            // the column the band may reach for the first time in this row enters the ring with the first row's value
-            {
+            if (i + 1 < tlen) tb_next = target[i + 1];        // in flight during the row
+            int f = 0, h1;
+            if constexpr (RING) h1 = bsw_row_head(i, w, qlen, h0, o_del, e_del, beg, end);
+            else { beg = bsw_band_beg(beg, i, w); end = bsw_band_end(end, i, w, qlen); h1 = bsw_first_h1(beg, i, h0, o_del, e_del); }   // (the form this kernel is fast with: meme_bsw_rules.h)
+            if (RING) {
+                while (beg - cb >= C) cb += C;
+                // the column the band may reach for the first time in this row enters the ring with the first row's value
                 const int need = i + w + 1 < qlen ? i + w + 1 : qlen;
                 if (hi < need) {
                     ++hi;
-                    he[BSW_SLOT(hi) * 64] = he_pack(BSW_ROW0(hi), 0, q_next > 4u ? 4u : q_next);
+                    he[slot(hi) * 64] = cw_pack(bsw_row0(h0, oe_ins, e_ins, hi), 0, q_next > 4u ? 4u : q_next);
                     q_next = hi + 1 < qlen ? (unsigned)query[hi + 1] : 0u;      // in flight during the row
                 }
             }
-            if (beg == 0) { h1 = h0 - (o_del + e_del * (i + 1)); if (h1 < 0) h1 = 0; }
-            else h1 = 0;
-            const unsigned sb4 = (unsigned)(sb & 0xff) * 0x01010101u;
-            const unsigned tab_lo = tb > 3 ? 0xffffffffu : (sb4 & ~(0xffu << (8 * tb))) | ((unsigned)(sa & 0xff) << (8 * tb));
-            const unsigned tab_hi = 0xffffffffu;
-            // one cell: `cur_` holds the word of the cell's slot (pc_), the next slot's word (pn_) is requested first
-#define BSW_CELLC(cur_, nxt_, pc_, pn_, mk_, jb_)                                                             \
+            const unsigned tab_lo = cw_score_tab(tb, sa, sb, -1), tab_hi = 0xffffffffu;        // code 4 = N in byte 0 of tab_hi
+            // Four cells per trip with rotating registers for the column state: the next column's LDS word (pn_) is
+            // requested before the current cell (word cur_ of pc_) is computed and first touched a whole cell later (a single rotating
+            // register made the compiler wait for the prefetch in the middle of the cell).  The row maximum and its rightmost
+            // column travel as one key (h << 10 | column), one accumulator per unrolled position (cw_join_keys).
+#define BSW_CELL(cur_, nxt_, pc_, pn_, mk_, jb_)                                                              \
             {                                                                                                  \
-                nxt_ = *(pn_);                                                                                 \
+                nxt_ = *(pn_);                                 /* (j+1 <= qlen: inside the row) */              \
                 int M = (int)((cur_ >> 8) & 0xfffu), e = (int)(cur_ >> 20);                                     \
-                const int sc = (int)(signed char)(__builtin_amdgcn_perm(tab_hi, tab_lo, cur_) & 0xffu);         \
-                M = M ? M + sc : 0;                                                                            \
+                const int sc = cw_score(tab_hi, tab_lo, cur_);                                                 \
+                M = M ? M + sc : 0;                            /* :184 */                                      \
                 const int h = max3_i32(M, e, f);                                                               \
                 const int key = (h << 10) + (jb_);                                                             \
-                mk_ = mk_ > key ? mk_ : key;                                                                   \
-                e = max3_i32(M - oe_del, e - e_del, 0);                                                        \
-                *(pc_) = he_repack(h1, e, cur_);                                                               \
+                mk_ = mk_ > key ? mk_ : key;                   /* rightmost column among equal maxima */       \
+                e = max3_i32(M - oe_del, e - e_del, 0);        /* E(i+1,j) (:190-194) */                       \
+                *(pc_) = cw_repack(h1, e, cur_);               /* H(i,j-1) for the next row (:183) */          \
                 h1 = h;                                                                                        \
-                f = max3_i32(M - oe_ins, f - e_ins, 0);                                                        \
+                f = max3_i32(M - oe_ins, f - e_ins, 0);        /* F(i,j+1) (:195-198) */                       \
             }
-            int s = BSW_SLOT(beg);
+            int s = slot(beg);
             unsigned wa = beg < end ? he[s * 64] : 0u, wb = 0u, wc = 0u, wd = 0u;
             int mk0 = -8, mk1 = -8, mk2 = -8, mk3 = -8;
             int j = beg;
-            while (j < end) {
-                // cells whose next slot is s + 1 (the run up to the ring's seam), four per trip
-                int run = end - j < C - 1 - s ? end - j : C - 1 - s;
+            // (Two forms the linear kernel's speed hangs on, each timed, profiles/bsw_rules_once.md: the loop closed as `if do while (RING && ...)` -- as a
+            // `while (j < end)` the linear kernel kept a loop around its only run, +3.7 % on 150-bp jobs -- and BSW_AT: the linear kernel addresses a cell
+            // by column, so that a trip's first LDS read is issued before the wait for the previous one; through p in both modes it is 2.3 % slower)
+            if (j < end) do {
+                // cells whose next word is the next slot (RING: the run up to the ring's seam; else the whole row), four per trip
+                const int run = RING && C - 1 - s < end - j ? C - 1 - s : end - j;
                 lds_u32 p = he + s * 64;
                 const int j_run = j + run;
+#define BSW_AT(k_) (RING ? p + (k_) * 64 : he + (j + (k_)) * 64)
                 for (; j + 3 < j_run; j += 4, p += 256) {
-                    BSW_CELLC(wa, wb, p, p + 64, mk0, j)
-                    BSW_CELLC(wb, wc, p + 64, p + 128, mk1, j)
-                    BSW_CELLC(wc, wd, p + 128, p + 192, mk2, j)
-                    BSW_CELLC(wd, wa, p + 192, p + 256, mk3, j)
+                    BSW_CELL(wa, wb, BSW_AT(0), BSW_AT(1), mk0, j)
+                    BSW_CELL(wb, wc, BSW_AT(1), BSW_AT(2), mk1, j)
+                    BSW_CELL(wc, wd, BSW_AT(2), BSW_AT(3), mk2, j)
+                    BSW_CELL(wd, wa, BSW_AT(3), BSW_AT(4), mk3, j)
                 }
                 for (; j < j_run; ++j, p += 64) {
-                    BSW_CELLC(wa, wb, p, p + 64, mk0, j)
+                    BSW_CELL(wa, wb, BSW_AT(0), BSW_AT(1), mk0, j)
                     wa = wb;
                 }
-                s += run;
-                if (j < end) {                                 // the cell in the ring's last slot: its right neighbour is slot 0
-                    BSW_CELLC(wa, wb, he + (C - 1) * 64, he, mk0, j)
-                    wa = wb;
-                    ++j; s = 0;
+#undef BSW_AT
+                if (RING) {
+                    s += run;
+                    if (j < end) {                             // the cell in the ring's last slot: its right neighbour is slot 0
+                        BSW_CELL(wa, wb, he + (C - 1) * 64, he, mk0, j)
+                        wa = wb;
+                        ++j; s = 0;
+                    }
                 }
-            }
-#undef BSW_CELLC
-            {
-                mk1 += 1; mk2 += 2; mk3 += 3;
-                const int ka = mk0 > mk1 ? mk0 : mk1, kb = mk2 > mk3 ? mk2 : mk3;
-                const int key = ka > kb ? ka : kb;
-                m = key < 0 ? 0 : key >> 10;
-                mj = key < 0 ? -1 : key & 1023;
-            }
-            const int s_end = BSW_SLOT(end);
-            he[s_end * 64] = he_pack(h1, 0, he[s_end * 64] & QMASK);    // :201
-            const unsigned w_front = he[BSW_SLOT(beg) * 64];
-            if ((beg < end ? end : beg) == qlen) {
-                max_ie = gscore > h1 ? max_ie : i;
-                gscore = gscore > h1 ? gscore : h1;
-            }
-            if (m == 0) break;
-            if (m > max) {
-                max = m; max_i = i; max_j = mj;
-                int off = mj - i;
-                if (off < 0) off = -off;
-                max_off = max_off > off ? max_off : off;
-            } else if (zdrop > 0) {
-                if (i - max_i > mj - max_j) {
-                    if (max - m - ((i - max_i) - (mj - max_j)) * e_del > zdrop) break;
-                } else {
-                    if (max - m - ((mj - max_j) - (i - max_i)) * e_ins > zdrop) break;
-                }
-            }
+            } while (RING && j < end);
+#undef BSW_CELL
+            const int key = cw_join_keys(mk0, mk1, mk2, mk3, 1);
+            const int m = key < 0 ? 0 : key >> 10, mj = key < 0 ? -1 : key & 1023;
+            const int s_end = slot(end);
+            he[s_end * 64] = cw_pack(h1, 0, he[s_end * 64] & QMASK);    // :201
+            const unsigned w_front = he[slot(beg) * 64];       // (for the band trimming below: requested here, used after the row's bookkeeping)
+            if (bsw_row_end(best, i, m, mj, h1, beg, end, qlen, e_del, e_ins, zdrop)) break;
+            // band trimming (:217-221): drop leading / trailing columns whose H and E are both zero
             int jt = beg;
             if (jt < end && (w_front & HE_MASK) == 0u) {
                 ++jt;
-                while (jt < end && (he[BSW_SLOT(jt) * 64] & HE_MASK) == 0u) ++jt;
+                while (jt < end && (he[slot(jt) * 64] & HE_MASK) == 0u) ++jt;
             }
             beg = jt;
             jt = end;
-            if (h1 == 0) {
+            if (h1 == 0) {                                     // (column `end` was just written as {h1, 0}: only a zero there asks for the scan)
                 --jt;
-                while (jt >= beg && (he[BSW_SLOT(jt) * 64] & HE_MASK) == 0u) --jt;
+                while (jt >= beg && (he[slot(jt) * 64] & HE_MASK) == 0u) --jt;
             }
-            end = jt + 2 < qlen ? jt + 2 : qlen;
+            end = bsw_next_end(jt, qlen);
         }
-#undef BSW_SLOT
-#undef BSW_ROW0
-        if (active) {
-            P->score = max;
-            P->qle = max_j + 1;
-            P->tle = max_i + 1;
-            P->gtle = max_ie + 1;
-            P->gscore = gscore;
-            P->max_off = max_off;
-        }
+        if (active) best.store(P);
     }
 }
+
+__global__ void __launch_bounds__(64) k_bsw_lane(LaneArgs A) { bsw_lane_pairs<false>(A, 0); }
+struct LaneCircArgs { LaneArgs L; int C; };
+__global__ void __launch_bounds__(64) k_bsw_lane_circ(LaneCircArgs AC) { bsw_lane_pairs<true>(AC.L, AC.C); }
 
 // ---- counting sort of the pairs by query length (the lanes of a wavefront should finish together) -------------------------
 // Sort key: query length first (LDS size class, column-loop length), then the surplus of target rows over query columns
@@ -788,7 +545,7 @@ int launch_bsw(meme_ctx* ctx, meme_seqpair* d_pairs, const uint8_t* d_ref, const
             i64 blocks = ctx->bsw_blocks > 0 ? ctx->bsw_blocks : dev_cus * 16;
             if (blocks > want) blocks = want;
             // classes whose queries are longer than the band is wide keep 2w + 2 columns in a ring instead of one word per query column
-            // (round 6: 53 KB per wavefront at w = 100 -- three wavefronts per CU -- where the 222 / 318 / 600-column classes hold two / one / one)
+            // (round 6: 52 KB per wavefront at w = 100 -- three wavefronts per CU -- where the 222 / 318 / 600-column classes hold two / one / one)
             const int ring = ((2 * (w > 0 ? w : 0) + 4 + 3) / 4) * 4;        // >= 2w + 2 columns (w = 100: 204 columns = 52 224 bytes, three wavefronts in a CU's 160 KB)
             if (ctx->bsw_circ != 0 && ring < qhi + 2) {
                 const size_t lds = (size_t)ring * 64 * sizeof(unsigned int);

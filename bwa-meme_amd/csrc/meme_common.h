@@ -298,6 +298,8 @@ __device__ __forceinline__ u64 load_pos5(const uint8_t* pos5, i64 i) {
     const u64 v5 = (two >> (8 * (int)(bo & 3))) & 0xffffffffffull;
     return ((v5 & 0xffffffffull) << 8) | (v5 >> 32);
 }
+// base p of the 2-bit text (DevIndex::pac)
+__device__ __forceinline__ int text_base(const u64* pac, i64 p) { return (int)(pac[p >> 5] >> (62 - 2 * (int)(p & 31))) & 3; }
 // 32 bases starting at base offset s from a big-endian-within-word 2-bit array
 __device__ __forceinline__ u64 extract32(const u64* w, i64 s) {
     i64 k = s >> 5;

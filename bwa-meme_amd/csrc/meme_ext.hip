@@ -55,7 +55,6 @@ __device__ __forceinline__ int cal_max_gap(const meme_ext_opt& o, int qlen) {   
     l = l > 1 ? l : 1;
     return l < o.w << 1 ? l : o.w << 1;
 }
-__device__ __forceinline__ int text_base(const u64* pac, i64 p) { return (int)(pac[p >> 5] >> (62 - 2 * (int)(p & 31))) & 3; }
 __device__ __forceinline__ i64 wave_min(i64 v) { for (int d = 32; d >= 1; d >>= 1) { const i64 y = __shfl_xor(v, d); v = y < v ? y : v; } return v; }
 __device__ __forceinline__ i64 wave_max(i64 v) { for (int d = 32; d >= 1; d >>= 1) { const i64 y = __shfl_xor(v, d); v = y > v ? y : v; } return v; }
 __device__ __forceinline__ int pad4(int x) { return (x + 3) & ~3; }

@@ -23,7 +23,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "meme_common.h"
+#include "meme_colword.h"
 
 namespace {
 
@@ -43,17 +43,6 @@ struct KswvArgs {
     const i64* rm_off;           // first row of each wavefront of this launch in the scratch
     int a, b, o_del, e_del, o_ins, e_ins;
 };
-
-typedef __attribute__((address_space(3))) unsigned int* lds_u32;
-
-__device__ __forceinline__ int max3_i32(int a, int b, int c) { int d; asm("v_max3_i32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
-// (f << 12 | h) in bits 8..31 above the low byte of the old word, two instructions
-__device__ __forceinline__ unsigned hf_repack(int h, int f, unsigned old) {
-    unsigned x, w;
-    asm("v_lshl_or_b32 %0, %1, 12, %2" : "=v"(x) : "v"(f), "v"(h));
-    asm("v_perm_b32 %0, %1, %2, %3" : "=v"(w) : "v"(x), "v"(old), "s"(0x06050400u));
-    return w;
-}
 
 struct PassOut { int raw, score, te, qe, score2, te2; };
 
@@ -86,10 +75,7 @@ __device__ __forceinline__ PassOut kswv_pass(lds_u32 W, bool is8, const uint8_t*
     bool mask = false, minsc_ok = false, exited = false;
     int exit_row = -1;
     int tb_next = tlen > 0 ? (int)t[0 <= t_rev ? t_rev : 0] : 4;
-    int wave_rows = tlen;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const int y = __shfl_xor(wave_rows, d); wave_rows = wave_rows > y ? wave_rows : y; }
-    const unsigned mm4 = (unsigned)(w_mismatch & 0xff) * 0x01010101u, am4 = (unsigned)(w_ambig & 0xff) * 0x01010101u;
+    const int wave_rows = wave_max(tlen);
     const unsigned tab_hi = (unsigned)(w_ambig & 0xff);                        // code 4 (N): ambiguous; code 5 (padding): 0
     for (int i = 0; i < wave_rows; ++i) {
         const bool live = i < tlen && !exited;
@@ -97,16 +83,15 @@ __device__ __forceinline__ PassOut kswv_pass(lds_u32 W, bool is8, const uint8_t*
         if (live) {
             const int tb = tb_next;
             if (i + 1 < tlen) tb_next = t[i + 1 <= t_rev ? t_rev - (i + 1) : i + 1];
-            // the row's scores as a byte table indexed by the query code (v_perm_b32 picks byte `code` of {tab_hi, tab_lo})
-            const unsigned tab_lo = tb > 3 ? am4 : (mm4 & ~(0xffu << (8 * tb))) | ((unsigned)(w_match & 0xff) << (8 * tb));
+            const unsigned tab_lo = cw_score_tab(tb, w_match, w_mismatch, w_ambig);
             int e = 0, diag = 0;
             // Four columns per trip with rotating registers (the next word is requested a cell ahead); the row maximum and its FIRST column as
-            // one key (h << 10 | 1023 - column), one accumulator per unrolled position (mk - position, joined below)
+            // one key (h << 10 | 1023 - column), one accumulator per unrolled position (cw_join_keys)
 #define KSWV_CELL(cur_, nxt_, j_, mk_, jr_)                                                                   \
             {                                                                                                  \
                 nxt_ = W[((j_) + 2) * 64];                     /* (one word of slack behind the last column) */  \
                 const int hold = (int)((cur_ >> 8) & 0xfffu), f = (int)(cur_ >> 20);                            \
-                const int sc = (int)(signed char)(__builtin_amdgcn_perm(tab_hi, tab_lo, cur_) & 0xffu);         \
+                const int sc = cw_score(tab_hi, tab_lo, cur_);                                                 \
                 int m = diag + sc;                                                                             \
                 m = m < cap ? m : cap;                                                                         \
                 const int h = max3_i32(m, e, f);               /* (e, f >= 0) */                               \
@@ -114,7 +99,7 @@ __device__ __forceinline__ PassOut kswv_pass(lds_u32 W, bool is8, const uint8_t*
                 mk_ = mk_ > key ? mk_ : key;                                                                   \
                 e = max3_i32(h - oe_ins, e - e_ins, 0);                                                        \
                 const int f2 = max3_i32(h - oe_del, f - e_del, 0);                                             \
-                W[((j_) + 1) * 64] = hf_repack(h, f2, cur_);                                                   \
+                W[((j_) + 1) * 64] = cw_repack(h, f2, cur_);                                                   \
                 diag = hold;                                                                                   \
             }
             unsigned wa = W[64], wb = 0u, wc = 0u, wd = 0u;
@@ -127,9 +112,7 @@ __device__ __forceinline__ PassOut kswv_pass(lds_u32 W, bool is8, const uint8_t*
                 KSWV_CELL(wd, wa, j + 3, mk3, jr)
             }
 #undef KSWV_CELL
-            mk1 -= 1; mk2 -= 2; mk3 -= 3;
-            const int ka = mk0 > mk1 ? mk0 : mk1, kb = mk2 > mk3 ? mk2 : mk3;
-            const int key = ka > kb ? ka : kb;
+            const int key = cw_join_keys(mk0, mk1, mk2, mk3, -1);
             const int imax = key < 0 ? 0 : key >> 10;
             const int iqe = 1023 - (key & 1023);
             if (i > 0) {                                                   // Block I (src/kswv.cpp:505-518, :1063-1078)
@@ -155,9 +138,7 @@ __device__ __forceinline__ PassOut kswv_pass(lds_u32 W, bool is8, const uint8_t*
         const bool on = !(is8 && R.score == 255);
         const int val = (gmax + qmax - 1) / qmax, low = te - val, high = te + val;
         const int last = !on ? -1 : (exited ? exit_row - 1 : tlen - 1);    // rows at and after a stop keep nothing (and were not written)
-        int wave_last = last;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { const int y = __shfl_xor(wave_last, d); wave_last = wave_last > y ? wave_last : y; }
+        const int wave_last = wave_max(last);
         int mx = none, t2 = -1;
         __threadfence_block();
         for (int i = 0; i <= wave_last; ++i) {
@@ -217,43 +198,36 @@ __global__ void __launch_bounds__(64) k_kswv(KswvArgs A) {
 __device__ __forceinline__ int flt_window_base(const u64* __restrict__ pac, i64 l_pac, i64 p) {
     const i64 k = p < l_pac ? p : (l_pac << 1) - 1 - p;
     const i64 kk = (k & ~3ll) + 3 - (k & 3);
-    const int c = kk < l_pac << 1 ? (int)(pac[kk >> 5] >> (62 - 2 * (int)(kk & 31))) & 3 : 0;
+    const int c = kk < l_pac << 1 ? text_base(pac, kk) : 0;
     return p < l_pac ? c : 3 - c;
 }
 
 __device__ __forceinline__ int seedsw_score(lds_u32 W, const u64* __restrict__ pac, i64 l_pac, i64 rb, int tlen, const uint8_t* __restrict__ q, int qlen, const KswvArgs& A) {
     const int w_match = A.a, w_mismatch = -A.b, w_ambig = -1;
     const int oe_del = A.o_del + A.e_del, oe_ins = A.o_ins + A.e_ins, e_del = A.e_del, e_ins = A.e_ins;
-    int wave_q = qlen, wave_rows = tlen;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int y = __shfl_xor(wave_q, d), z = __shfl_xor(wave_rows, d);
-        wave_q = wave_q > y ? wave_q : y;
-        wave_rows = wave_rows > z ? wave_rows : z;
-    }
+    const int wave_q = wave_max(qlen), wave_rows = wave_max(tlen);
     for (int j = 0; j <= wave_q; ++j) {                      // (one word of slack behind the last column)
         unsigned c = 5u;
         if (j < qlen) { c = q[j]; c = c > 4u ? 4u : c; }
         W[(j + 1) * 64] = c;
     }
-    const unsigned mm4 = (unsigned)(w_mismatch & 0xff) * 0x01010101u;
     const unsigned tab_hi = (unsigned)(w_ambig & 0xff);     // code 4 (N): ambiguous; code 5 (past the query): 0
     int gmax = 0;
     for (int i = 0; i < wave_rows; ++i) {
         if (i < tlen) {
             const int tb = flt_window_base(pac, l_pac, rb + i);
-            const unsigned tab_lo = (mm4 & ~(0xffu << (8 * tb))) | ((unsigned)(w_match & 0xff) << (8 * tb));
+            const unsigned tab_lo = cw_score_tab(tb, w_match, w_mismatch, w_ambig);
             int f = 0, diag = 0, rmax = 0;
             unsigned cur = W[64];
             for (int j = 0; j < qlen; ++j) {
                 const unsigned nxt = W[(j + 2) * 64];
                 const int hold = (int)((cur >> 8) & 0xfffu), e = (int)(cur >> 20);
-                const int sc = (int)(signed char)(__builtin_amdgcn_perm(tab_hi, tab_lo, cur) & 0xffu);
+                const int sc = cw_score(tab_hi, tab_lo, cur);
                 const int h = max3_i32(diag + sc, e, f);        // (:274-277; e, f >= 0: _mm_subs_epu16)
                 rmax = rmax > h ? rmax : h;
                 const int e2 = max3_i32(h - oe_del, e - e_del, 0);
                 f = max3_i32(h - oe_ins, f - e_ins, 0);
-                W[(j + 1) * 64] = hf_repack(h, e2, cur);
+                W[(j + 1) * 64] = cw_repack(h, e2, cur);
                 diag = hold;
                 cur = nxt;
             }

@@ -127,7 +127,7 @@ __global__ void __launch_bounds__(256) k_mate_seq(const meme_kswv_job* __restric
     uint8_t* r = ref + J.idr;
     for (int l = lane; l < J.len1; l += 64) {
         const i64 p = X.rb + l;
-        r[l] = (uint8_t)((pac[p >> 5] >> (62 - 2 * (int)(p & 31))) & 3ull);
+        r[l] = (uint8_t)text_base(pac, p);
     }
     const uint8_t* ms = reads + read_off[X.read];
     uint8_t* q = qer + J.idq;

@@ -206,6 +206,29 @@ def test_device_entry_equals_golden_and_oracle(ctx, circ):
         ctx.set_tuning("bsw_circ", 1)
 
 
+@pytest.mark.parametrize("h0_max", [60, 900])
+@pytest.mark.parametrize("w", [7, 100])
+def test_ring_seam_at_exact_query_lengths(w, h0_max):
+    """The ring of k_bsw_lane_circ has C = ((2w + 4 + 3) / 4) * 4 columns (20 for w = 7, 204 for w = 100).  Query lengths around its seam, 130 pairs of each:
+    C - 1 is the last length without a top-up, at C the first topped-up column is `end` itself, 2C is the second lap; h0 up to 900 keeps first-row values
+    positive beyond the first fill.  All six outputs of every pair equal the oracle's, with the ring and with a word per query column."""
+    ring = ((2 * w + 4 + 3) // 4) * 4
+    assert ring == {7: 20, 100: 204}[w]
+    lens = (ring - 2, ring - 1, ring, ring + 1, 2 * ring - 1, 2 * ring, 2 * ring + 1)
+    pairs, ref, qer, want = _oracle(("seam", w, h0_max), lambda: _concat([bsw_gen.make_pairs(130, seed=300 + q + h0_max, min_q=q, max_q=q, h0_max=h0_max) for q in lens]), w)
+    assert pairs.shape[0] == 7 * 130 and set(pairs["len2"].tolist()) == set(lens)
+    c = hipapi.Context(0)
+    try:
+        c.set_tuning("bsw_lane_min_pairs", 0)
+        for circ in (1, 0):
+            c.set_tuning("bsw_circ", circ)
+            got = pairs.copy()
+            c.bsw_batch(got, ref, qer, w, _opt(5))
+            assert np.array_equal(bsw_gen.outputs(got), want), (w, h0_max, circ)
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("max_q", [600, 120])
 def test_host_entry_launches_per_class_beyond_the_one_launch_bound(max_q):
     """launch_bsw sends a batch of fewer than n_cus * 64 * 16 pairs out as ONE launch of the longest query's class; production's 2 M-read chunks are beyond
