@@ -8,15 +8,18 @@
 //   H(i,j)   = max{M, E, F}; the direction byte of the cell (h from M/E/F, e opened or extended, f opened or extended) goes to the
 //   backtrack matrix exactly as the reference stores it, and the backtrack walks it the reference's way -- so that ties (M over E over F)
 //   and with them the placement of gaps in the CIGAR come out the same.
+// What decides that placement is not stated here: the scoring entry, bwa_gen_cigar2's band, the band of a row and the borders of the matrix, the cell,
+// the walk back and the writer of its operations are meme_gcig_rules.h (plain values; tests/test_gcig_rules_model.py runs them on the CPU), and
+// both DP kernels, k_cjob_prep and k_gcig_nogap call them.  This file holds what needs the lanes, once each: F's scan (gcig_fscan), the NM / MD
+// emitter (gcig_md) and the decimal writer (gcig_put_num); and where each kernel keeps H, E, the sequences and the direction bytes.
 // Sequences are not shipped: a job names a read of the batch resident on the ctx, its query span, and a span of the fwd+rc text (2-bit
 // pac64 in HBM); alignments on the reverse strand have both sequences reversed, as bwa_gen_cigar2 does to keep gaps left-aligned.
 #include <string.h>
 
 #include "meme_common.h"
+#include "meme_gcig_rules.h"
 
 namespace {
-
-constexpr int MINUS_INF = -0x40000000;       // src/ksw.cpp:545
 
 struct GcigArgs {
     const meme_gjob* jobs; i64 njobs;
@@ -35,7 +38,77 @@ struct GcigArgs {
     const u64* packed; int pW, pMW, pstride; // the batch's packed reads (2 bits per base + N masks, k_pack_reads): what k_gcig_nogap compares
 };
 
-#define GCIG_DPP(old_, src_, ctrl_, rowmask_) __builtin_amdgcn_update_dpp((old_), (src_), (ctrl_), (rowmask_), 0xF, false)
+// F's scan (gcig_scan_key / gcig_scan_f of the rules): the maximum of the keys of the lanes BELOW each lane of a group of G (a group's lane 0 does not use
+// it), in the register file: row_shr 1/2/4/8, row_bcast15 into rows 1,3 (G >= 32), row_bcast31 into rows 2,3 (G == 64), then wave_shr:1 -- as ds_bpermute
+// shuffles the eight steps were eight LDS round trips on the row's dependent chain, 1 000 of its 1 200 cycles.  Every lane of the wavefront takes part.
+#define GCIG_DPP(src_, ctrl_, rowmask_) __builtin_amdgcn_update_dpp(GCIG_SCAN_FLOOR, (src_), (ctrl_), (rowmask_), 0xF, false)
+template <int G>
+__device__ __forceinline__ int gcig_fscan(int key) {
+    int sg = key, y;
+    y = GCIG_DPP(sg, 0x111, 0xF); sg = sg > y ? sg : y;
+    y = GCIG_DPP(sg, 0x112, 0xF); sg = sg > y ? sg : y;
+    y = GCIG_DPP(sg, 0x114, 0xF); sg = sg > y ? sg : y;
+    y = GCIG_DPP(sg, 0x118, 0xF); sg = sg > y ? sg : y;
+    if (G >= 32) { y = GCIG_DPP(sg, 0x142, 0xA); sg = sg > y ? sg : y; }
+    if (G == 64) { y = GCIG_DPP(sg, 0x143, 0xC); sg = sg > y ? sg : y; }
+    return GCIG_DPP(sg, 0x138, 0xF);
+}
+
+// kputw: v >= 0 in decimal at out[len ..), written where `store`; returns the number of its digits
+__device__ __forceinline__ int gcig_put_num(char* out, int len, int v, bool store) {
+    char buf[12];
+    int l = 0;
+    do { buf[l++] = (char)('0' + v % 10); v /= 10; } while (v);
+    if (store) for (int i = 0; i < l; ++i) out[len + i] = buf[l - 1 - i];
+    return l;
+}
+
+// NM and MD (src/bwa.cpp:322-355) by a group of G lanes (lane gl of the group whose first lane is gbase; gmask: G ones) from a job's n operations in
+// CIGAR order over the (possibly reversed) query qs and target tbase(position).  Matches are compared G bases at a time -- one ballot, then only the
+// mismatches are visited --, deleted bases are written by the lanes side by side; the text of the string is identical on every lane of the group, the lane
+// with `store` writes it.
+struct GcigMd { int nm, len; };
+template <int G, class T>
+__device__ __forceinline__ GcigMd gcig_md(const uint32_t* ops, int n, const uint8_t* qs, T&& tbase, bool rev, int gl, int gbase, unsigned long long gmask, bool store, char* out) {
+    const char* const b2c = rev ? "TGCAN" : "ACGTN";
+    int len = 0, x = 0, y = 0, u = 0, n_mm = 0, n_gap = 0;
+    for (int k = 0; k < n; ++k) {
+        const int op = (int)(ops[k] & 0xf), l = (int)(ops[k] >> 4);
+        if (op == 0) {
+            for (int i0 = 0; i0 < l; i0 += G) {
+                const int i = i0 + gl;
+                const bool in = i < l;
+                int tb = 0, qb = 0;
+                if (in) { tb = tbase(y + i); qb = qs[x + i]; }
+                unsigned long long mask = (__ballot(in && tb != qb) >> gbase) & gmask;
+                int pos0 = 0;
+                while (mask) {
+                    const int b = __builtin_ctzll(mask);
+                    u += b - pos0;
+                    len += gcig_put_num(out, len, u, store);
+                    const int t = __shfl(tb, gbase + b);
+                    if (store) out[len] = b2c[t];
+                    ++len; ++n_mm; u = 0; pos0 = b + 1;
+                    mask &= mask - 1;
+                }
+                u += (l - i0 < G ? l - i0 : G) - pos0;
+            }
+            x += l; y += l;
+        } else if (op == 2) {
+            if (k > 0 && k < n - 1) {        // (a deletion at either end of the CIGAR is not reported: mem_reg2aln squeezes it out)
+                len += gcig_put_num(out, len, u, store);
+                if (store) out[len] = '^';
+                ++len;
+                for (int i = gl; i < l; i += G) out[len + i] = b2c[tbase(y + i)];
+                len += l; u = 0; n_gap += l;
+            }
+            y += l;
+        } else { x += l; n_gap += l; }
+    }
+    len += gcig_put_num(out, len, u, store);
+    if (store) out[len] = 0;
+    return {n_mm + n_gap, len};
+}
 
 // The whole-wavefront kernel described above (`k_gcig` in the comments of this file).
 __global__ void __launch_bounds__(64) k_gcig_t(GcigArgs A) {
@@ -52,206 +125,104 @@ __global__ void __launch_bounds__(64) k_gcig_t(GcigArgs A) {
     uint8_t* ts = qs + ((qlen + 3) & ~3);    // the target bases in row order: a row must not wait for a load from the text (1-2 us each, 250 in a row)
     uint8_t* zl = ts + ((tlen + 3) & ~3);    // the backtrack matrix, when it fits (A.zcap bytes): the walk back is one dependent load per step
     const uint8_t* rd = A.reads + A.read_off[J.read] + J.qb;
+    const auto text_at = [&](int p) -> int { return text_base(A.pac, J.rev ? J.rb + tlen - 1 - p : J.rb + p); };
+    const auto tbase = [&](int p) -> int { return w >= 0 ? (int)ts[p] : text_at(p); };      // (the gap-free shortcut does not load ts)
     for (int j = lane; j < qlen; j += 64) qs[j] = J.rev ? rd[qlen - 1 - j] : rd[j];
-    if (w >= 0) for (int i = lane; i < tlen; i += 64) ts[i] = (uint8_t)text_base(A.pac, J.rev ? J.rb + tlen - 1 - i : J.rb + i);
-    uint32_t* cg = A.cig + A.coff[jb];
-    const int cap = qlen + tlen + 2;
-    int n = 0;                               // operations so far; cg[cap - 1 - k] = k-th pushed
+    if (w >= 0) for (int i = lane; i < tlen; i += 64) ts[i] = (uint8_t)text_at(i);
+    GcigOps ops{A.cig + A.coff[jb], qlen + tlen + 2, true};      // every lane the same walk, every lane stores the same words
     int score;
     if (w < 0) {
         // bwa_gen_cigar2's gap-free shortcut (src/bwa.cpp:295-304: equal lengths and w_ == 0): one M operation, the score summed
         __syncthreads();
         int part = 0;
-        for (int j = lane; j < qlen; j += 64) {
-            const int tb = text_base(A.pac, J.rev ? J.rb + tlen - 1 - j : J.rb + j), qb = qs[j];
-            part += qb > 3 ? -1 : (tb == qb ? A.o.a : -A.o.b);
-        }
+        for (int j = lane; j < qlen; j += 64) part += gcig_score(text_at(j), qs[j], A.o.a, A.o.b);
         for (int d = 32; d; d >>= 1) part += __shfl_xor(part, d);
         score = part;
-        cg[cap - 1] = (unsigned)qlen << 4;
-        n = 1;
+        ops.push(0, qlen);
+        ops.flush();
     } else {
     const int oe_del = A.o.o_del + A.o.e_del, oe_ins = A.o.o_ins + A.o.e_ins, e_del = A.o.e_del, e_ins = A.o.e_ins;
-    const int n_col = qlen < 2 * w + 1 ? qlen : 2 * w + 1;
+    const int n_col = gcig_n_col(qlen, w);
     uint8_t* z = (i64)n_col * tlen <= A.zcap ? zl : A.z + A.zoff[jb];
     int* hp = hA;                            // H(i-1, j-1) at [j]
     int* hn = hB;
-    // first row (src/ksw.cpp:591-595)
     for (int j = lane; j <= qlen; j += 64) {
-        hA[j] = j == 0 ? 0 : (j <= w ? -(A.o.o_ins + e_ins * j) : MINUS_INF);
-        eE[j] = MINUS_INF;
+        hA[j] = gcig_row0(j, w, A.o.o_ins, e_ins);
+        eE[j] = GCIG_MINUS_INF;
     }
     __syncthreads();
     for (int i = 0; i < tlen; ++i) {
         const int tb = ts[i];
-        const int beg = i > w ? i - w : 0;
-        const int end = i + w + 1 < qlen ? i + w + 1 : qlen;
-        int f_in = MINUS_INF;                                         // F(i, first column of the chunk)
-        int h_in = beg == 0 ? -(A.o.o_del + e_del * (i + 1)) : MINUS_INF;   // H(i, beg - 1): what the reference's h1 starts from
+        const int beg = gcig_beg(i, w), end = gcig_end(i, w, qlen);
+        int f_in = GCIG_MINUS_INF;                                    // F(i, first column of the chunk)
+        const int h_in = gcig_left(i, beg, A.o.o_del, e_del);
         if (lane == 0 && beg <= qlen) hn[beg] = h_in;                 // (beg > qlen cannot happen for bands the host check admits: w >= |tlen - qlen|)
         uint8_t* zi = z + (i64)i * n_col;
         for (int cb = beg; cb < end; cb += 64) {
             const int j = cb + lane;
             const bool in = j < end;
-            int m = MINUS_INF, e = MINUS_INF;
+            int m = GCIG_MINUS_INF, e = GCIG_MINUS_INF;
             if (in) {
-                const int qb = qs[j];
-                const int sc = (tb > 3 || qb > 3) ? -1 : (tb == qb ? A.o.a : -A.o.b);      // bwa_fill_scmat (src/bwa.cpp:262-270)
-                m = hp[j] + sc;
+                m = hp[j] + gcig_score(tb, qs[j], A.o.a, A.o.b);
                 e = eE[j];
             }
-            // F along the row: F(i,j) = max( f_in - (j-cb)*e_ins , max_{cb <= k < j} (M(i,k) - oe_ins - (j-1-k)*e_ins) )
-            // as an inclusive max-scan of G_k = M(i,k) - oe_ins + k*e_ins over the lanes, shifted by one lane
-            const int g = in ? m - oe_ins + (j - cb) * e_ins : -2000000000;
-            // (the scan in the register file: row_shr 1/2/4/8, row_bcast15 into rows 1,3, row_bcast31 into rows 2,3, then wave_shr:1 -- as ds_bpermute
-            // shuffles the eight steps were eight LDS round trips on the row's dependent chain, 1 000 of its 1 200 cycles)
-            int sg = g, y;
-            y = GCIG_DPP(-2000000000, sg, 0x111, 0xF); sg = sg > y ? sg : y;
-            y = GCIG_DPP(-2000000000, sg, 0x112, 0xF); sg = sg > y ? sg : y;
-            y = GCIG_DPP(-2000000000, sg, 0x114, 0xF); sg = sg > y ? sg : y;
-            y = GCIG_DPP(-2000000000, sg, 0x118, 0xF); sg = sg > y ? sg : y;
-            y = GCIG_DPP(-2000000000, sg, 0x142, 0xA); sg = sg > y ? sg : y;
-            y = GCIG_DPP(-2000000000, sg, 0x143, 0xC); sg = sg > y ? sg : y;
-            const int ex = GCIG_DPP(-2000000000, sg, 0x138, 0xF);        // max over lanes below (lane 0: not used)
-            // f at this column: from the carry (decayed) or from a column of this chunk
-            const int from_carry = f_in - lane * e_ins;
-            int f = lane == 0 ? f_in : (ex - (lane - 1) * e_ins > from_carry ? ex - (lane - 1) * e_ins : from_carry);
-            // the reference's cell, on this lane's values
-            unsigned d = m >= e ? 0u : 1u;
-            int h = m >= e ? m : e;
-            d = h >= f ? d : 2u;
-            h = h >= f ? h : f;
-            int t = m - oe_del;
-            int e2 = e - e_del;
-            d |= e2 > t ? 1u << 2 : 0u;
-            e2 = e2 > t ? e2 : t;
-            t = m - oe_ins;
-            int f2 = f - e_ins;
-            d |= f2 > t ? 2u << 4 : 0u;
-            f2 = f2 > t ? f2 : t;
-            if (in) { eE[j] = e2; hn[j + 1] = h; zi[j - beg] = (uint8_t)d; }
-            // carry to the next chunk: F(i, cb + 64) = f2 of lane 63
-            f_in = __builtin_amdgcn_readlane(f2, 63);
+            const int f = gcig_scan_f(gcig_fscan<64>(gcig_scan_key(in, m, oe_ins, e_ins, lane)), f_in, e_ins, lane);
+            const GcigCell c = gcig_cell(m, e, f, oe_del, e_del, oe_ins, e_ins);
+            if (in) { eE[j] = c.e; hn[j + 1] = c.h; zi[j - beg] = (uint8_t)c.d; }
+            f_in = __builtin_amdgcn_readlane(c.f, 63);                // carry to the next chunk: F(i, cb + 64)
         }
-        if (lane == 0) eE[end] = MINUS_INF;                              // eh[end].e (:647); eh[end].h was stored by the row's last column
+        if (lane == 0) eE[end] = GCIG_MINUS_INF;                         // eh[end].e (:649); eh[end].h was stored by the row's last column
         __syncthreads();
         int* tsw = hp; hp = hn; hn = tsw;
     }
     score = hp[qlen];
-    // backtrack (src/ksw.cpp:650-664), every lane the same walk; the operations are written from the back of the job's scratch
-    {
-        __threadfence();
-        __syncthreads();
-        int i = tlen - 1, k = (i + w + 1 < qlen ? i + w + 1 : qlen) - 1, which = 0;
-        const i64 zsize = (i64)n_col * tlen;
-        int last_op = -1;
-        unsigned cur = 0;
-        auto push = [&](int op, int len) {
-            if (last_op == op) cur += (unsigned)len << 4;
-            else { if (last_op >= 0) { cg[cap - 1 - n] = cur; ++n; } cur = (unsigned)len << 4 | (unsigned)op; last_op = op; }
-        };
-        // The walk is the same on every lane: the byte it reads goes through readfirstlane so that i, k, `which` and the addresses live in scalar
-        // registers.  Measured (profiles/r05_gcig.md): 21-29 % fewer VALU instructions per job and NO change in the kernel's time -- so the kernel is not
-        // bound by VALU issue; what it IS bound by is open (four explanations refuted, same file).  Kept because it is exact and costs nothing.
-        // A matrix in global memory is walked through a window in LDS: the rows [win_lo, win_hi) the walk is about to cross are fetched by the
-        // whole wavefront at once (a walk straight on HBM is 500 dependent loads of a microsecond each -- ten times the DP above it).
-        const bool windowed = z != zl && A.zcap >= 2 * n_col + 8;
-        const int win_rows = windowed ? (A.zcap - 8) / n_col : 0;
-        i64 win_base = 0, win_b0 = zsize;        // zl[x - win_base] = z[x] for the bytes [win_b0, ..) of the window
-        while (i >= 0 && k >= 0) {
-            i64 zi = (i64)i * n_col + (k - (i > w ? i - w : 0));
-            if (zi < 0) zi = 0;
-            if (zi >= zsize) zi = zsize - 1;
-            if (windowed) {
-                if (zi < win_b0) {
-                    __syncthreads();
-                    const int row = (int)(zi / n_col);      // (the clamps above can leave row i)
-                    const int win_lo = row - win_rows + 1 > 0 ? row - win_rows + 1 : 0;
-                    const i64 b0 = (i64)win_lo * n_col, b1 = (i64)(row + 1) * n_col;
-                    win_b0 = b0;
-                    const uint8_t* src = z + b0;
-                    const int shift = (int)(reinterpret_cast<uintptr_t>(src) & 3);      // dword loads from the aligned address below
-                    const unsigned* src4 = reinterpret_cast<const unsigned*>(src - shift);
-                    unsigned* dst4 = reinterpret_cast<unsigned*>(zl);
-                    const int nd = (int)((b1 - b0 + shift + 3) >> 2);
-                    for (int d = lane; d < nd; d += 64) dst4[d] = src4[d];
-                    win_base = b0 - shift;
-                    __syncthreads();
-                }
-                which = __builtin_amdgcn_readfirstlane((int)zl[zi - win_base]) >> (which << 1) & 3;
-            } else
-            which = __builtin_amdgcn_readfirstlane((int)z[zi]) >> (which << 1) & 3;
-            if (which == 0) { push(0, 1); --i; --k; }
-            else if (which == 1) { push(2, 1); --i; }
-            else { push(1, 1); --k; }
-        }
-        if (i >= 0) push(2, i + 1);
-        if (k >= 0) push(1, k + 1);
-        if (last_op >= 0) { cg[cap - 1 - n] = cur; ++n; }
-    }
-    }
-    if (lane == 0) { meme_gres R; R.score = score; R.n_cigar = n; R.cigar_off = cap - n; A.res[jb] = R; }
-    if (!A.md) return;
-    // NM and MD (src/bwa.cpp:322-355): the operations in CIGAR order over the (possibly reversed) query and target.  Matches are compared 64
-    // bases at a time -- one ballot, then only the mismatches are visited --, deleted bases are written by the lanes side by side; the text
-    // of the string is identical on every lane, lane 0 stores it.
     __threadfence();
     __syncthreads();
-    char* out = A.md + A.mdoff[jb];
-    const char* const b2c = J.rev ? "TGCAN" : "ACGTN";
-    int len = 0, x = 0, y = 0, u = 0, n_mm = 0, n_gap = 0;
-    auto put_num = [&](int v) {              // kputw
-        char buf[12];
-        int l = 0;
-        do { buf[l++] = (char)('0' + v % 10); v /= 10; } while (v);
-        if (lane == 0) for (int i = 0; i < l; ++i) out[len + i] = buf[l - 1 - i];
-        len += l;
-    };
-    for (int k = 0; k < n; ++k) {
-        const unsigned c = cg[cap - n + k];
-        const int op = (int)(c & 0xf), l = (int)(c >> 4);
-        if (op == 0) {
-            for (int i0 = 0; i0 < l; i0 += 64) {
-                const int i = i0 + lane;
-                const bool in = i < l;
-                int tb = 0, qb = 0;
-                if (in) { tb = w >= 0 ? (int)ts[y + i] : text_base(A.pac, J.rev ? J.rb + tlen - 1 - (y + i) : J.rb + y + i); qb = qs[x + i]; }
-                unsigned long long mask = __ballot(in && tb != qb);
-                int pos0 = 0;
-                while (mask) {
-                    const int b = __builtin_ctzll(mask);
-                    u += b - pos0;
-                    put_num(u);
-                    const int t = __shfl(tb, b);
-                    if (lane == 0) out[len] = b2c[t];
-                    ++len; ++n_mm; u = 0; pos0 = b + 1;
-                    mask &= mask - 1;
-                }
-                u += (l - i0 < 64 ? l - i0 : 64) - pos0;
-            }
-            x += l; y += l;
-        } else if (op == 2) {
-            if (k > 0 && k < n - 1) {        // (a deletion at either end of the CIGAR is not reported: mem_reg2aln squeezes it out)
-                put_num(u);
-                if (lane == 0) out[len] = '^';
-                ++len;
-                for (int i = lane; i < l; i += 64) out[len + i] = b2c[w >= 0 ? (int)ts[y + i] : text_base(A.pac, J.rev ? J.rb + tlen - 1 - (y + i) : J.rb + y + i)];
-                len += l; u = 0; n_gap += l;
-            }
-            y += l;
-        } else { x += l; n_gap += l; }
+    // The walk is the same on every lane: the byte it reads goes through readfirstlane so that i, k, `which` and the addresses live in scalar
+    // registers.  Measured (profiles/r05_gcig.md): 21-29 % fewer VALU instructions per job and NO change in the kernel's time -- so the kernel is not
+    // bound by VALU issue; what it IS bound by is open (four explanations refuted, same file).  Kept because it is exact and costs nothing.
+    // A matrix in global memory is walked through a window in LDS: the rows [win_lo, win_hi) the walk is about to cross are fetched by the
+    // whole wavefront at once (a walk straight on HBM is 500 dependent loads of a microsecond each -- ten times the DP above it).  The refill's barriers
+    // stand under conditions that are the same on every lane (zi comes from i, k and `which`), as the walk's loop does.
+    const bool windowed = z != zl && A.zcap >= 2 * n_col + 8;
+    const int win_rows = windowed ? (A.zcap - 8) / n_col : 0;
+    i64 win_base = 0, win_b0 = (i64)n_col * tlen;        // zl[x - win_base] = z[x] for the bytes [win_b0, ..) of the window
+    gcig_walk<i64>(tlen, qlen, w, n_col, [&](i64 zi) -> int {
+        if (!windowed) return __builtin_amdgcn_readfirstlane((int)z[zi]);
+        if (zi < win_b0) {
+            __syncthreads();
+            const int row = (int)(zi / n_col);      // (the walk's clamps can leave row i)
+            const int win_lo = row - win_rows + 1 > 0 ? row - win_rows + 1 : 0;
+            const i64 b0 = (i64)win_lo * n_col, b1 = (i64)(row + 1) * n_col;
+            win_b0 = b0;
+            const uint8_t* src = z + b0;
+            const int shift = (int)(reinterpret_cast<uintptr_t>(src) & 3);      // dword loads from the aligned address below
+            const unsigned* src4 = reinterpret_cast<const unsigned*>(src - shift);
+            unsigned* dst4 = reinterpret_cast<unsigned*>(zl);
+            const int nd = (int)((b1 - b0 + shift + 3) >> 2);
+            for (int d = lane; d < nd; d += 64) dst4[d] = src4[d];
+            win_base = b0 - shift;
+            __syncthreads();
+        }
+        return __builtin_amdgcn_readfirstlane((int)zl[zi - win_base]);
+    }, ops);
     }
-    put_num(u);
-    if (lane == 0) { out[len] = 0; A.nm[jb] = n_mm + n_gap; A.mdlen[jb] = len; }
+    if (lane == 0) { meme_gres R; R.score = score; R.n_cigar = ops.n; R.cigar_off = ops.cigar_off(); A.res[jb] = R; }
+    if (!A.md) return;
+    __threadfence();
+    __syncthreads();
+    const GcigMd M = gcig_md<64>(ops.cg + ops.cigar_off(), ops.n, qs, tbase, J.rev != 0, lane, 0, ~0ull, lane == 0, A.md + A.mdoff[jb]);
+    if (lane == 0) { A.nm[jb] = M.nm; A.mdlen[jb] = M.len; }
 }
 
 // Several jobs per wavefront (round 6).  k_gcig above gives a job all 64 lanes and runs its rows one after the other; the bands bwa_gen_cigar2
 // computes for short reads are 5-15 columns wide, so ~9 of the 64 lanes work and the kernel's time follows its instruction count
-// (profiles/r05_gcig.md).  Here a job whose band has at most G columns (G = 16, 32 or 64: one, two or four DPP rows; G = 64 is one job per wavefront again, without the chunk loop and with the rings) takes a GROUP of G lanes and a wavefront
-// runs 64 / G jobs side by side: the same instruction stream, 4 or 2 jobs per instruction.  A row is ONE chunk (end - beg <= 2w + 1 <= G), so F's
-// max-plus scan needs the row_shr steps only (+ row_bcast15 for G = 32) and no carry.  H and E live in rings of 2G entries (a row reads what the row
-// before wrote inside its band, never beyond: indices modulo the ring), the backtrack matrix (<= G x tlen bytes) always in LDS; the walk back runs
-// per lane, identical within a group.  Same cell, same direction bytes, same walk as above -- so the same CIGAR, NM and MD.
+// (profiles/r05_gcig.md).  Here a job whose band has at most G columns (G = 16, 32 or 64: one, two or four DPP rows; G = 64 is one job per wavefront
+// again, without the chunk loop and with the rings) takes a GROUP of G lanes and a wavefront runs 64 / G jobs side by side: the same instruction
+// stream, 4 or 2 jobs per instruction.  A row is ONE chunk (end - beg <= 2w + 1 <= G), so F's scan stays inside the group's DPP rows and carries
+// nothing in.  H and E live in rings of 2G entries (a row reads what the row before wrote inside its band, never beyond: indices modulo the ring),
+// the backtrack matrix (<= G x tlen bytes) always in LDS; the walk back runs per lane, identical within a group.  The rules, the scan and the
+// emitter are k_gcig's -- so the same CIGAR, NM and MD.
 template <int G>
 __global__ void __launch_bounds__(64) k_gcig_grp(GcigArgs A) {
     extern __shared__ int lds[];
@@ -274,18 +245,17 @@ __global__ void __launch_bounds__(64) k_gcig_grp(GcigArgs A) {
     uint8_t* zl = ts + A.grp_tcap;
     if (live) {
         const uint8_t* rd = A.reads + A.read_off[J.read] + J.qb;
-        for (int j = gl; j < qlen; j += G) qs[j] = J.rev ? rd[qlen - 1 - j] : rd[j];
-        for (int i = gl; i < tlen; i += G) ts[i] = (uint8_t)text_base(A.pac, J.rev ? J.rb + tlen - 1 - i : J.rb + i);
+        // (the strand picks the 32-bit index, not one of two 64-bit addresses: in the loops' eight unrolled copies that is two VGPRs of the kernel)
+        for (int j = gl; j < qlen; j += G) qs[j] = rd[J.rev ? qlen - 1 - j : j];
+        for (int i = gl; i < tlen; i += G) ts[i] = (uint8_t)text_base(A.pac, J.rb + (J.rev ? tlen - 1 - i : i));
     }
-    uint32_t* cg = A.cig + (live ? A.coff[jb] : 0);
-    const int cap = qlen + tlen + 2;
-    int n = 0;
+    GcigOps ops{A.cig + (live ? A.coff[jb] : 0), qlen + tlen + 2, gl == 0};         // every lane of the group the same walk (a dead group: no cell, no operation)
     const int oe_del = A.o.o_del + A.o.e_del, oe_ins = A.o.o_ins + A.o.e_ins, e_del = A.o.e_del, e_ins = A.o.e_ins;
-    const int n_col = qlen < 2 * w + 1 ? qlen : 2 * w + 1;
-    // first row (src/ksw.cpp:591-595): the columns row 0 can read.  The cells left of the band and E above a column the band has just reached are not kept in the
-    // rings: H(i-1, -1) is arithmetic (-(o_del + e_del * i), 0 for the first row) and E of a column at or beyond the previous row's end is -inf (:647) -- two
+    const int n_col = gcig_n_col(qlen, w);
+    // The first row: the columns row 0 can read.  The cells left of the band and E above a column the band has just reached are not kept in the rings: H(i-1, -1)
+    // is arithmetic (gcig_corner) and E of a column at or beyond the previous row's end (gcig_end_above) is -inf -- two
     // single-lane stores per row less, and every load of a row is unconditional (lanes beyond the band compute on whatever the ring holds and store nothing).
-    for (int j = gl + 1; j <= qlen && j <= w + 1; j += G) hA[j & RM] = j <= w ? -(A.o.o_ins + e_ins * j) : MINUS_INF;
+    for (int j = gl + 1; j <= qlen && j <= w + 1; j += G) hA[j & RM] = gcig_row0(j, w, A.o.o_ins, e_ins);
     int tl_max = tlen;
     for (int d = 32; d >= G; d >>= 1) { const int o = __shfl_xor(tl_max, d); tl_max = tl_max > o ? tl_max : o; }
     __syncthreads();
@@ -294,118 +264,29 @@ __global__ void __launch_bounds__(64) k_gcig_grp(GcigArgs A) {
     for (int i = 0; i < tl_max; ++i) {
         const bool row = i < tlen;
         const int tb = ts[i < tlen ? i : 0];
-        const int beg = i > w ? i - w : 0;
-        const int end = i + w + 1 < qlen ? i + w + 1 : qlen;
-        const int end_prev = i == 0 ? 0 : (i + w < qlen ? i + w : qlen);
+        const int beg = gcig_beg(i, w), end = gcig_end(i, w, qlen), end_prev = gcig_end_above(i, w, qlen);
         const int j = beg + gl;
         const bool in = row && j < end;
         const int qb = qs[j];
         const int hprev = hp[j & RM], eprev = eE[j & RM];
-        const int sc = (tb > 3 || qb > 3) ? -1 : (tb == qb ? A.o.a : -A.o.b);
-        const int m = (j == 0 ? (i == 0 ? 0 : -(A.o.o_del + e_del * i)) : hprev) + sc;
-        const int e = j >= end_prev ? MINUS_INF : eprev;
-        const int g = in ? m - oe_ins + gl * e_ins : -2000000000;
-        int sg = g, y;
-        y = GCIG_DPP(-2000000000, sg, 0x111, 0xF); sg = sg > y ? sg : y;
-        y = GCIG_DPP(-2000000000, sg, 0x112, 0xF); sg = sg > y ? sg : y;
-        y = GCIG_DPP(-2000000000, sg, 0x114, 0xF); sg = sg > y ? sg : y;
-        y = GCIG_DPP(-2000000000, sg, 0x118, 0xF); sg = sg > y ? sg : y;
-        if (G >= 32) { y = GCIG_DPP(-2000000000, sg, 0x142, 0xA); sg = sg > y ? sg : y; }
-        if (G == 64) { y = GCIG_DPP(-2000000000, sg, 0x143, 0xC); sg = sg > y ? sg : y; }
-        const int ex = GCIG_DPP(-2000000000, sg, 0x138, 0xF);            // the lane below (a group's lane 0 does not use it)
-        const int f = gl == 0 ? MINUS_INF : (ex - (gl - 1) * e_ins > MINUS_INF - gl * e_ins ? ex - (gl - 1) * e_ins : MINUS_INF - gl * e_ins);
-        unsigned d = m >= e ? 0u : 1u;
-        int h = m >= e ? m : e;
-        d = h >= f ? d : 2u;
-        h = h >= f ? h : f;
-        int t = m - oe_del;
-        int e2 = e - e_del;
-        d |= e2 > t ? 1u << 2 : 0u;
-        e2 = e2 > t ? e2 : t;
-        t = m - oe_ins;
-        const int f2 = f - e_ins;
-        d |= f2 > t ? 2u << 4 : 0u;
-        if (in) { eE[j & RM] = e2; hn[(j + 1) & RM] = h; zl[i * n_col + gl] = (uint8_t)d; }
+        const int sc = gcig_score(tb, qb, A.o.a, A.o.b);
+        const int m = (j == 0 ? gcig_corner(i, A.o.o_del, e_del) : hprev) + sc;
+        const int e = j >= end_prev ? GCIG_MINUS_INF : eprev;
+        const int f = gcig_scan_f(gcig_fscan<G>(gcig_scan_key(in, m, oe_ins, e_ins, gl)), GCIG_MINUS_INF, e_ins, gl);
+        const GcigCell c = gcig_cell(m, e, f, oe_del, e_del, oe_ins, e_ins);
+        if (in) { eE[j & RM] = c.e; hn[(j + 1) & RM] = c.h; zl[i * n_col + gl] = (uint8_t)c.d; }
         __syncthreads();
         if (row) { int* tsw = hp; hp = hn; hn = tsw; }
     }
     const int score = live ? hp[qlen & RM] : 0;
-    // backtrack (src/ksw.cpp:650-664): every lane of the group the same walk
-    {
-        int i = tlen - 1, k = (i + w + 1 < qlen ? i + w + 1 : qlen) - 1, which = 0;
-        const int zsize = n_col * tlen;
-        int last_op = -1;
-        unsigned cur = 0;
-        auto push = [&](int op, int len) {
-            if (last_op == op) cur += (unsigned)len << 4;
-            else { if (last_op >= 0) { if (gl == 0) cg[cap - 1 - n] = cur; ++n; } cur = (unsigned)len << 4 | (unsigned)op; last_op = op; }
-        };
-        while (i >= 0 && k >= 0) {
-            int zi = i * n_col + (k - (i > w ? i - w : 0));
-            if (zi < 0) zi = 0;
-            if (zi >= zsize) zi = zsize - 1;
-            which = (int)zl[zi] >> (which << 1) & 3;
-            if (which == 0) { push(0, 1); --i; --k; }
-            else if (which == 1) { push(2, 1); --i; }
-            else { push(1, 1); --k; }
-        }
-        if (i >= 0) push(2, i + 1);
-        if (k >= 0) push(1, k + 1);
-        if (last_op >= 0) { if (gl == 0) cg[cap - 1 - n] = cur; ++n; }
-    }
-    if (live && gl == 0) { meme_gres Rr; Rr.score = score; Rr.n_cigar = n; Rr.cigar_off = cap - n; A.res[jb] = Rr; }
+    gcig_walk<int>(tlen, qlen, w, n_col, [&](int zi) -> int { return zl[zi]; }, ops);
+    if (live && gl == 0) { meme_gres Rr; Rr.score = score; Rr.n_cigar = ops.n; Rr.cigar_off = ops.cigar_off(); A.res[jb] = Rr; }
     if (!A.md) return;
-    // NM and MD (src/bwa.cpp:322-355), as in k_gcig with the group's G lanes
     __threadfence();
     __syncthreads();
-    char* out = A.md + (live ? A.mdoff[jb] : 0);
-    const char* const b2c = J.rev ? "TGCAN" : "ACGTN";
-    int len = 0, x = 0, y = 0, u = 0, n_mm = 0, n_gap = 0;
-    auto put_num = [&](int v) {
-        char buf[12];
-        int l = 0;
-        do { buf[l++] = (char)('0' + v % 10); v /= 10; } while (v);
-        if (gl == 0) for (int i = 0; i < l; ++i) out[len + i] = buf[l - 1 - i];
-        len += l;
-    };
-    for (int k = 0; k < n; ++k) {
-        const unsigned c = cg[cap - n + k];
-        const int op = (int)(c & 0xf), l = (int)(c >> 4);
-        if (op == 0) {
-            for (int i0 = 0; i0 < l; i0 += G) {
-                const int i = i0 + gl;
-                const bool in = i < l;
-                int tb = 0, qb = 0;
-                if (in) { tb = (int)ts[y + i]; qb = qs[x + i]; }
-                unsigned long long mask = (__ballot(in && tb != qb) >> gbase) & GMASK;
-                int pos0 = 0;
-                while (mask) {
-                    const int b = __builtin_ctzll(mask);
-                    u += b - pos0;
-                    put_num(u);
-                    const int t = __shfl(tb, gbase + b);
-                    if (gl == 0) out[len] = b2c[t];
-                    ++len; ++n_mm; u = 0; pos0 = b + 1;
-                    mask &= mask - 1;
-                }
-                u += (l - i0 < G ? l - i0 : G) - pos0;
-            }
-            x += l; y += l;
-        } else if (op == 2) {
-            if (k > 0 && k < n - 1) {
-                put_num(u);
-                if (gl == 0) out[len] = '^';
-                ++len;
-                for (int i = gl; i < l; i += G) out[len + i] = b2c[(int)ts[y + i]];
-                len += l; u = 0; n_gap += l;
-            }
-            y += l;
-        } else { x += l; n_gap += l; }
-    }
-    if (live) {
-        put_num(u);
-        if (gl == 0) { out[len] = 0; A.nm[jb] = n_mm + n_gap; A.mdlen[jb] = len; }
-    }
+    const GcigMd M = gcig_md<G>(ops.cg + ops.cigar_off(), ops.n, qs, [&](int p) -> int { return ts[p]; }, J.rev != 0, gl, gbase, GMASK, live && gl == 0,
+                                A.md + (live ? A.mdoff[jb] : 0));
+    if (live && gl == 0) { A.nm[jb] = M.nm; A.mdlen[jb] = M.len; }
 }
 
 // bwa_gen_cigar2's gap-free shortcut (src/bwa.cpp:295-304) for the jobs of a batch that take it, ONE LANE per job: the query span against
@@ -428,13 +309,6 @@ __global__ void __launch_bounds__(256) k_gcig_nogap(GcigArgs A) {
         const char* const b2c = J.rev ? "TGCA" : "ACGT";
         const int nblk = (qlen + 31) >> 5;
         int len = 0, n_mm = 0, n_n = 0, last = J.rev ? qlen : -1;
-        auto put_run = [&](int run) {
-            char buf[12];
-            int l = 0;
-            do { buf[l++] = (char)('0' + run % 10); run /= 10; } while (run);
-            for (int i = 0; i < l; ++i) out[len + i] = buf[l - 1 - i];
-            len += l;
-        };
         for (int kk = 0; kk < nblk; ++kk) {
             const int k = J.rev ? nblk - 1 - kk : kk;
             const int p0 = J.qb + 32 * k, nvalid = qlen - 32 * k < 32 ? qlen - 32 * k : 32;
@@ -459,12 +333,12 @@ __global__ void __launch_bounds__(256) k_gcig_nogap(GcigArgs A) {
                     const int i = J.rev ? 31 - (__builtin_ctzll(y) >> 1) : (__clzll((long long)y) >> 1);
                     y &= ~(1ull << (62 - 2 * i));
                     const int j = 32 * k + i;
-                    put_run(J.rev ? last - j - 1 : j - last - 1);
+                    len += gcig_put_num(out, len, J.rev ? last - j - 1 : j - last - 1, true);
                     out[len++] = b2c[(int)(t >> (62 - 2 * i)) & 3];
                     last = j;
                 }
         }
-        if (out) { put_run(J.rev ? last : qlen - last - 1); out[len] = 0; A.nm[jb] = n_mm; A.mdlen[jb] = len; }
+        if (out) { len += gcig_put_num(out, len, J.rev ? last : qlen - last - 1, true); out[len] = 0; A.nm[jb] = n_mm; A.mdlen[jb] = len; }
         const int cap = qlen + J.tlen + 2;
         A.cig[A.coff[jb] + cap - 1] = (unsigned)qlen << 4;
         meme_gres R;
@@ -491,7 +365,7 @@ __global__ void __launch_bounds__(256) k_gcig_sizes(const meme_gjob* __restrict_
     for (i64 jb = (i64)blockIdx.x * blockDim.x + threadIdx.x; jb < njobs; jb += (i64)gridDim.x * blockDim.x) {
         const meme_gjob J = jobs[jb];
         const bool dp = !(fast && nogap_fast(J, read_off));
-        const i64 n_col = J.qlen < 2 * J.w + 1 ? J.qlen : 2 * J.w + 1;
+        const i64 n_col = gcig_n_col(J.qlen, J.w);
         const bool g16 = dp && J.w >= 0 && n_col <= 16 && n_col * J.tlen <= z16;
         const bool g32 = dp && !g16 && J.w >= 0 && n_col <= 32 && n_col * J.tlen <= z32;
         const bool g64 = dp && !g16 && !g32 && J.w >= 0 && n_col <= 64 && n_col * J.tlen <= z64;
@@ -529,25 +403,14 @@ __global__ void __launch_bounds__(256) k_gcig_check(const meme_gjob* __restrict_
     }
 }
 
-// bwa_gen_cigar2's own preamble (src/bwa.cpp:288-316) for a batch of its calls: the strand from rb, the gap-free shortcut (equal lengths,
-// w_ == 0: band -1 here) or the band it hands to ksw_global2
+// bwa_gen_cigar2's own preamble (src/bwa.cpp:288-316) for a batch of its calls: the strand from rb, and gcig_band -- the gap-free shortcut (band -1 here)
+// or the band it hands to ksw_global2
 __global__ void __launch_bounds__(256) k_cjob_prep(const meme_cjob* __restrict__ cj, i64 njobs, i64 l_pac, meme_bsw_opt o, meme_gjob* __restrict__ jobs) {
     for (i64 jb = (i64)blockIdx.x * blockDim.x + threadIdx.x; jb < njobs; jb += (i64)gridDim.x * blockDim.x) {
         const meme_cjob C = cj[jb];
         meme_gjob J;
         J.rb = C.rb; J.read = C.read; J.qb = C.qb; J.qlen = C.qlen; J.tlen = C.tlen; J.rev = C.rb >= l_pac ? 1 : 0;
-        if (C.qlen == C.tlen && C.w_ == 0) J.w = -1;
-        else {
-            const int max_ins = (int)((double)(((C.qlen + 1) >> 1) * o.a - o.o_ins) / o.e_ins + 1.);
-            const int max_del = (int)((double)(((C.qlen + 1) >> 1) * o.a - o.o_del) / o.e_del + 1.);
-            int max_gap = max_ins > max_del ? max_ins : max_del;
-            max_gap = max_gap > 1 ? max_gap : 1;
-            const int dl = C.tlen > C.qlen ? C.tlen - C.qlen : C.qlen - C.tlen;
-            int w = (max_gap + dl + 1) >> 1;
-            w = w < C.w_ ? w : C.w_;
-            w = w > dl + 3 ? w : dl + 3;
-            J.w = w;
-        }
+        J.w = gcig_band(C.qlen, C.tlen, C.w_, o);
         jobs[jb] = J;
     }
 }

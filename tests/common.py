@@ -455,6 +455,18 @@ def gencig_workload(n=2500, seed=177, read_len=(40, 251), bands=(0, 1, 3, 10, 30
     return g, reads, calls
 
 
+def cjob_band(qlen, tlen, w_, a=1, o_del=6, e_del=1, o_ins=6, e_ins=1):
+    """k_cjob_prep = bwa_gen_cigar2's preamble (src/bwa.cpp:288-316): the band ksw_global2 gets, -1 for the gap-free shortcut"""
+    qlen, tlen, w_ = (np.asarray(x, np.int64) for x in (qlen, tlen, w_))
+    half = ((qlen + 1) >> 1) * a
+    max_ins = ((half - o_ins) / e_ins + 1.).astype(np.int64)            # (int) of a double: towards zero, as astype does
+    max_del = ((half - o_del) / e_del + 1.).astype(np.int64)
+    max_gap = np.maximum(np.maximum(max_ins, max_del), 1)
+    dl = np.abs(tlen - qlen)
+    w = np.maximum(np.minimum((max_gap + dl + 1) >> 1, w_), dl + 3)
+    return np.where((qlen == tlen) & (w_ == 0), -1, w)
+
+
 def sam_workload(n=1500, seed=301, read_len=(30, 251)):
     """Inputs of the SAM-text tests (tests/golden/sam_golden.npz): records the way mem_reg2aln / mem_sam_pe leave them for mem_aln2sam -- mapped and
     unmapped ends, mates mapped / unmapped / on another contig / absent (single-end), both strands, CIGARs with clipping, insertions, deletions

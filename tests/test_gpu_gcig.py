@@ -1,12 +1,13 @@
 """The CIGAR kernel (meme_global_batch_host = ksw_global2 under bwa_gen_cigar2), through the C ABI, against score and CIGAR of the
 compiled reference (tests/golden/gcig_golden.npz) and against the oracle with other penalties."""
 import os
+import re
 
 import numpy as np
 import pytest
 
 import oracle_py as O
-from common import GOLDEN, build_index, gcig_workload, gencig_workload
+from common import GOLDEN, build_index, cjob_band, gcig_workload, gencig_workload
 from pymeme import hipapi, synth
 
 pytestmark = pytest.mark.gpu
@@ -184,18 +185,6 @@ def _class_counts(cls):
     return [int((cls == k).sum()) for k in range(6)]
 
 
-def _cjob_band(qlen, tlen, w_, a=1, o_del=6, e_del=1, o_ins=6, e_ins=1):
-    """k_cjob_prep = bwa_gen_cigar2's preamble (src/bwa.cpp:288-316): the band ksw_global2 gets, -1 for the gap-free shortcut"""
-    qlen, tlen, w_ = (np.asarray(x, np.int64) for x in (qlen, tlen, w_))
-    half = ((qlen + 1) >> 1) * a
-    max_ins = ((half - o_ins) / e_ins + 1.).astype(np.int64)            # (int) of a double: towards zero, as astype does
-    max_del = ((half - o_del) / e_del + 1.).astype(np.int64)
-    max_gap = np.maximum(np.maximum(max_ins, max_del), 1)
-    dl = np.abs(tlen - qlen)
-    w = np.maximum(np.minimum((max_gap + dl + 1) >> 1, w_), dl + 3)
-    return np.where((qlen == tlen) & (w_ == 0), -1, w)
-
-
 # matrix in LDS / walked through a window / walked straight on global memory, of the 4 000 jobs of gcig_workload() when all go to k_gcig_t
 _ZCAP_SPLIT = {0: (0, 0, 4000), 64: (0, 1183, 2817), 2048: (777, 3223, 0), 8192: (2187, 1813, 0), 24576: (3280, 720, 0)}
 
@@ -252,7 +241,7 @@ def test_every_matrix_storage_mode_gives_the_golden_gen_cigar_results(tmp_path, 
     want = [(int(G["score"][k]), G["cigars"][off[k]:off[k + 1]], int(G["nm"][k]), mds[k]) for k in range(calls.shape[0])]
     groups = _groups_on()
     q, t = calls["qlen"], calls["tlen"]
-    w = _cjob_band(q, t, calls["w_"])
+    w = cjob_band(q, t, calls["w_"])
     zc, _, cls, n_col = _plan(q, t, w, groups, zcap)
     mine = cls == 2
     assert zc == zcap and mine.sum() > 0 and (cls == 3).sum() > 0
@@ -305,7 +294,7 @@ def test_short_reads_take_the_whole_matrix_mode_by_default(tmp_path):
         ctx.close()
     g, reads, calls = gencig_workload(n=600, seed=303, read_len=(40, 151))
     assert int(calls["tlen"].max()) * 33 <= _Z_LDS_CAP
-    w = _cjob_band(calls["qlen"], calls["tlen"], calls["w_"])
+    w = cjob_band(calls["qlen"], calls["tlen"], calls["w_"])
     zc, _, cls, _ = _plan(calls["qlen"], calls["tlen"], w, groups)
     assert zc == _Z_LDS_CAP and (cls == 2).sum() > 0
     text = hipapi.fwd_rc_text(g)
@@ -338,7 +327,7 @@ def test_reads_of_251_to_500_bases(tmp_path):
         ctx.close()
     g, reads, calls = gencig_workload(n=300, seed=313, read_len=(251, 501), bands=(0,) + bands)
     text = hipapi.fwd_rc_text(g)
-    w = _cjob_band(calls["qlen"], calls["tlen"], calls["w_"])
+    w = cjob_band(calls["qlen"], calls["tlen"], calls["w_"])
     _, _, cls, _ = _plan(calls["qlen"], calls["tlen"], w, groups)
     (tmp_path / "calls").mkdir()
     ctx = _ctx_with_reads(tmp_path / "calls", g, reads)
@@ -385,7 +374,7 @@ def test_one_long_target_switches_a_group_class_off_for_the_batch(tmp_path):
             calls[f] = jobs[f]
         calls["w_"] = jobs["w"]
         res, cig, md, _ = ctx.gen_cigar_batch_host(calls)
-        wc = _cjob_band(calls["qlen"], calls["tlen"], calls["w_"])
+        wc = cjob_band(calls["qlen"], calls["tlen"], calls["w_"])
         assert list(ctx.timings().gcig_class_jobs) == _class_counts(_plan(calls["qlen"], calls["tlen"], wc, _groups_on())[2])
         want = [O.gen_cigar2(text, g.shape[0], reads[int(J["read"])][int(J["qb"]):int(J["qb"]) + int(J["qlen"])], int(J["rb"]), int(J["rb"]) + int(J["tlen"]), int(J["w_"]))
                 for J in calls]
@@ -416,3 +405,149 @@ def test_max_batch_refuses_more_jobs_and_takes_that_many(tmp_path):
     finally:
         ctx.close()
         free.close()
+
+
+# ---- the shapes at which what the DP kernels share can go wrong: the rules of csrc/meme_gcig_rules.h in both kernels' storage, F's scan at every group width and
+# ---- across the chunk seam, the NM / MD emitter at every group width ----------------------------------------------------------------------------------------
+_EDGE_W = {7: 0, 8: 1, 15: 1, 16: 4, 31: 4, 32: 2}        # band -> 2w + 1 = 15, 17, 31, 33, 63, 65 band columns -> the class with groups on (slot of gcig_class_jobs)
+_EDGE_Q = {16: 0, 17: 1, 32: 1, 33: 4, 64: 4, 65: 2}      # the same numbers of columns as the query's length under a band of 100
+_MD_W = {0: 3, 7: 0, 15: 1, 31: 4, 100: 2}                # band ARGUMENT of a 150-base call without length difference -> its class (0: the gap-free shortcut)
+# mismatch positions of 150-base calls: match runs of exactly G, G + 1 and 2G between them for G = 16, 32, 64 (64: two calls), and mismatches in the last lane of
+# a group and the first lane of the next
+_MD_RUNS = {16: [(5, 22, 40, 73)], 32: [(5, 38, 72, 137)], 64: [(3, 68, 134), (10, 139)], 0: [(15, 16, 31, 32, 63, 64)]}
+
+
+class _Posed:
+    """Jobs posed in the frame the kernels align in (on the reverse strand both sequences reversed): a target is drawn from the text, the query is built
+    against it in that frame, add() stores the read the job names."""
+
+    def __init__(self, g, seed):
+        self.text, self.l_pac, self.rng = hipapi.fwd_rc_text(g), g.shape[0], np.random.default_rng(seed)
+        self.reads, self.jobs, self.calls, self.seqs = [], [], [], []
+        self.want_j, self.want_c, self.n = [], [], 0
+
+    def target(self, tlen):
+        self.n += 1                                                  # strands alternate
+        rb = int(self.rng.integers(1000, self.l_pac - 1000 - tlen)) + (self.n & 1) * self.l_pac
+        t = self.text[rb:rb + tlen]
+        return rb, (t[::-1] if self.n & 1 else t).copy()
+
+    def noisy(self, t):
+        q = t.copy()
+        hit = self.rng.random(q.shape[0]) < 0.02
+        q[hit] = (q[hit] + self.rng.integers(1, 4, size=int(hit.sum()))) & 3
+        return q
+
+    def fit(self, q, qlen):
+        """q cut or filled with random bases to qlen"""
+        return np.concatenate([q, self.rng.integers(0, 4, size=max(qlen - q.shape[0], 0)).astype(np.uint8)])[:qlen]
+
+    def add(self, q, rb, t, w, cls, call=False):
+        rev = int(rb >= self.l_pac)
+        q = np.ascontiguousarray(q, np.uint8)
+        assert q.shape[0] <= 150
+        self.reads.append(q[::-1].copy() if rev else q)
+        if call:
+            self.calls.append((rb, len(self.reads) - 1, 0, q.shape[0], t.shape[0], w, 0)); self.want_c.append(cls)
+        else:
+            self.jobs.append((rb, len(self.reads) - 1, 0, q.shape[0], t.shape[0], w, rev)); self.want_j.append(cls); self.seqs.append((q, t))
+
+
+def _shared_piece_jobs(g):
+    P = _Posed(g, 401)
+    rng = P.rng
+    # ksw_global2 jobs: the band columns on both sides of every class edge, through the band and through the query's length; tlen - qlen in -3 .. 3
+    for edge, reps in ((_EDGE_W, 3), (_EDGE_Q, 2)):
+        for x, cls in edge.items():
+            for dl in range(-3, 4):
+                for _ in range(reps):
+                    qlen, w = (int(rng.integers(100, 151)), x) if edge is _EDGE_W else (x, 100)
+                    rb, t = P.target(qlen + dl)
+                    P.add(P.fit(P.noisy(t), qlen), rb, t, w, cls)
+    # two and three chunks of 64 columns per row, with an insertion of 10-40 bases whose run crosses query column 63|64 (w = 64, 100: in a row below w, the
+    # chunks start at column 0 and F is carried across the seam)
+    for w in (33, 64, 100):
+        for dl in range(-3, 4):
+            for _ in range(4):
+                L = int(rng.integers(10, min(40, w - 6) + 1))
+                p = int(rng.integers(64 - L + 3, 61))
+                rb, t = P.target(150 - L + dl)
+                q = np.concatenate([P.noisy(t[:p]), rng.integers(0, 4, size=L).astype(np.uint8), P.noisy(t[p:])])
+                P.add(P.fit(q, 150), rb, t, w, 2)
+    # bwa_gen_cigar2 calls for the MD emitter: the runs and lane positions above, through every class
+    for G, pats in _MD_RUNS.items():
+        for pat in pats:
+            for w_, cls in _MD_W.items():
+                for _ in range(2):                                   # both strands
+                    rb, t = P.target(150)
+                    q = t.copy()
+                    q[list(pat)] = (q[list(pat)] + 1) & 3
+                    P.add(q, rb, t, w_, cls, call=True)
+    # deletions longer than a group writes at once, in the class whose group is one base narrower (the band columns are the query's) and in longer queries
+    for qlen, D, cls in ((16, 17, 0), (32, 33, 1), (64, 65, 4), (100, 17, None), (100, 33, None), (100, 65, 2)):
+        for _ in range(2):
+            rb, t = P.target(qlen + D)
+            P.add(np.concatenate([t[:qlen // 2], t[qlen // 2 + D:]]), rb, t, 100, cls, call=True)
+    # a deletion as the first and as the last operation: not reported
+    for w_ in (7, 15, 31, 100):
+        for first in (0, 0, 1, 1):
+            rb, t = P.target(123)
+            P.add(t[3:] if first else t[:120], rb, t, w_, None, call=True)
+    return P
+
+
+def _ops(cg):
+    return [(int(c) & 0xf, int(c) >> 4) for c in cg]
+
+
+def test_shared_rules_scan_and_md_emitter_at_class_edges_and_chunk_seams(tmp_path):
+    """What k_gcig_t and k_gcig_grp<16 / 32 / 64> share -- meme_gcig_rules.h, gcig_fscan, gcig_md, gcig_put_num -- at the shapes where a shared piece can go wrong
+    in one kernel only: see _shared_piece_jobs.  Score, operations, NM and MD of every job equal the oracle's; which class takes which job is asserted first."""
+    g = synth.make_genome(120_000, seed=403, repeat_frac=0.02)
+    P = _shared_piece_jobs(g)
+    jobs, calls = np.array(P.jobs, dtype=hipapi.GJOB), np.array(P.calls, dtype=hipapi.CJOB)
+    groups = _groups_on()
+    assert 300 <= jobs.shape[0] + calls.shape[0] <= 600 and max(len(r) for r in P.reads) == 150
+    # the classes: as posed with groups on -- every slot populated --, k_gcig_t for every DP job without
+    _, _, cls_j, n_col = _plan(jobs["qlen"], jobs["tlen"], jobs["w"], groups)
+    assert sorted(set(n_col.tolist()) & {15, 16, 17, 31, 32, 33, 63, 64, 65}) == [15, 16, 17, 31, 32, 33, 63, 64, 65]
+    assert set((jobs["tlen"] - jobs["qlen"])[:len(_EDGE_W) * 21 + len(_EDGE_Q) * 14].tolist()) == set(range(-3, 4))
+    wc = cjob_band(calls["qlen"], calls["tlen"], calls["w_"])
+    _, _, cls_c, _ = _plan(calls["qlen"], calls["tlen"], wc, groups)
+    for cls, want in ((cls_j, P.want_j), (cls_c, P.want_c)):
+        for k, c in enumerate(want):
+            assert c is None or int(cls[k]) == (c if groups or c == 3 else 2), (k, c, int(cls[k]))
+        assert not groups or all(_class_counts(cls)[s] > 0 for s in (0, 1, 4, 2))
+    # what the oracle's alignments are, against what the jobs were posed for
+    pen = (1, 4, 6, 1, 6, 1)
+    want_j = [O.ksw_global2(q, t, int(J["w"]), *pen) for J, (q, t) in zip(jobs, P.seqs)]
+    seam = 0
+    for J, (_, cg) in zip(jobs, want_j):
+        x = y = 0
+        for op, l in _ops(cg):
+            seam += int(op == 1 and l >= 10 and x <= 63 and x + l - 1 >= 64 and y - 1 < int(J["w"]) and int(J["w"]) >= 64)
+            x += l if op != 2 else 0
+            y += l if op != 1 else 0
+    assert seam >= 36, seam
+    want_c = [O.gen_cigar2(P.text, P.l_pac, P.reads[int(J["read"])], int(J["rb"]), int(J["rb"]) + int(J["tlen"]), int(J["w_"])) for J in calls]
+    assert all(x is not None for x in want_c)
+    runs = {c: set() for c in range(5)}
+    for c, (_, _, _, md) in zip(cls_c, want_c):
+        runs[int(c)] |= {int(x) for x in re.split(rb"[ACGTN^]+", md) if x}
+    for G, c in ((16, 0), (32, 1), (64, 4), (64, 2)):
+        assert {G, G + 1, 2 * G} <= runs[c if groups else 2], (G, c)
+    dels = [l for _, cg, _, _ in want_c for op, l in _ops(cg)[1:-1] if op == 2]
+    assert all(dels.count(D) >= 2 for D in (17, 33, 65))
+    assert sum(_ops(cg)[0][0] == 2 for _, cg, _, _ in want_c) >= 4 and sum(_ops(cg)[-1][0] == 2 for _, cg, _, _ in want_c) >= 4
+    ctx = _ctx_with_reads(tmp_path, g, P.reads)
+    try:
+        res, cig, _ = ctx.global_batch_host(jobs)
+        assert list(ctx.timings().gcig_class_jobs) == _class_counts(cls_j)
+        for k, (sc, cg) in enumerate(want_j):
+            o0 = int(res["cigar_off"][k])
+            assert sc == int(res["score"][k]) and np.array_equal(cg, cig[o0:o0 + int(res["n_cigar"][k])]), (k, jobs[k])
+        res, cig, md, _ = ctx.gen_cigar_batch_host(calls)
+        assert list(ctx.timings().gcig_class_jobs) == _class_counts(cls_c)
+        _check_calls(res, cig, md, want_c)
+    finally:
+        ctx.close()
