@@ -190,6 +190,12 @@ struct SamWs {         // cols: SamCols; contigs: contig name offsets + names + 
     DevBuf names, name_off, quals, recs, blob, cols, scratch, text, contigs; HostBuf h_text_off, h_text; Events<2> ev;
 };
 
+struct PrimaryWs {     // regs / reg_off / out / n_pri / mapq / status: the host form's staging; sorted: a heavy read's records in the first order; rank: its ranks in the second; list: the heavy
+                       // reads, counter: how many; logtab: log((double)k), k < 65536, by the host's libm
+    DevBuf regs, reg_off, out, n_pri, mapq, status, sorted, rank, list, counter, logtab; HostBuf h_regs, h_n_pri, h_mapq, h_status; Events<2> ev;
+    bool log_ready = false;
+};
+
 struct SideStreams {   // beside ctx->stream: the routed chaining tiers, the early overflow tier of seeding (meme_side_stream creates stream i with its event)
     Stream st[3];
     Events<3> done;    // done[i]: what was launched on st[i] has finished
@@ -206,7 +212,7 @@ struct meme_ctx {
     // workspaces (scan_tmp: tiles of the prefix sums, meme_scan_exclusive and the seeding gather)
     ResidentBatch batch;
     DevBuf scan_tmp;
-    ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam; SeedWs seed;
+    ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam; PrimaryWs primary; SeedWs seed;
     // Streams.  Order of destruction: meme_ctx_destroy synchronises every stream of the ctx; then the members go in reverse order of declaration, so the streams
     // and their fork / join events -- these two and, last member of the last workspace, the seeding stage's -- are destroyed BEFORE any DevBuf / HostBuf above is
     // freed.  A new stream holder goes below the buffers too: here, or last in SeedWs.  (A stage's timing events go with the stage; they are idle by then.)
@@ -226,6 +232,8 @@ struct meme_ctx {
     i64 ext_split = 1;                 // 1: the extension stage's read-walking kernels run eight lanes per read for reads with at most 8 chained seeds, a wavefront per read for the rest; 0: a wavefront per read
     i64 bsw_circ = 1;                  // 1: lane-per-pair banded SW of queries longer than 2w + 2 columns keeps its columns in a ring (k_bsw_lane_circ); 0: a word per query column
     i64 sam_max_batch = 0;             // > 0: meme_sam_format_batch_host refuses more record slots than this with MEME_E_CAPACITY (the caller then formats in pieces)
+    i64 primary_split = 8;             // primary marking: reads with more records than this go to the wavefront-per-read tier (0: every non-empty read; at most 8, the lanes of the light tier's group)
+    i64 primary_blocks = 0;            // > 0: cap on the workgroups of the primary-marking kernels (0 = none)
     i64 ext_live_only = 0;             // 1: meme_extend_last_batch_host hands over the surviving records only (qe > qb: what src/bwamem.cpp:1680-1693 keeps)
     i64 ext_rounds = 1;                // with ext_live_only: rounds of one seed per read before everything still ahead is extended at once (0: the reference's batch, then compaction)
     i64 gcig_groups = 1;               // 1: CIGAR jobs with bands of at most 16 / 32 / 64 columns run 4 / 2 / 1 to a wavefront as one chunk per row (k_gcig_grp); 0: a wavefront each, 64-column chunks

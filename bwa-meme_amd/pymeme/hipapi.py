@@ -118,6 +118,29 @@ class MateHost(C.Structure):
                 ("jobs", C.c_void_p), ("res", C.c_void_p), ("pose_ms", C.c_float), ("kernel_ms", C.c_float)]
 
 
+class PrimaryOpt(C.Structure):      # meme_primary_opt
+    _fields_ = [(n, C.c_int32) for n in ("a", "b", "o_del", "e_del", "o_ins", "e_ins", "min_seed_len", "T")] + [("mask_level", C.c_float), ("mapQ_coef_len", C.c_float)] + \
+               [("mapQ_coef_fac", C.c_int32), ("primary5", C.c_int32)]
+
+
+class PrimaryHost(C.Structure):     # meme_primary_host_result
+    _fields_ = [("nreads", C.c_int64), ("total_regs", C.c_int64), ("regs", C.c_void_p), ("n_pri", C.c_void_p), ("mapq", C.c_void_p), ("status", C.c_void_p), ("n_heavy", C.c_int64),
+                ("kernel_ms", C.c_float)]
+
+
+class PrimaryDeviceOut(C.Structure):    # meme_primary_device_out
+    _fields_ = [(n, C.c_void_p) for n in ("d_regs_out", "d_n_pri", "d_mapq", "d_status", "d_n_heavy")]
+
+
+def default_primary_opt(**kw):
+    # mem_opt_init (reference src/bwamem.cpp:126-162): a 1, b 4, gaps 6 + 1, min_seed_len 19, T 30, mask_level 0.5, mapQ_coef_len 50, mapQ_coef_fac = log(50) = 3
+    o = PrimaryOpt(1, 4, 6, 1, 6, 1, 19, 30, 0.5, 50.0, 3, 0)
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
+
+
 class MateOpt(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("a", "b", "o_del", "e_del", "o_ins", "e_ins", "pen_unpaired", "max_matesw", "min_seed_len", "batch_reads")]
 
@@ -156,7 +179,7 @@ EXPORTS = ["meme_device_count", "meme_ctx_create", "meme_ctx_destroy", "meme_las
            "meme_index_pos5_bytes",
            "meme_index_attach", "meme_index_describe", "meme_index_share", "meme_index_replicate", "meme_host_alloc",
            "meme_host_free", "meme_stage_pack_text", "meme_stage_pos5_from_sa", "meme_stage_build_entries", "meme_stage_build_plcp",
-           "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_seed_batch_device",
+           "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_primary_batch_host", "meme_primary_batch_device", "meme_seed_batch_device",
            "meme_bsw_batch", "meme_bsw_batch_device", "meme_get_timings", "meme_set_tuning", "meme_debug_packed_reads"]
 
 _lib = None
@@ -474,6 +497,30 @@ class Context:
             return np.frombuffer(buf, dtype=dtype, count=count).copy()
         return {"gar": view(res.gar, res.n_gar, np.int32), "gar_off": view(res.gar_off, res.nbatches + 1, np.int64), "job_off": view(res.job_off, res.nbatches + 1, np.int64),
                 "jobs": view(res.jobs, res.njobs, KSWV_JOB), "res": view(res.res, res.njobs, KSWR), "pose_ms": float(res.pose_ms), "kernel_ms": float(res.kernel_ms)}
+
+    def primary_batch_host(self, regs, reg_off, id_base=0, opt=None):
+        """meme_primary_batch_host: primary marking and mapping quality (mem_mark_primary_se, mem_reorder_primary5 under opt.primary5, mem_approx_mapq_se) of the
+        records regs (ALNREG) per read, read r with id id_base + r.  Returns dict(regs in the final order, n_pri, mapq, status, n_heavy, kernel_ms)."""
+        opt = opt or default_primary_opt()
+        assert regs.dtype == ALNREG and regs.flags.c_contiguous
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
+        n = reg_off.shape[0] - 1
+        res = PrimaryHost()
+        _check(lib().meme_primary_batch_host(C.c_void_p(self.h), _p(regs), _p(reg_off), C.c_int64(n), C.c_int64(int(id_base)), C.byref(opt), C.byref(res)))
+
+        def view(ptr, count, dtype):
+            if count == 0 or not ptr:
+                return np.zeros(0, dtype=dtype)
+            buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
+            return np.frombuffer(buf, dtype=dtype, count=count).copy()
+        return {"regs": view(res.regs, res.total_regs, ALNREG), "n_pri": view(res.n_pri, res.nreads, np.int32), "mapq": view(res.mapq, res.total_regs, np.uint8),
+                "status": view(res.status, res.nreads, np.uint8), "n_heavy": int(res.n_heavy), "kernel_ms": float(res.kernel_ms)}
+
+    def primary_batch_device(self, d_regs_ptr, d_reg_off_ptr, nreads, total_regs, id_base, opt, d_regs_out_ptr, d_n_pri_ptr, d_mapq_ptr, d_status_ptr, d_n_heavy_ptr):
+        """meme_primary_batch_device: the same on device arrays the caller owns, asynchronous on the ctx's stream (sync() before reading the results)."""
+        out = PrimaryDeviceOut(d_regs_out_ptr, d_n_pri_ptr, d_mapq_ptr, d_status_ptr, d_n_heavy_ptr)
+        _check(lib().meme_primary_batch_device(C.c_void_p(self.h), C.c_void_p(d_regs_ptr), C.c_void_p(d_reg_off_ptr), C.c_int64(nreads), C.c_int64(total_regs), C.c_int64(int(id_base)),
+                                               C.byref(opt or default_primary_opt()), C.byref(out)))
 
     def chain_batch_host(self, smems, smem_off, hits, hit_off, read_len, contigs, opt):
         """meme_chain_batch_host: chains of seeds the caller brings (numpy arrays laid out as seed_batch_host returns them)."""

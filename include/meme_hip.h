@@ -17,6 +17,7 @@
  *   meme_gen_cigar_batch_host       <- bwa_gen_cigar2() whole: CIGAR + NM + MD       src/bwa.cpp:274-362
  *   meme_sam_format_batch_host      <- mem_aln2sam() for a chunk's plain records     src/bwamem.cpp:2174-2312
  *   meme_matesw_batch_host          <- mem_sam_pe_batch_pre() + mem_sam_pe_batch()   src/bwamem_pair.cpp:660-716, 1060-1223, 719-818
+ *   meme_primary_batch_host         <- mem_mark_primary_se() + mem_reorder_primary5() + mem_approx_mapq_se()   src/bwamem.cpp:1974-2100
  *   meme_bsw_batch                  <- BandedPairWiseSW::getScores8 / getScores16 /
  *                                      scalarBandedSWAWrapper                 src/bandedSWA.h:118-135,257-297
  *
@@ -389,6 +390,46 @@ int meme_matesw_batch_host(meme_ctx* ctx, meme_ctx* reads_of /* NULL: ctx itself
                            const meme_mate_reg* regs, const int64_t* reg_off /* nreads + 1 */, int64_t first_read, int64_t nreads, const meme_pestat* pes /* 4 */,
                            const meme_contig* contigs, int32_t n_contigs, int64_t l_pac, const meme_mate_opt* opt, meme_mate_host_result* out);
 
+/* ---- primary marking and mapping quality: the first and the third step of mem_sam_pe ------------------------------------------------------
+ * What mem_mark_primary_se (reference src/bwamem.cpp:2002-2046, with mem_mark_primary_se_core :1974-2000), mem_reorder_primary5 (:2078-2100, only
+ * with opt->primary5 = MEM_F_PRIMARY5) and mem_approx_mapq_se (:2052-2076) do with the alignment records of a read, for every read of a batch:
+ * regs[reg_off[r] .. reg_off[r+1]) are read r's records as mem_sort_dedup_patch_mate_sort leaves them.  Per read the records come back in the
+ * reference's final order (same reg_off) with sub, alt_sc, sub_n, secondary, secondary_all and hash as the reference leaves them, every other
+ * field untouched; n_pri[r] = what mem_mark_primary_se returns; mapq[k] = what mem_approx_mapq_se returns for record k of the final order
+ * (the caller applies mem_reg2aln's rule: 0 for a record with secondary >= 0, :2332).
+ * The id: read r of the call has id id_base + r, the last argument of mem_mark_primary_se, which seeds the hash that orders records of equal score.
+ * A single-end run passes n_processed + i for read i of its chunk (src/bwamem.cpp:1907), so id_base = n_processed; a paired run passes
+ * ((n_processed >> 1) + pair) << 1 | end (src/bwamem_pair.cpp:923-924), which is n_processed + r again for the interleaved reads of a chunk,
+ * n_processed being even.
+ * Preconditions: finished records (qe > qb, re > rb, is_alt 0 or 1); sub_n is read, not reset, as in the reference.  opt->a >= 1 and opt->a + opt->b > 0.
+ * Only the mapQ_coef_len > 0 branch of the quality exists (the aligner's command line reaches no other): mapQ_coef_len <= 0 is MEME_E_ARG.
+ * Logarithms are looked up in a table of the host libm's log((double)k), k < 65536, staged once per ctx: a read one of whose qualities needs an
+ * argument beyond it (an alignment span or sub_n + 1 of 65536 and more) gets status[r] = 1 -- its marking is done, its qualities are unspecified --
+ * and the call succeeds.  status[r] = 2 (device form only): reg_off[r], reg_off[r+1] are not a span inside [0, total_regs]; the read is skipped.
+ * Host form: results in pinned memory of the ctx until its next call of this function. */
+typedef struct {
+    int32_t a, b, o_del, e_del, o_ins, e_ins, min_seed_len, T;   /* mem_opt_t fields of the same names */
+    float mask_level, mapQ_coef_len;
+    int32_t mapQ_coef_fac;
+    int32_t primary5;             /* opt->flag & MEM_F_PRIMARY5 */
+} meme_primary_opt;
+typedef struct {
+    int64_t nreads, total_regs;
+    const meme_alnreg* regs;      /* final order, offsets = the call's reg_off */
+    const int32_t* n_pri;         /* nreads */
+    const uint8_t* mapq;          /* total_regs */
+    const uint8_t* status;        /* nreads */
+    int64_t n_heavy;              /* reads the wavefront-per-read tier took (tuning "primary_split") */
+    float kernel_ms;              /* HIP events around the stage's kernels */
+} meme_primary_host_result;
+int meme_primary_batch_host(meme_ctx* ctx, const meme_alnreg* regs, const int64_t* reg_off /* nreads + 1, from 0 */, int64_t nreads, int64_t id_base,
+                            const meme_primary_opt* opt, meme_primary_host_result* out);
+/* The same on device arrays the caller owns (d_regs_out: total_regs records, not d_regs; d_n_pri, d_status: nreads; d_mapq: total_regs; d_n_heavy: one
+ * counter), asynchronous on the ctx's stream: nothing is copied and the host does not wait, so a later stage can run behind it without leaving HBM. */
+typedef struct { meme_alnreg* d_regs_out; int32_t* d_n_pri; uint8_t* d_mapq; uint8_t* d_status; uint64_t* d_n_heavy; } meme_primary_device_out;
+int meme_primary_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs, const int64_t* d_reg_off, int64_t nreads, int64_t total_regs, int64_t id_base,
+                              const meme_primary_opt* opt, const meme_primary_device_out* out);
+
 /* ---- measurement ---------------------------------------------------------------------------------
  * HIP-event timings of the kernels of the last *_device call, measured on the ctx's stream.          */
 typedef struct {
@@ -407,7 +448,7 @@ typedef struct {
     int64_t gcig_class_jobs[6];   /* the last CIGAR call's jobs by kernel: 16-lane groups, 32-lane groups, a wavefront each in 64-column chunks, the gap-free shortcut, 64-lane "groups"; the last entry is always 0 (the two-columns-per-lane kernel it counted was removed) */
 } meme_timings;
 int meme_get_timings(meme_ctx* ctx, meme_timings* out);
-int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value);   /* "group_lanes", "seed_blocks_per_cu", "seed_blocks", "smem_cap", "bsw_blocks", "bsw_lane_min_pairs", "chain_wave_tiers", "chain_lane_hits", "chain_light_hits", "seed_defer", "ext_live_only" (1: meme_extend_last_batch_host hands over only the records mem_kernel2_core keeps, src/bwamem.cpp:1680-1693 -- qe > qb, in order -- instead of one per chained seed with the purged ones marked; the stage then also runs in rounds -- "ext_rounds" (default 1; 0: off): a read's seeds are taken in extension order, tested against the read's surviving alignments first and extended only if they survive, one seed per read and round, after that many rounds everything still ahead at once: the same surviving records, without the banded SW of seeds the purge drops), "gcig_groups" (1, default: CIGAR jobs whose band has at most 16 / 32 / 64 columns run 4 / 2 / 1 to a wavefront with one chunk per row; 0: one wavefront per job in 64-column chunks; any other value: MEME_E_ARG), "gcig_zcap" (>= 0: bytes of LDS a CIGAR job keeps for its backtrack matrix or the window it is walked back through; default: chosen per call, 8192 where a typical matrix of the batch fits, else 2048; results do not depend on it), "ext_census" (1: meme_extend_last_batch_host also counts the extension jobs whose query is a prefix of its target), "max_batch" (> 0: meme_extend_last_batch_host / meme_global_batch_host refuse larger batches with MEME_E_CAPACITY), "ext_slab_jobs" (default 8 Mi, at least 1: the extension stage poses and aligns its jobs in slabs of whole reads with at most this many jobs per side, and at least one read, each -- a bound, and how the tests reach the multi-slab path; same records), "ext_split" (default 1: the extension stage's kernels that walk a read's chains run eight lanes per read for reads with at most 8 chained seeds and a wavefront per read for the others; 0: a wavefront per read throughout; same records), "bsw_circ" (default 1: the lane-per-pair banded-SW kernel keeps the columns of queries longer than its band in a ring of 2w + 2 columns -- same results, more wavefronts per CU; 0: one LDS word per query column as before), "sam_max_batch" (> 0: meme_sam_format_batch_host refuses more record slots than this with MEME_E_CAPACITY; the caller formats in pieces), "helper_blocks" (> 0: at most this many workgroups in the read packer, the offsets scan and the hit gather of a seeding call, as "seed_blocks" does for the search kernel -- how the tests drive their loops round with small batches; 0, default: no cap; same results) */
+int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value);   /* "group_lanes", "seed_blocks_per_cu", "seed_blocks", "smem_cap", "bsw_blocks", "bsw_lane_min_pairs", "chain_wave_tiers", "chain_lane_hits", "chain_light_hits", "seed_defer", "ext_live_only" (1: meme_extend_last_batch_host hands over only the records mem_kernel2_core keeps, src/bwamem.cpp:1680-1693 -- qe > qb, in order -- instead of one per chained seed with the purged ones marked; the stage then also runs in rounds -- "ext_rounds" (default 1; 0: off): a read's seeds are taken in extension order, tested against the read's surviving alignments first and extended only if they survive, one seed per read and round, after that many rounds everything still ahead at once: the same surviving records, without the banded SW of seeds the purge drops), "gcig_groups" (1, default: CIGAR jobs whose band has at most 16 / 32 / 64 columns run 4 / 2 / 1 to a wavefront with one chunk per row; 0: one wavefront per job in 64-column chunks; any other value: MEME_E_ARG), "gcig_zcap" (>= 0: bytes of LDS a CIGAR job keeps for its backtrack matrix or the window it is walked back through; default: chosen per call, 8192 where a typical matrix of the batch fits, else 2048; results do not depend on it), "ext_census" (1: meme_extend_last_batch_host also counts the extension jobs whose query is a prefix of its target), "max_batch" (> 0: meme_extend_last_batch_host / meme_global_batch_host refuse larger batches with MEME_E_CAPACITY), "ext_slab_jobs" (default 8 Mi, at least 1: the extension stage poses and aligns its jobs in slabs of whole reads with at most this many jobs per side, and at least one read, each -- a bound, and how the tests reach the multi-slab path; same records), "ext_split" (default 1: the extension stage's kernels that walk a read's chains run eight lanes per read for reads with at most 8 chained seeds and a wavefront per read for the others; 0: a wavefront per read throughout; same records), "bsw_circ" (default 1: the lane-per-pair banded-SW kernel keeps the columns of queries longer than its band in a ring of 2w + 2 columns -- same results, more wavefronts per CU; 0: one LDS word per query column as before), "sam_max_batch" (> 0: meme_sam_format_batch_host refuses more record slots than this with MEME_E_CAPACITY; the caller formats in pieces), "helper_blocks" (> 0: at most this many workgroups in the read packer, the offsets scan and the hit gather of a seeding call, as "seed_blocks" does for the search kernel -- how the tests drive their loops round with small batches; 0, default: no cap; same results), "primary_split" (default 8, its maximum: meme_primary_batch_host / _device run reads with at most this many records eight lanes to a read with the records in registers, reads with more a wavefront each with the records in HBM; 0 sends every non-empty read to the wavefront tier; larger values count as 8; same results), "primary_blocks" (> 0: at most this many workgroups in each kernel of that stage, so that a small batch goes round their grid-stride loops; 0, default: no cap; same results) */
 
 /* Debug: the packed image of the last seeded batch (what the search kernels read), copied to the host.  Per read `stride` 64-bit
  * words: fw[W] rc[W] nfw[MW] nrc[MW] len | hasN << 31 (2 bits per base, first base in the top bits, N packed as A; mask bit j of word m =
