@@ -12,6 +12,7 @@
 //   k_ext_fold<left>   results into the records (:2985-3018 and siblings); jobs whose band was too narrow to a retry list (MAX_BAND_TRY 2)
 //   k_ext_h0           start score of the right extension = score after the left one (:3371-3376)
 //   k_ext_purge        alignments of seeds an earlier alignment of the read already covers are dropped (:3389-3485)
+// The reference's rules -- spans, job geometry, records, fold, purge predicates -- are meme_ext_rules.h's; here is who walks what.
 //
 // One wavefront per read in the kernels that walk a read's chains (a read has 1 to a few hundred chained seeds: lanes take seeds, the
 // wavefront reduces / scans across them, and a repeat-rich read cannot hold 63 others back); one lane per job in the others.
@@ -19,11 +20,9 @@
 #include <string.h>
 
 #include "meme_common.h"
+#include "meme_ext_rules.h"
 
 namespace {
-
-constexpr int H0 = -99;                    // H0_, src/macro.h:44
-constexpr int EXT_BAND_TRIES = 2;          // MAX_BAND_TRY, src/bwamem.cpp:62
 
 struct ExtArgs {
     const uint8_t* reads; const i64* read_off; i64 g0, ns;            // reads [g0, g0 + ns) of the batch
@@ -48,31 +47,10 @@ struct ExtArgs {
 };
 constexpr int EXT_LIGHT = 8;
 
-__device__ __forceinline__ int cal_max_gap(const meme_ext_opt& o, int qlen) {       // src/bwamem.cpp:85-95
-    const int l_del = (int)((double)(qlen * o.a - o.o_del) / o.e_del + 1.);
-    const int l_ins = (int)((double)(qlen * o.a - o.o_ins) / o.e_ins + 1.);
-    int l = l_del > l_ins ? l_del : l_ins;
-    l = l > 1 ? l : 1;
-    return l < o.w << 1 ? l : o.w << 1;
-}
-__device__ __forceinline__ i64 wave_min(i64 v) { for (int d = 32; d >= 1; d >>= 1) { const i64 y = __shfl_xor(v, d); v = y < v ? y : v; } return v; }
-__device__ __forceinline__ i64 wave_max(i64 v) { for (int d = 32; d >= 1; d >>= 1) { const i64 y = __shfl_xor(v, d); v = y > v ? y : v; } return v; }
-__device__ __forceinline__ int pad4(int x) { return (x + 3) & ~3; }
 // sub-wavefront groups of G lanes (G = 64: the wavefront): ballots, broadcasts and reductions that stay inside the group
 template <int G> __device__ __forceinline__ u64 gballot(bool p, int gbase) { const u64 b = __ballot(p); return G == 64 ? b : (b >> gbase) & (((u64)1 << (G & 63)) - 1); }
 template <int G> __device__ __forceinline__ i64 group_min(i64 v) { for (int d = G / 2; d >= 1; d >>= 1) { const i64 y = __shfl_xor(v, d); v = y < v ? y : v; } return v; }
 template <int G> __device__ __forceinline__ i64 group_max(i64 v) { for (int d = G / 2; d >= 1; d >>= 1) { const i64 y = __shfl_xor(v, d); v = y > v ? y : v; } return v; }
-
-// seeds of the chain fully inside the alignment (src/bwamem.cpp:2907-2917 and after every fold)
-__device__ inline void seedcov(meme_alnreg* a, const meme_chain_seed* sd, int n) {
-    if (a->rb == H0 || a->qb == H0 || a->qe == H0 || a->re == H0) return;
-    int cov = 0;
-    for (int i = 0; i < n; ++i) {
-        const meme_chain_seed t = sd[i];
-        if (t.qbeg >= a->qb && t.qbeg + t.len <= a->qe && t.rbeg >= a->rb && t.rbeg + t.len <= a->re) cov += t.len;
-    }
-    a->seedcov = cov;
-}
 
 template <bool WRITE, int G>
 __global__ void __launch_bounds__(256) k_ext_jobs(ExtArgs A) {
@@ -100,23 +78,15 @@ __global__ void __launch_bounds__(256) k_ext_jobs(ExtArgs A) {
             const meme_chain_seed* sd = A.seeds + s0 + ch.seed_beg;
             i64 b_min = A.l_pac << 1, e_max = 0;
             for (int i = lane; i < ch.n_seeds; i += G) {
-                const meme_chain_seed t = sd[i];
-                const i64 b = t.rbeg - (t.qbeg + cal_max_gap(o, t.qbeg));
-                const int tail = l_query - t.qbeg - t.len;
-                const i64 e = t.rbeg + t.len + (tail + cal_max_gap(o, tail));
-                b_min = b < b_min ? b : b_min;
-                e_max = e > e_max ? e : e_max;
+                const ExtSpan x = ext_seed_reach(sd[i], l_query, o);
+                b_min = x.b < b_min ? x.b : b_min;
+                e_max = x.e > e_max ? x.e : e_max;
             }
             i64 rmax0 = group_min<G>(b_min), rmax1 = group_max<G>(e_max);
-            if (rmax0 < 0) rmax0 = 0;
-            if (rmax1 > A.l_pac << 1) rmax1 = A.l_pac << 1;
             const i64 mid = sd[0].rbeg;
-            if (rmax0 < A.l_pac && A.l_pac < rmax1) { if (mid < A.l_pac) rmax1 = A.l_pac; else rmax0 = A.l_pac; }
+            ext_span_finish(rmax0, rmax1, mid, A.l_pac);
             // bns_fetch_seq_v2: the span stays inside the chain's reference sequence (on the strand of its first seed)
-            i64 far_beg = A.contig_off[ch.rid], far_end = far_beg + A.contig_len[ch.rid];
-            if (mid >= A.l_pac) { const i64 t = far_beg; far_beg = (A.l_pac << 1) - far_end; far_end = (A.l_pac << 1) - t; }
-            rmax0 = rmax0 > far_beg ? rmax0 : far_beg;
-            rmax1 = rmax1 < far_end ? rmax1 : far_end;
+            bns_clamp(A.l_pac, A.contig_off[ch.rid], A.contig_len[ch.rid], mid >= A.l_pac, rmax0, rmax1);
             A.rmax[2 * (c0 + c)] = rmax0;
             A.rmax[2 * (c0 + c) + 1] = rmax1;
         }
@@ -141,12 +111,9 @@ __global__ void __launch_bounds__(256) k_ext_jobs(ExtArgs A) {
         const meme_chain_seed t = sd[il];
         const i64 rmax0 = A.rmax[2 * (c0 + c)], rmax1 = A.rmax[2 * (c0 + c) + 1];
         const bool pick = valid && A.mode != 1 && (A.mode == 0 || A.sel[s0 + j]);              // its jobs are posed by this launch
-        const bool sideL = valid && t.qbeg > 0, sideR = valid && t.qbeg + t.len != l_query;   // the seed has a left / right flank at all
-        const bool hasL = pick && sideL, hasR = pick && sideR;
-        const int qe = t.qbeg + t.len;
-        const int l2L = t.qbeg, l1L = (int)(t.rbeg - rmax0);
-        const int l2R = l_query - qe, l1R = (int)(rmax1 - (t.rbeg + t.len));
-        const int bytesL = hasL ? pad4(l1L) + pad4(l2L) : 0, bytesR = hasR ? pad4(l1R) + pad4(l2R) : 0;
+        const ExtGeom g = ext_geom(t, rmax0, rmax1, l_query);       // the flanks the seed has, their lengths and bytes
+        const bool hasL = pick && g.sideL, hasR = pick && g.sideR;
+        const int bytesL = hasL ? g.bytesL : 0, bytesR = hasR ? g.bytesR : 0;
         const u64 mL = gballot<G>(hasL, gbase), mR = gballot<G>(hasR, gbase), below = ((u64)1 << lane) - 1;
         // exclusive scan of the bytes over the lanes
         int bsum = bytesL + bytesR, bex;
@@ -162,32 +129,15 @@ __global__ void __launch_bounds__(256) k_ext_jobs(ExtArgs A) {
             if (A.seed_score) {
                 const int* ss = A.seed_score + s0 + ch.seed_beg;
                 const int mine = ss[il];
-                for (int k = 0; k < ch.n_seeds; ++k) { const int lk = ss[k]; rank += (lk < mine || (lk == mine && k < il)) ? 1 : 0; }
+                for (int k = 0; k < ch.n_seeds; ++k) rank += ext_seed_before(ss[k], k, mine, il) ? 1 : 0;
             } else
-                for (int k = 0; k < ch.n_seeds; ++k) { const int lk = sd[k].len; rank += (lk < t.len || (lk == t.len && k < il)) ? 1 : 0; }
+                for (int k = 0; k < ch.n_seeds; ++k) rank += ext_seed_before(sd[k].len, k, t.len, il) ? 1 : 0;
             if (A.mode != 2) A.order[s0 + ch.seed_beg + rank] = il;
             const i64 reg = s0 + ch.seed_beg + (ch.n_seeds - 1 - rank);        // best seed first
-            meme_alnreg a;
-            memset(&a, 0, sizeof(a));
-            a.w = o.w; a.score = a.truesc = -1; a.rid = ch.rid; a.frac_rep = A.frac_rep[r]; a.seedlen0 = t.len; a.c = (u64)(c0 + c);
-            a.rb = a.re = H0; a.qb = a.qe = H0;
-            if (sideL) { a.qb = t.qbeg; a.rb = t.rbeg; } else { a.score = a.truesc = t.len * o.a; a.qb = 0; a.rb = t.rbeg; }
-            if (sideR) { a.qe = qe; a.re = t.rbeg + t.len; } else { a.qe = l_query; a.re = t.rbeg + t.len; seedcov(&a, sd, ch.n_seeds); }
-            if (A.mode != 2) A.regs[reg] = a;
-            if (hasL) {
-                meme_seqpair sp;
-                memset(&sp, 0, sizeof(sp));
-                sp.h0 = t.len * o.a; sp.seqid = (int32_t)r; sp.regid = (int32_t)reg; sp.len1 = l1L; sp.len2 = l2L;
-                sp.idr = (int32_t)(byte0 + nB + bex); sp.idq = sp.idr + pad4(l1L);
-                A.L[jobL0 + nL + __popcll(mL & below)] = sp;
-            }
-            if (hasR) {
-                meme_seqpair sp;
-                memset(&sp, 0, sizeof(sp));
-                sp.h0 = H0; sp.seqid = (int32_t)r; sp.regid = (int32_t)reg; sp.len1 = l1R; sp.len2 = l2R;
-                sp.idr = (int32_t)(byte0 + nB + bex + bytesL); sp.idq = sp.idr + pad4(l1R);
-                A.R[jobR0 + nR + __popcll(mR & below)] = sp;
-            }
+            if (A.mode != 2) A.regs[reg] = ext_record0(t, g.sideL, g.sideR, l_query, o, ch.rid, A.frac_rep[r], (u64)(c0 + c), sd, ch.n_seeds);
+            const int idr = (int)(byte0 + nB + bex);
+            if (hasL) A.L[jobL0 + nL + __popcll(mL & below)] = ext_pose(t.len * o.a, (int)r, (int)reg, g.l1L, g.l2L, idr);
+            if (hasR) A.R[jobR0 + nR + __popcll(mR & below)] = ext_pose(H0, (int)r, (int)reg, g.l1R, g.l2R, idr + bytesL);
         }
         if (WRITE) {
             // the sequences, job after job, 64 lanes x 4 bases per step: left jobs reversed (both sequences run away from the seed)
@@ -199,10 +149,10 @@ __global__ void __launch_bounds__(256) k_ext_jobs(ExtArgs A) {
                     m &= m - 1;
                     const i64 rbeg = __shfl(t.rbeg, gbase + jl);
                     const int qb = __shfl(t.qbeg, gbase + jl), ln = __shfl(t.len, gbase + jl);
-                    const int l1 = __shfl(side ? l1R : l1L, gbase + jl), l2 = __shfl(side ? l2R : l2L, gbase + jl);
+                    const int l1 = __shfl(side ? g.l1R : g.l1L, gbase + jl), l2 = __shfl(side ? g.l2R : g.l2L, gbase + jl);
                     const i64 dst = byte0 + nB + __shfl(bex, gbase + jl) + (side ? __shfl(bytesL, gbase + jl) : 0);
                     uint8_t* dr = A.seq + dst;
-                    uint8_t* dq = dr + pad4(l1);
+                    uint8_t* dq = dr + ext_query_off(l1);
                     for (int i = lane * 4; i < l1; i += 4 * G) {
                         unsigned v = 0;
                         for (int b = 0; b < 4; ++b) {
@@ -243,8 +193,6 @@ struct FltArgs {
     const i64* off2;                 // its exclusive scan = the new seed_off
     meme_chain_seed* seeds2; int* score2;
 };
-constexpr int FLT_OFF = INT32_MIN;
-constexpr int SEEDSW_EXT = 50;      // MEM_SHORT_EXT, src/bwamem.cpp:249
 
 // the alignments mem_seed_sw would run (src/bwamem.cpp:494-520, bns_fetch_seq src/bntseq.cpp:541-570): one lane per chained seed
 __global__ void __launch_bounds__(64) k_flt_pose(FltArgs A) {
@@ -265,29 +213,9 @@ __global__ void __launch_bounds__(64) k_flt_pose(FltArgs A) {
             if (hsp >= 0) {
                 v = -1;
                 const meme_chain_seed t = A.seeds[s0 + j];
-                if (t.len < MEME_SEEDSW_MAX) {
-                    int qb = t.qbeg, qe = t.qbeg + t.len;
-                    i64 rb = t.rbeg, re = t.rbeg + t.len;
-                    const i64 mid = (rb + re) >> 1;
-                    qb -= SEEDSW_EXT; qb = qb > 0 ? qb : 0;
-                    qe += SEEDSW_EXT; qe = qe < l_query ? qe : l_query;
-                    rb -= SEEDSW_EXT; rb = rb > 0 ? rb : 0;
-                    re += SEEDSW_EXT; re = re < A.l_pac << 1 ? re : A.l_pac << 1;
-                    if (rb < A.l_pac && A.l_pac < re) { if (mid < A.l_pac) re = A.l_pac; else rb = A.l_pac; }
-                    if (!(qe - qb >= MEME_SEEDSW_MAX || re - rb >= MEME_SEEDSW_MAX)) {
-                        // the window stays inside the reference sequence of the seed's midpoint, on its strand
-                        const bool rev = mid >= A.l_pac;
-                        const i64 fpos = rev ? (A.l_pac << 1) - 1 - mid : mid;
-                        int lo = 0, hi = A.n_contigs - 1;
-                        while (lo < hi) { const int m = (lo + hi + 1) >> 1; if (A.contig_off[m] <= fpos) lo = m; else hi = m - 1; }
-                        i64 far_beg = A.contig_off[lo], far_end = far_beg + A.contig_len[lo];
-                        if (rev) { const i64 x = far_beg; far_beg = (A.l_pac << 1) - far_end; far_end = (A.l_pac << 1) - x; }
-                        rb = rb > far_beg ? rb : far_beg;
-                        re = re < far_end ? re : far_end;
-                        J.rb = rb; J.qoff = q0 + qb; J.seed = (int)(s0 + j); J.tlen = (short)(re - rb); J.qlen = (short)(qe - qb);
-                        job = true;
-                    }
-                }
+                const FltWindow W = flt_window(t, l_query, A.l_pac, A.contig_off, A.contig_len, A.n_contigs, MEME_SEEDSW_MAX);
+                job = W.job;
+                if (job) { J.rb = W.rb; J.qoff = q0 + W.qb; J.seed = (int)(s0 + j); J.tlen = (short)(W.re - W.rb); J.qlen = (short)(W.qe - W.qb); }
             }
             A.sc[s0 + j] = v;
         }
@@ -300,8 +228,6 @@ __global__ void __launch_bounds__(64) k_flt_pose(FltArgs A) {
         }
     }
 }
-
-__device__ __forceinline__ bool flt_keeps(int v, int hsp) { return v == FLT_OFF || v < 0 || v >= hsp; }      // (:589)
 
 // seeds that stay: per read (-> scan -> the new seed_off), per chain (n_seeds; seed_beg = the kept seeds of the read's earlier chains)
 template <bool MOVE>
@@ -328,7 +254,7 @@ __global__ void __launch_bounds__(64) k_flt_apply(FltArgs A) {
                 const meme_chain_seed t = A.seeds[g];
                 const i64 d = d0 + kept + kc + __popcll(m & (((u64)1 << lane) - 1));
                 A.seeds2[d] = t;
-                A.score2[d] = v == FLT_OFF ? t.len : (v < 0 ? t.len * A.a : v);       // (:591)
+                A.score2[d] = flt_kept_score(v, t.len, A.a);
             }
             kc += __popcll(m);
         }
@@ -350,19 +276,9 @@ template <bool LEFT>
 __global__ void __launch_bounds__(256) k_ext_fold(FoldArgs F) {
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < F.n; i += (i64)gridDim.x * blockDim.x) {
         const meme_seqpair sp = F.pairs[i];
-        meme_alnreg* a = &F.regs[sp.regid];
-        const int prev = a->score;
-        a->score = sp.score;
-        if (a->score == prev || sp.max_off < (F.w >> 1) + (F.w >> 2) || F.last) {
-            if (LEFT) {
-                if (sp.gscore <= 0 || sp.gscore <= a->score - F.o.pen_clip5) { a->qb -= sp.qle; a->rb -= sp.tle; a->truesc = a->score; }
-                else { a->qb = 0; a->rb -= sp.gtle; a->truesc = sp.gscore; }
-            } else {
-                if (sp.gscore <= 0 || sp.gscore <= a->score - F.o.pen_clip3) { a->qe += sp.qle; a->re += sp.tle; a->truesc += a->score - sp.h0; }
-                else { a->qe = (int)(F.read_off[sp.seqid + 1] - F.read_off[sp.seqid]); a->re += sp.gtle; a->truesc += sp.gscore - sp.h0; }
-            }
-            a->w = a->w > F.w ? a->w : F.w;
-            const meme_chain ch = F.chains[a->c];
+        meme_alnreg& a = F.regs[sp.regid];
+        if (ext_fold<LEFT>(a, sp, F.w, F.last, F.o, (int)(F.read_off[sp.seqid + 1] - F.read_off[sp.seqid]))) {
+            const meme_chain ch = F.chains[a.c];
             seedcov(a, F.seeds + F.seed_off[sp.seqid] + ch.seed_beg, ch.n_seeds);
         } else F.retry[atomicAdd(F.n_retry, 1ull)] = sp;
     }
@@ -379,71 +295,59 @@ struct PurgeArgs {
     meme_ext_opt o;
 };
 
-// (:3389-3485) in the order the one-read-at-a-time aligner would have met the seeds: chain after chain, best seed first
-__global__ void __launch_bounds__(256) k_ext_purge(PurgeArgs P) {
-    const i64 r = (i64)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= P.nreads) return;
-    const int lane = threadIdx.x & 63;
+// (:3389-3485) is the seed s -- k-th of its chain's extension order `ord`, `cur` records of the read before it -- dropped?  The group's lanes take the earlier
+// records, then the chain's seeds extended before s (later in ord; -1: dropped themselves); every lane of the group returns the same answer
+template <int G>
+__device__ __forceinline__ bool ext_seed_dropped(const meme_alnreg* av, int cur, const meme_chain_seed& s, const meme_chain_seed* sd, const int* ord, int k, int n_seeds,
+                                                 int l_query, const meme_ext_opt& o, int lane, int gbase) {
+    // an earlier, surviving alignment that contains the seed and has it within its band on either side?
+    bool found = false;
+    for (int ib = 0; ib < cur && !found; ib += G) {
+        const int i = ib + lane;
+        bool hit = false;
+        if (i < cur) { const meme_alnreg* p = &av[i]; hit = ext_covers(p->rb, p->re, p->qb, p->qe, p->w, p->seedlen0, s, l_query, o); }
+        found = gballot<G>(hit, gbase) != 0;
+    }
+    if (!found) return false;
+    // (almost) contained -- unless a long, overlapping, better seed of the chain on another diagonal says otherwise
+    bool other = false;
+    for (int ub = k + 1; ub < n_seeds && !other; ub += G) {
+        const int u = ub + lane;
+        const bool hit = u < n_seeds && ord[u] >= 0 && ext_other_diagonal(s, sd[ord[u]]);
+        other = gballot<G>(hit, gbase) != 0;
+    }
+    return !other;
+}
+
+// The walk over read r in the order the one-read-at-a-time aligner would have met its seeds -- chain after chain, best seed first -- from rank k_first of chain
+// c_first, `cur` seeds met before: dropped seeds are marked (qb = qe = -1; -1 in the order); survivor(c, k, cur, chain, seed) = true ends the walk at a survivor.
+// Returns the number of seeds met when the read is walked to its end, -1 when survivor ended it.
+template <int G, class F>
+__device__ __forceinline__ int ext_walk(const PurgeArgs& P, i64 r, int lane, int gbase, int c_first, int k_first, int cur, const F& survivor) {
     const i64 c0 = P.chain_off[r];
     const int nc = (int)(P.chain_off[r + 1] - c0);
     const i64 s0 = P.seed_off[r];
-    const int S = (int)(P.seed_off[r + 1] - s0);
-    if (S < 2) return;                                 // a lone alignment has nothing before it
     const int l_query = (int)(P.read_off[r + 1] - P.read_off[r]);
-    meme_alnreg* av = P.regs + s0;
-    int cur = 0;                                       // record of the seed at hand = number of seeds met so far
-    for (int c = 0; c < nc; ++c) {
+    meme_alnreg* av = P.regs + s0;                     // av[cur]: record of the seed at hand
+    for (int c = c_first; c < nc; ++c) {
         const meme_chain ch = P.chains[c0 + c];
         const meme_chain_seed* sd = P.seeds + s0 + ch.seed_beg;
         int* ord = P.order + s0 + ch.seed_beg;
-        for (int k = ch.n_seeds - 1; k >= 0; --k, ++cur) {
+        for (int k = c == c_first ? k_first : ch.n_seeds - 1; k >= 0; --k, ++cur) {
             const meme_chain_seed s = sd[ord[k]];
-            // an earlier, surviving alignment that contains the seed and has it within its band on either side?
-            bool found = false;
-            for (int ib = 0; ib < cur && !found; ib += 64) {
-                const int i = ib + lane;
-                bool hit = false;
-                if (i < cur) {
-                    const meme_alnreg* p = &av[i];
-                    const i64 prb = p->rb, pre = p->re;
-                    const int pqb = p->qb, pqe = p->qe;
-                    if (!(pqb == -1 && pqe == -1) && !(s.rbeg < prb || s.rbeg + s.len > pre || s.qbeg < pqb || s.qbeg + s.len > pqe) &&
-                        !(s.len - p->seedlen0 > .1 * l_query)) {
-                        const int pw = p->w;
-                        int qd = s.qbeg - pqb;
-                        i64 rd = s.rbeg - prb;
-                        int max_gap = cal_max_gap(P.o, qd < rd ? qd : (int)rd);
-                        int band = max_gap < pw ? max_gap : pw;
-                        if (qd - rd < band && rd - qd < band) hit = true;
-                        else {
-                            qd = pqe - (s.qbeg + s.len);
-                            rd = pre - (s.rbeg + s.len);
-                            max_gap = cal_max_gap(P.o, qd < rd ? qd : (int)rd);
-                            band = max_gap < pw ? max_gap : pw;
-                            if (qd - rd < band && rd - qd < band) hit = true;
-                        }
-                    }
-                }
-                found = __ballot(hit) != 0;
-            }
-            if (!found) continue;
-            // (almost) contained -- unless a long, overlapping, better seed of the chain on another diagonal says otherwise
-            bool other = false;
-            for (int ub = k + 1; ub < ch.n_seeds && !other; ub += 64) {
-                const int u = ub + lane;
-                bool hit = false;
-                if (u < ch.n_seeds && ord[u] >= 0) {
-                    const meme_chain_seed t = sd[ord[u]];
-                    if (!(t.len < s.len * .95)) {
-                        if (s.qbeg <= t.qbeg && s.qbeg + s.len - t.qbeg >= s.len >> 2 && t.qbeg - s.qbeg != t.rbeg - s.rbeg) hit = true;
-                        else if (t.qbeg <= s.qbeg && t.qbeg + t.len - s.qbeg >= s.len >> 2 && s.qbeg - t.qbeg != s.rbeg - t.rbeg) hit = true;
-                    }
-                }
-                other = __ballot(hit) != 0;
-            }
-            if (!other) { av[cur].qb = -1; av[cur].qe = -1; ord[k] = -1; }
+            if (ext_seed_dropped<G>(av, cur, s, sd, ord, k, ch.n_seeds, l_query, P.o, lane, gbase)) { av[cur].qb = -1; av[cur].qe = -1; ord[k] = -1; }
+            else if (survivor(c, k, cur, ch, s)) return -1;
         }
     }
+    return cur;
+}
+
+// the reference's batch order: every alignment exists, the whole read is walked
+__global__ void __launch_bounds__(256) k_ext_purge(PurgeArgs P) {
+    const i64 r = (i64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= P.nreads) return;
+    if (P.seed_off[r + 1] - P.seed_off[r] < 2) return;            // a lone alignment has nothing before it
+    ext_walk<64>(P, r, threadIdx.x & 63, 0, 0, P.chains[P.chain_off[r]].n_seeds - 1, 0, [](int, int, int, const meme_chain&, const meme_chain_seed&) { return false; });
 }
 
 // ---- extension in rounds ------------------------------------------------------------------------------------------------------------------
@@ -460,13 +364,6 @@ struct AdvArgs {
     const i64* rmax; i64 *cntL, *cntR, *cntB;        // the round's plan as k_ext_jobs<false> would count it: left / right jobs and sequence bytes of the read's selected seeds
     const i64* list; i64 nlist; int light;           // as in ExtArgs: the wavefront-per-read launch walks `list`, the eight-lanes-per-read launch everything with at most EXT_LIGHT seeds
 };
-// jobs and bytes of one selected seed (the arithmetic of k_ext_jobs)
-__device__ __forceinline__ void adv_count(const meme_chain_seed& t, i64 rmax0, i64 rmax1, int l_query, i64& nL, i64& nR, i64& nB) {
-    const int qe = t.qbeg + t.len;
-    if (t.qbeg > 0) { ++nL; nB += pad4((int)(t.rbeg - rmax0)) + pad4(t.qbeg); }
-    if (qe != l_query) { ++nR; nB += pad4((int)(rmax1 - (t.rbeg + t.len))) + pad4(l_query - qe); }
-}
-
 template <int G>
 __global__ void __launch_bounds__(256) k_ext_advance(AdvArgs V) {
     const PurgeArgs& P = V.P;
@@ -479,97 +376,42 @@ __global__ void __launch_bounds__(256) k_ext_advance(AdvArgs V) {
     const int nc = (int)(P.chain_off[r + 1] - c0);
     const i64 s0 = P.seed_off[r];
     if (V.light && P.seed_off[r + 1] - s0 > EXT_LIGHT) return;
-    int4 st = V.state[r];                              // x chain, y rank of the next seed in it (-1: the chain is done), z seeds met so far
+    const int4 st = V.state[r];                        // x chain, y rank of the next seed in it (-1: the chain is done), z seeds met so far
     if (V.mode != ADV_FINISH && lane == 0) { V.act[r] = 0; V.cntL[r] = 0; V.cntR[r] = 0; V.cntB[r] = 0; V.cntS[r] = 0; }
     if (st.x >= nc) return;
     const int l_query = (int)(P.read_off[r + 1] - P.read_off[r]);
-    meme_alnreg* av = P.regs + s0;
-    int cur = st.z;
-    for (int c = st.x; c < nc; ++c) {
-        const meme_chain ch = P.chains[c0 + c];
-        const meme_chain_seed* sd = P.seeds + s0 + ch.seed_beg;
-        int* ord = P.order + s0 + ch.seed_beg;
-        for (int k = c == st.x ? st.y : ch.n_seeds - 1; k >= 0; --k, ++cur) {
-            const meme_chain_seed s = sd[ord[k]];
-            bool found = false;
-            for (int ib = 0; ib < cur && !found; ib += G) {
-                const int i = ib + lane;
-                bool hit = false;
-                if (i < cur) {
-                    const meme_alnreg* p = &av[i];
-                    const i64 prb = p->rb, pre = p->re;
-                    const int pqb = p->qb, pqe = p->qe;
-                    if (!(pqb == -1 && pqe == -1) && !(s.rbeg < prb || s.rbeg + s.len > pre || s.qbeg < pqb || s.qbeg + s.len > pqe) &&
-                        !(s.len - p->seedlen0 > .1 * l_query)) {
-                        const int pw = p->w;
-                        int qd = s.qbeg - pqb;
-                        i64 rd = s.rbeg - prb;
-                        int max_gap = cal_max_gap(P.o, qd < rd ? qd : (int)rd);
-                        int band = max_gap < pw ? max_gap : pw;
-                        if (qd - rd < band && rd - qd < band) hit = true;
-                        else {
-                            qd = pqe - (s.qbeg + s.len);
-                            rd = pre - (s.rbeg + s.len);
-                            max_gap = cal_max_gap(P.o, qd < rd ? qd : (int)rd);
-                            band = max_gap < pw ? max_gap : pw;
-                            if (qd - rd < band && rd - qd < band) hit = true;
-                        }
-                    }
+    i64 nL = 0, nR = 0, nB = 0;                        // the round's plan: jobs and bytes of the seeds selected, as k_ext_jobs will pose them
+    const auto plan = [&](const meme_chain_seed& t, i64 c) { const ExtGeom g = ext_geom(t, V.rmax[2 * c], V.rmax[2 * c + 1], l_query); nL += g.sideL; nR += g.sideR; nB += g.bytesL + g.bytesR; };
+    const int met = ext_walk<G>(P, r, lane, gbase, st.x, st.y, st.z, [&](int c, int k, int cur, const meme_chain& ch, const meme_chain_seed& s) {
+        if (V.mode == ADV_FINISH) return false;        // a survivor whose alignment exists
+        if (V.mode == ADV_REST) {                      // this survivor and everything behind it go into the round; ADV_FINISH walks on from here
+            unsigned long long cnt = 0;
+            for (int c2 = c; c2 < nc; ++c2) {
+                const meme_chain ch2 = P.chains[c0 + c2];
+                const int* ord2 = P.order + s0 + ch2.seed_beg;
+                const int k1 = c2 == c ? k : ch2.n_seeds - 1;
+                for (int k2 = k1 - lane; k2 >= 0; k2 -= G) {
+                    const int il = ord2[k2];
+                    V.sel[s0 + ch2.seed_beg + il] = 1;
+                    plan(P.seeds[s0 + ch2.seed_beg + il], c0 + c2);
                 }
-                found = gballot<G>(hit, gbase) != 0;
+                cnt += k1 + 1;
             }
-            bool drop = false;
-            if (found) {
-                bool other = false;
-                for (int ub = k + 1; ub < ch.n_seeds && !other; ub += G) {
-                    const int u = ub + lane;
-                    bool hit = false;
-                    if (u < ch.n_seeds && ord[u] >= 0) {
-                        const meme_chain_seed t = sd[ord[u]];
-                        if (!(t.len < s.len * .95)) {
-                            if (s.qbeg <= t.qbeg && s.qbeg + s.len - t.qbeg >= s.len >> 2 && t.qbeg - s.qbeg != t.rbeg - s.rbeg) hit = true;
-                            else if (t.qbeg <= s.qbeg && t.qbeg + t.len - s.qbeg >= s.len >> 2 && s.qbeg - t.qbeg != s.rbeg - t.rbeg) hit = true;
-                        }
-                    }
-                    other = gballot<G>(hit, gbase) != 0;
-                }
-                drop = !other;
-            }
-            if (drop) { av[cur].qb = -1; av[cur].qe = -1; ord[k] = -1; continue; }
-            if (V.mode == ADV_FINISH) continue;        // a survivor whose alignment exists
-            if (V.mode == ADV_REST) {                  // this survivor and everything behind it go into the round; ADV_FINISH walks on from here
-                unsigned long long cnt = 0;
-                i64 nL = 0, nR = 0, nB = 0;
-                for (int c2 = c; c2 < nc; ++c2) {
-                    const meme_chain ch2 = P.chains[c0 + c2];
-                    const int* ord2 = P.order + s0 + ch2.seed_beg;
-                    const int k1 = c2 == c ? k : ch2.n_seeds - 1;
-                    const i64 rmax0 = V.rmax[2 * (c0 + c2)], rmax1 = V.rmax[2 * (c0 + c2) + 1];
-                    for (int k2 = k1 - lane; k2 >= 0; k2 -= G) {
-                        const int il = ord2[k2];
-                        V.sel[s0 + ch2.seed_beg + il] = 1;
-                        adv_count(P.seeds[s0 + ch2.seed_beg + il], rmax0, rmax1, l_query, nL, nR, nB);
-                    }
-                    cnt += k1 + 1;
-                }
-                for (int d = G / 2; d >= 1; d >>= 1) { nL += __shfl_xor(nL, d); nR += __shfl_xor(nR, d); nB += __shfl_xor(nB, d); }
-                if (lane == 0) { V.act[r] = 1; V.state[r] = make_int4(c, k, cur, 0); V.cntS[r] = (i64)cnt; V.cntL[r] = nL; V.cntR[r] = nR; V.cntB[r] = nB; }
-                return;
-            }
-            if (lane == 0) {                           // this round's seed of the read
-                V.sel[s0 + ch.seed_beg + ord[k]] = 1;
-                V.act[r] = 1;
-                V.state[r] = make_int4(c, k - 1, cur + 1, 0);
-                V.cntS[r] = 1;
-                i64 nL = 0, nR = 0, nB = 0;
-                adv_count(s, V.rmax[2 * (c0 + c)], V.rmax[2 * (c0 + c) + 1], l_query, nL, nR, nB);
-                V.cntL[r] = nL; V.cntR[r] = nR; V.cntB[r] = nB;
-            }
-            return;
+            for (int d = G / 2; d >= 1; d >>= 1) { nL += __shfl_xor(nL, d); nR += __shfl_xor(nR, d); nB += __shfl_xor(nB, d); }
+            if (lane == 0) { V.act[r] = 1; V.state[r] = make_int4(c, k, cur, 0); V.cntS[r] = (i64)cnt; V.cntL[r] = nL; V.cntR[r] = nR; V.cntB[r] = nB; }
+            return true;
         }
-        st.y = 0;                                      // (later chains start at their best seed; st.x no longer equals c)
-    }
-    if (lane == 0) V.state[r] = make_int4(nc, 0, cur, 0);
+        if (lane == 0) {                               // this round's seed of the read
+            V.sel[s0 + ch.seed_beg + P.order[s0 + ch.seed_beg + k]] = 1;
+            V.act[r] = 1;
+            V.state[r] = make_int4(c, k - 1, cur + 1, 0);
+            V.cntS[r] = 1;
+            plan(s, c0 + c);
+            V.cntL[r] = nL; V.cntR[r] = nR; V.cntB[r] = nB;
+        }
+        return true;
+    });
+    if (met >= 0 && lane == 0) V.state[r] = make_int4(nc, 0, met, 0);
 }
 
 // reads with more than EXT_LIGHT chained seeds: the list the wavefront-per-read launches walk (order is irrelevant: everything is indexed by read)

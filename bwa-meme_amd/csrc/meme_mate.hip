@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "meme_common.h"
+#include "meme_ext_rules.h"      // bns_clamp_to_mid
 
 namespace {
 
@@ -83,18 +84,8 @@ __global__ void __launch_bounds__(256) k_mate_plan(MateArgs A) {
                     }
                     if (rb < 0) rb = 0;
                     if (re > A.l_pac << 1) re = A.l_pac << 1;
-                    if (rb < re) {                                                       // bns_fetch_seq: the sequence of the window's midpoint, its strand
-                        const i64 mid = (rb + re) >> 1;
-                        const bool mrev = mid >= A.l_pac;
-                        const i64 fpos = mrev ? (A.l_pac << 1) - 1 - mid : mid;
-                        int lo = 0, hi = A.n_contigs - 1;
-                        while (lo < hi) { const int c = (lo + hi + 1) >> 1; if (A.contig_off[c] <= fpos) lo = c; else hi = c - 1; }
-                        rid = lo;
-                        i64 far_beg = A.contig_off[lo], far_end = far_beg + A.contig_len[lo];
-                        if (mrev) { const i64 t = far_beg; far_beg = (A.l_pac << 1) - far_end; far_end = (A.l_pac << 1) - t; }
-                        rb = rb > far_beg ? rb : far_beg;
-                        re = re < far_end ? re : far_end;
-                    }
+                    // bns_fetch_seq: the sequence of the window's midpoint, its strand
+                    if (rb < re) rid = bns_clamp_to_mid(A.l_pac, A.contig_off, A.contig_len, A.n_contigs, (rb + re) >> 1, rb, re);
                     if (rec.rid == rid && re - rb >= A.min_seed_len) {                   // :1131
                         if (WRITE) {
                             meme_kswv_job J;

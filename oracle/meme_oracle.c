@@ -1258,10 +1258,17 @@ static int o_flt_window_base(const uint8_t* text, int64_t l_pac, int64_t p) {
     return p < l_pac ? c : 3 - c;
 }
 
+int orc_seed_sw_window(int qlen, const uint8_t* query, const uint8_t* text, int64_t l_pac, int64_t rb, int tlen, const orc_ext_opt* o) {
+    uint8_t win[200];
+    int i;
+    if (tlen > 200) return -1;
+    for (i = 0; i < tlen; ++i) win[i] = (uint8_t)o_flt_window_base(text, l_pac, rb + i);
+    return o_ksw_i16_score(qlen, query, tlen, win, o);
+}
+
 int orc_seed_sw(const uint8_t* read, int l_query, const orc_cseed* s, const uint8_t* text, int64_t l_pac, const int64_t* contig_off,
                 const int32_t* contig_len, int n_contigs, const orc_ext_opt* o) {
-    int qb, qe, lo, hi, i, sc;
-    uint8_t win[200];
+    int qb, qe, lo, hi;
     int64_t rb, re, mid, fpos, far_beg, far_end;
     if (s->len >= 200) return -1;                            /* MEM_SHORT_LEN, :250, :502 */
     qb = s->qbeg; qe = s->qbeg + s->len;
@@ -1281,9 +1288,7 @@ int orc_seed_sw(const uint8_t* read, int l_query, const orc_cseed* s, const uint
     if (mid >= l_pac) { const int64_t t = far_beg; far_beg = (l_pac << 1) - far_end; far_end = (l_pac << 1) - t; }
     if (rb < far_beg) rb = far_beg;
     if (re > far_end) re = far_end;
-    for (i = 0; i < (int)(re - rb); ++i) win[i] = (uint8_t)o_flt_window_base(text, l_pac, rb + i);
-    sc = o_ksw_i16_score(qe - qb, read + qb, (int)(re - rb), win, o);
-    return sc;
+    return orc_seed_sw_window(qe - qb, read + qb, text, l_pac, rb, (int)(re - rb), o);
 }
 
 /* One read: seeds that fail the test leave their chains (the read's seeds are packed to the front, chain after chain; seed_beg / n_seeds

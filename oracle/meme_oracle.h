@@ -146,6 +146,8 @@ int orc_extend_batch_scored(const uint8_t* reads, const int64_t* read_off, int64
  * mem_seed_t::score afterwards; returns the number of seeds that stay. */
 int orc_seed_sw(const uint8_t* read, int l_query, const orc_cseed* s, const uint8_t* text, int64_t l_pac, const int64_t* contig_off,
                 const int32_t* contig_len, int n_contigs, const orc_ext_opt* o);
+/* its alignment alone, for a caller that poses the window itself: the query against the tlen bases the aligner reads at rb of the fwd + rc text */
+int orc_seed_sw_window(int qlen, const uint8_t* query, const uint8_t* text, int64_t l_pac, int64_t rb, int tlen, const orc_ext_opt* o);
 int orc_flt_chained_seeds(const uint8_t* read, int l_query, orc_chain* chains, int n_chains, orc_cseed* seeds, int32_t* score, const uint8_t* text,
                           int64_t l_pac, const int64_t* contig_off, const int32_t* contig_len, int n_contigs, const orc_ext_opt* o, int min_chain_weight,
                           int64_t* n_sw);

@@ -193,6 +193,86 @@ def flt_workload(min_chain_weight=0, n_long=120, n_short=400, lo=800, hi=1300):
             "text": text, "l_pac": l_pac, "contig_off": G["contig_off"], "contig_len": G["contig_len"]}
 
 
+def ext_seam_workload(copies=((3, 2), (2, 3), (2, 32), (2, 48), (2, 70)), reads_per_unit=3, n=140_000, seed=907):
+    """Reads with a chosen number of chained seeds, for the seams of the extension stage's lane code (eight lanes or a wavefront per read, records taken 64 at
+    a time): per (seeds, k) of `copies` a random 150-bp unit planted k times in a random genome, and reads that are the unit with seeds - 1 substitutions --
+    `seeds` exact stretches per copy, one chain of that many seeds per copy; the alignment of a chain's best seed spans the read and contains the others,
+    which the purge drops.  (Up to 10 copies the re-seeding round adds a seed per copy: 2 copies of 3 stretches are 8 chained seeds, 3 copies of 2 are 9; the
+    caller asserts the counts it needs.)  Seeds and chains from the oracle; layout of ext_golden_inputs() + "kind": the index into `copies` of every read."""
+    import oracle_py as O
+    from pymeme import hipapi, hostapi
+    rng = np.random.default_rng(seed)
+    g = rng.integers(0, 4, size=n, dtype=np.uint8)
+    bounds = np.linspace(0, n, 4).astype(np.int64)                  # synth.write_fasta(contigs=3)
+    slots = [p for p in range(500, n - 500, 450) if not any(p - 10 < b < p + 160 for b in bounds)]
+    assert len(slots) >= sum(k for _, k in copies)
+    slots = [slots[i] for i in rng.permutation(len(slots))]
+    reads, kind = [], []
+    for u, (n_seeds, k) in enumerate(copies):
+        unit = rng.integers(0, 4, size=150, dtype=np.uint8)
+        for _ in range(k):
+            p = slots.pop()
+            g[p:p + 150] = unit
+        for j in range(reads_per_unit):
+            r = unit.copy()
+            cuts = np.linspace(0, 150, n_seeds + 1).astype(int)[1:-1] + j        # the substitutions: the read in n_seeds stretches of about equal length
+            r[cuts] = (r[cuts] + 1 + j % 3) & 3
+            if j % 2:
+                r = (3 - r[::-1]).astype(np.uint8)
+            reads.append(np.ascontiguousarray(r)); kind.append(u)
+    text = hipapi.fwd_rc_text(g)
+    _, sa = hostapi.build_sa(g)
+    idx = O.Index(text, sa)
+    read_off = np.arange(0, 150 * (len(reads) + 1), 150, dtype=np.int64)
+    sm, nsm, hits, nh, _ = O.seed_batch(idx, np.concatenate(reads), read_off, smem_cap=512, hit_cap=1 << 14)
+    contig_off = bounds[:-1].copy()
+    contig_len = np.diff(bounds).astype(np.int32)
+    copt = O.default_chain_opt(n)
+    ch_list, sd_list, frac, coff, soff = [], [], [], [0], [0]
+    for r in range(len(reads)):
+        rc, ch, sd, tree, fr = O.chain_read(sm[r, :nsm[r]], hits[r, :nh[r]], 150, contig_off, np.zeros(3, np.uint8), copt)
+        assert rc >= 0
+        ch_list.append(ch); sd_list.append(sd); frac.append(fr)
+        coff.append(coff[-1] + rc); soff.append(soff[-1] + sd.shape[0])
+    return {"genome": g, "reads": np.concatenate(reads), "read_off": read_off, "chain_off": np.array(coff, np.int64), "chains": np.concatenate(ch_list),
+            "seed_off": np.array(soff, np.int64), "seeds": np.concatenate(sd_list), "frac_rep": np.array(frac, np.float32), "text": text, "l_pac": n,
+            "contig_off": contig_off, "contig_len": contig_len, "kind": np.array(kind)}
+
+
+def flt_hsp(l_query, min_chain_weight, a=1):
+    """min_HSP_score of mem_flt_chained_seeds for a read length (src/bwamem.cpp:579-583: float coefficients, double min_l), -1 where the filter does not run"""
+    f = np.float32
+    min_l = float(f(1.1) * f(min_chain_weight)) if min_chain_weight else float(f(5.5)) * float(np.log(l_query))
+    if min_l > float(f(0.05) * f(l_query)):
+        return -1
+    return max(0, int(a * min_l + .499))
+
+
+def seed_sw_window(rbeg, qbeg, length, l_query, l_pac, contig_off, contig_len, ext=50, short_len=200):
+    """The alignment mem_seed_sw poses for a chained seed (src/bwamem.cpp:494-520 with bns_fetch_seq, src/bntseq.cpp:541-570), statement by statement in
+    Python integers: (rb, re, qb, qe), or None where the seed is kept without one."""
+    if length >= short_len:
+        return None
+    qb, qe, rb, re = qbeg, qbeg + length, rbeg, rbeg + length
+    mid = (rb + re) >> 1
+    qb, qe = max(qb - ext, 0), min(qe + ext, l_query)
+    rb, re = max(rb - ext, 0), min(re + ext, l_pac << 1)
+    if rb < l_pac < re:
+        if mid < l_pac:
+            re = l_pac
+        else:
+            rb = l_pac
+    if qe - qb >= short_len or re - rb >= short_len:
+        return None
+    is_rev = mid >= l_pac
+    fpos = (l_pac << 1) - 1 - mid if is_rev else mid
+    rid = max(k for k in range(len(contig_off)) if int(contig_off[k]) <= fpos)
+    far_beg, far_end = int(contig_off[rid]), int(contig_off[rid]) + int(contig_len[rid])
+    if is_rev:
+        far_beg, far_end = (l_pac << 1) - far_end, (l_pac << 1) - far_beg
+    return max(rb, far_beg), min(re, far_end), qb, qe
+
+
 def gcig_workload(n=3000, seed=77, read_len=(40, 251), bands=(1, 3, 10, 30, 100, 200, 400)):
     """Inputs of the CIGAR-kernel tests (tests/golden/gcig_golden.npz): a 300 kbp genome, reads of 40-250 bases sampled with
     substitutions, indels (up to 30 bases) and an occasional N, from both strands; per read one or two global-alignment jobs the way

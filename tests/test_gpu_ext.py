@@ -180,6 +180,44 @@ def test_device_records_equal_oracle_with_other_options(tmp_path, w, clip, zdrop
     _assert_same(R2["regs"], want[keep], want["frac_rep"].view(np.uint32)[keep])
 
 
+_seams = []
+
+
+def _seam_workload():
+    """common.ext_seam_workload and the oracle's records of it, once"""
+    if not _seams:
+        from common import ext_seam_workload
+        I = ext_seam_workload()
+        want, _ = O.extend_batch(I["reads"], I["read_off"], I["chain_off"], I["chains"], I["seed_off"], I["seeds"], I["frac_rep"], I["text"], I["l_pac"],
+                                 I["contig_off"], I["contig_len"])
+        _seams.append((I, want))
+    return _seams[0]
+
+
+def test_seams_of_the_purge_lanes_on_reads_of_planted_repeats(tmp_path):
+    """The purge's lane code (ext_seed_dropped<G>, under k_ext_purge and k_ext_advance<8 | 64>) at its seams: reads with exactly 8 and 9 chained seeds (the last
+    read eight lanes take and the first a wavefront takes under "ext_split"), exactly 64, 65-128 and more than 128 (one, two and three chunks of 64 earlier
+    records), purged records behind the 64th of their read, seeds that start the read or end it (no left / right job).  The whole-batch records and, in rounds,
+    the survivors against the oracle."""
+    I, want = _seam_workload()
+    per_read = np.diff(I["seed_off"])
+    for cond in (per_read == 8, per_read == 9, per_read == 64, (per_read >= 65) & (per_read <= 128), per_read >= 129):
+        assert cond.any(), per_read
+    purged = (want["qb"] == -1) & (want["qe"] == -1)
+    within = np.arange(want.shape[0]) - np.repeat(I["seed_off"][:-1], per_read)
+    assert (purged & (within >= 64)).any() and (purged & (within < 64)).any()
+    assert (I["seeds"]["qbeg"] == 0).any() and (I["seeds"]["qbeg"] + I["seeds"]["len"] == 150).any()
+    R = _device_records(tmp_path, I)
+    assert np.array_equal(R["reg_off"], I["seed_off"])
+    _assert_same(R["regs"], want, want["frac_rep"].view(np.uint32))
+    keep, want_off = _live_of(I["seed_off"], want["qb"], want["qe"])
+    for rounds in (0, 1, 3):
+        R = _device_records(tmp_path, I, live_only=True, rounds=rounds)
+        assert np.array_equal(R["reg_off"], want_off), rounds
+        _assert_same(R["regs"], want[keep], want["frac_rep"].view(np.uint32)[keep])
+        assert R["n_ext_seeds"] == keep.shape[0] if rounds == 0 else int(keep.sum()) <= R["n_ext_seeds"] < keep.shape[0], rounds
+
+
 @pytest.mark.parametrize("W,penalties", [(5, None), (10, None), (20, None), (20, (2, 9, 3, 2, 5, 1))])
 def test_seed_filter_on_the_device_equals_oracle(tmp_path, W, penalties):
     """mem_flt_chained_seeds (src/bwamem.cpp:565-598) between chaining and extension.  It runs where 1.1 W <= 0.05 x read length: for every
