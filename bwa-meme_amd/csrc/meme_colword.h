@@ -1,6 +1,7 @@
 // Column words of the lane-per-job Smith-Waterman kernels (k_bsw_lane / k_bsw_lane_circ of meme_bsw.hip, k_kswv / k_seedsw of meme_kswv.hip),
 // device only.  A lane keeps the state of DP column j in one 32-bit LDS word, laid out [column][lane] (bank-conflict free whatever column each
-// lane is at): the query code in the low byte, then two 12-bit fields.  Which two values the fields hold, and the recurrence, is each kernel's own.
+// lane is at): the query code in the low byte, then two 12-bit fields.  Which two values the fields hold, and the recurrence, is each kernel's own
+// (k_kswv and k_seedsw share cw_gotoh_cell).
 #pragma once
 #include "meme_common.h"
 
@@ -26,6 +27,22 @@ __device__ __forceinline__ unsigned cw_score_tab(int tb, int match, int mismatch
 }
 // the score of the column whose word is `cw`: v_perm_b32 picks byte `code` of {tab_hi, tab_lo} (selector byte 0; the other result bytes are not looked at)
 __device__ __forceinline__ int cw_score(unsigned tab_hi, unsigned tab_lo, unsigned cw) { return (int)(signed char)(__builtin_amdgcn_perm(tab_hi, tab_lo, cw) & 0xffu); }
+
+// One Gotoh cell of a local alignment on a column word {code, H(i-1, j), the gap state that travels down the column}; the gap state that travels along the
+// row (`along`) and the diagonal stay in registers.  Gap states are opened from H and never negative.  H(i, j) goes to `seen` (the caller's row maximum), the
+// column's next word to `slot`.  CAPPED: diagonal + score saturates at `cap` (the unsigned bytes of the reference's int8 lanes).
+template <bool CAPPED, class Seen> __device__ __forceinline__ void cw_gotoh_cell(lds_u32 slot, unsigned cur, unsigned tab_hi, unsigned tab_lo, int cap, int& diag, int& along,
+                                                                                 int oe_down, int e_down, int oe_along, int e_along, const Seen& seen) {
+    const int hold = (int)((cur >> 8) & 0xfffu), down = (int)(cur >> 20);
+    int m = diag + cw_score(tab_hi, tab_lo, cur);
+    if (CAPPED) m = m < cap ? m : cap;
+    const int h = max3_i32(m, along, down);
+    seen(h);
+    const int down2 = max3_i32(h - oe_down, down - e_down, 0);      // (in this order: with the row's state first k_kswv's row loop measured 1 % slower)
+    along = max3_i32(h - oe_along, along - e_along, 0);
+    *slot = cw_repack(h, down2, cur);
+    diag = hold;
+}
 
 // A row's maximum and its column travel as one key (h << 10 | column term), one accumulator per position of the four-cell unrolled loop, each
 // holding the column term of its trip's FIRST cell: position p is `step` * p further (step = 1: column, rightmost wins; -1: 1023 - column, first wins)

@@ -71,6 +71,16 @@ KS_HD FltWindow flt_window(const meme_chain_seed& t, int l_query, int64_t l_pac,
     W.job = true;
     return W;
 }
+// The base at position p of the window is the one the REFERENCE's call reads, which is not the genome's: mem_kernel1_core_Learned is handed worker_t::rc_pac
+// as `pac` (src/bwamem.cpp:1770) -- the 2-bit fwd + rc text with the four bases of every BYTE in reverse order, as the learned index's key extraction wants
+// them (src/fastmap.cpp:440-457; "BitReverseTable256", src/LearnedIndex_seeding.h:129-137, reverses 2-bit groups) -- and bns_get_seq (src/bntseq.cpp:515-539)
+// reads it with the plain _get_pac: within every aligned group of four bases the order is reversed; windows on the reverse strand are fetched from the forward
+// half and complemented (:526-531).  SAM output depends on it (under -W), so it is reproduced, not corrected.  pos: the position whose 2-bit code is read.
+struct FltBase { int64_t pos; bool complement; };
+KS_HD FltBase flt_base_index(int64_t l_pac, int64_t p) {
+    const int64_t k = p < l_pac ? p : (l_pac << 1) - 1 - p;
+    return FltBase{(k & ~(int64_t)3) + 3 - (k & 3), p >= l_pac};
+}
 // v: FLT_OFF, -1 (no alignment: kept, :502 / :515) or the alignment's score; the seed stays (:589) with the score (:591)
 KS_HD bool flt_keeps(int v, int hsp) { return v == FLT_OFF || v < 0 || v >= hsp; }
 KS_HD int flt_kept_score(int v, int len, int a) { return v == FLT_OFF ? len : (v < 0 ? len * a : v); }

@@ -21,6 +21,7 @@
 
 #include "meme_common.h"
 #include "meme_ext_rules.h"      // bns_clamp_to_mid
+#include "meme_kswv_rules.h"     // every decision of the step
 
 namespace {
 
@@ -38,13 +39,6 @@ struct MateArgs {
     int32_t* gar; meme_kswv_job* jobs; MateAux* aux;
 };
 
-__device__ __forceinline__ int infer_dir(i64 l_pac, i64 b1, i64 b2, i64* dist) {          // mem_infer_dir, src/bwamem_pair.cpp:58-65
-    const int r1 = b1 >= l_pac, r2 = b2 >= l_pac;
-    const i64 p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-    *dist = p2 > b1 ? p2 - b1 : b1 - p2;
-    return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
-
 template <bool WRITE>
 __global__ void __launch_bounds__(256) k_mate_plan(MateArgs A) {
     for (i64 r = (i64)blockIdx.x * 256 + threadIdx.x; r < A.n; r += (i64)gridDim.x * 256) {
@@ -54,7 +48,7 @@ __global__ void __launch_bounds__(256) k_mate_plan(MateArgs A) {
         const meme_mate_reg* ma = A.regs + A.reg_off[m];
         const int nm = (int)(A.reg_off[m + 1] - A.reg_off[m]);
         const int l_ms = (int)(A.read_off[A.first + m + 1] - A.read_off[A.first + m]);
-        const int xtra = 0x40000 | 0x80000 | (l_ms * A.a < 250 ? 0x10000 : 0) | (A.min_seed_len * A.a);      // KSW_XSUBO | KSW_XSTART | KSW_XBYTE | threshold (:1135)
+        const int xtra = mate_xtra(l_ms, A.a, A.min_seed_len);
         i64 nq = 0, nj = 0, nr = 0;
         i64 q0 = 0, j0 = 0, r0 = 0, y0 = 0, jb = 0;
         if (WRITE) { q0 = A.offQ[r]; j0 = A.offJ[r]; r0 = A.offR[r]; y0 = A.offY[r]; jb = A.offJ[r / A.batch_reads * A.batch_reads]; }
@@ -62,36 +56,21 @@ __global__ void __launch_bounds__(256) k_mate_plan(MateArgs A) {
         for (int j = 0; j < na && nq < A.max_matesw; ++j) {
             const meme_mate_reg rec = a[j];
             if (!(rec.score >= top - A.pen_unpaired)) continue;                          // :690
-            int skip = 0;                                                                 // bit o: orientation o is not tried
-            for (int o = 0; o < 4; ++o) skip |= (A.pes[o].failed ? 1 : 0) << o;          // :1081-1083
-            for (int k = 0; k < nm; ++k) {                                               // :1085-1091
-                i64 dist;
-                const int o = infer_dir(A.l_pac, rec.rb, ma[k].rb, &dist);
-                if (dist >= A.pes[o].low && dist <= A.pes[o].high) skip |= 1 << o;
-            }
+            const int skip = mate_skip_mask(A.pes, A.l_pac, rec.rb, ma, nm);
             int rid = -1;                                                                 // (carried from one orientation to the next, as in the reference)
             for (int o = 0; o < 4; ++o) {
                 int idx = -1;
-                if (!(skip >> o & 1) && skip != 15) {
-                    const int is_rev = (o >> 1) != (o & 1), is_larger = !(o >> 1);       // :1108-1109
-                    i64 rb, re;
-                    if (!is_rev) {                                                       // :1118-1125
-                        rb = is_larger ? rec.rb + A.pes[o].low : rec.rb - A.pes[o].high;
-                        re = (is_larger ? rec.rb + A.pes[o].high : rec.rb - A.pes[o].low) + l_ms;
-                    } else {
-                        rb = (is_larger ? rec.rb + A.pes[o].low : rec.rb - A.pes[o].high) - l_ms;
-                        re = is_larger ? rec.rb + A.pes[o].high : rec.rb - A.pes[o].low;
-                    }
-                    if (rb < 0) rb = 0;
-                    if (re > A.l_pac << 1) re = A.l_pac << 1;
+                if (mate_tries(skip, o)) {
+                    const MateWindow W = mate_window(o, A.pes[o], rec.rb, l_ms, A.l_pac);
+                    i64 rb = W.rb, re = W.re;
                     // bns_fetch_seq: the sequence of the window's midpoint, its strand
                     if (rb < re) rid = bns_clamp_to_mid(A.l_pac, A.contig_off, A.contig_len, A.n_contigs, (rb + re) >> 1, rb, re);
-                    if (rec.rid == rid && re - rb >= A.min_seed_len) {                   // :1131
+                    if (mate_is_job(rec.rid, rid, rb, re, A.min_seed_len)) {
                         if (WRITE) {
                             meme_kswv_job J;
                             J.idr = r0 + nr; J.idq = y0 + nj * l_ms; J.len1 = (int)(re - rb); J.len2 = l_ms; J.xtra = xtra; J.pad = 0;
                             A.jobs[j0 + nj] = J;
-                            MateAux X; X.rb = rb; X.read = (int)(A.first + m); X.is_rev = is_rev;
+                            MateAux X; X.rb = rb; X.read = (int)(A.first + m); X.is_rev = W.is_rev;
                             A.aux[j0 + nj] = X;
                             idx = (int)(j0 + nj - jb);                                   // relative to the worker batch's first job: what the third step indexes with
                         }
@@ -122,12 +101,7 @@ __global__ void __launch_bounds__(256) k_mate_seq(const meme_kswv_job* __restric
     }
     const uint8_t* ms = reads + read_off[X.read];
     uint8_t* q = qer + J.idq;
-    for (int l = lane; l < J.len2; l += 64) {
-        uint8_t c;
-        if (X.is_rev) { const uint8_t b = ms[J.len2 - 1 - l]; c = b < 4 ? (uint8_t)(3 - b) : (uint8_t)4; }
-        else c = ms[l];
-        q[l] = c;
-    }
+    for (int l = lane; l < J.len2; l += 64) q[l] = mate_query_base(ms, J.len2, l, X.is_rev != 0);
 }
 
 // first gar entry and first job of every worker batch (batch b = reads [b * batch_reads, ...)), + the totals behind the last one
