@@ -377,6 +377,8 @@ static int index_build_from(meme_ctx* ctx, int64_t n, int64_t l1_bytes, int64_t 
     if ((rc = own_alloc(ctx, &d_pac, (size_t)words * 8))) return rc;
     if ((rc = own_alloc(ctx, &d_l2, (size_t)n_l2 * 32))) return rc;
     if ((rc = own_alloc(ctx, &d_l1, (size_t)(n_l1 > 0 ? n_l1 : 1) * 32))) return rc;
+    // no third layer: one placeholder record, which a second-layer record that claims a route (bit 63 of its error word) still reads
+    if (n_l1 == 0) HIP_TRY(hipMemsetAsync(d_l1, 0, 32, ctx->stream));
     // staging buffer: the 5-byte position image (the largest input), reused for the text bytes and the parameter records
     // (a streaming source needs it for the text bytes only: the 31 GB position image and the 24-byte records pass through small rings)
     size_t tmp_bytes = stream ? (size_t)n + 64 : (size_t)meme_index_pos5_bytes(n);
@@ -564,6 +566,7 @@ extern "C" int meme_index_load_files(meme_ctx* ctx, const char* prefix) {
 
 extern "C" int meme_index_attach(meme_ctx* ctx, const meme_index_arrays* a) {
     if (!ctx || !a || !a->d_sa_ent || !a->d_pac64 || !a->d_l2 || a->sa_num < 64) return MEME_E_ARG;
+    if (a->l1_records > 0 && !a->d_l1) { meme_set_error("meme_index_attach: l1_records = %lld with a null d_l1", (long long)a->l1_records); return MEME_E_ARG; }
     drop_index(ctx);
     int rc = set_rmi(ctx, a->l2_records, a->l1_records);
     if (rc) return rc;

@@ -25,8 +25,8 @@
 //  * Partition point, lower and upper interval edge are all "where does a monotone predicate flip?": a window that
 //    does not contain the flip moves a bracket [lo, hi] and the next window gallops or bisects -- relocations and
 //    edge scans are just more trips through the same loop.
-//  * The learned model is a hint: model error bounds are never needed, so any parameter file the
-//    reference loads is accepted.
+//  * The learned model is a hint: any records give the same seeds -- finite or not, any error word, any third-layer
+//    pointers (tests/test_gpu_seed_model_hint.py); only the table sizes are the loader's to check.
 //  * Reads are packed once per batch by k_pack_reads (2 bits/base, both strands, first base in the top bits of each
 //    u64, plus N masks) and staged in LDS when pulled; a 32-base query word at any offset is a funnel shift of two
 //    LDS words, replacing the reference's 8 pre-shifted copies of every read.
@@ -399,7 +399,7 @@ __device__ __forceinline__ i64 rmi_lookup(glb_rmi l2, glb_rmi l1, i64 n_l1, int 
     if (err >> 63) {
         u64 ps = (err >> 32) & 0x7fffffffull;
         double pn = (double)(err & 0xffffffffull) - 1.0;
-        double c = f < 0.0 ? 0.0 : (f > pn ? pn : f);
+        double c = !(f >= 0.0) ? 0.0 : (f > pn ? pn : f);   // (a NaN route goes to record ps)
         u64 j = ps + (u64)c;
         if (j >= (u64)n_l1) j = n_l1 > 0 ? (u64)n_l1 - 1 : 0;   // a malformed table cannot send the load astray
         f = fma(l1[j].slope, x, l1[j].icpt);
@@ -407,7 +407,7 @@ __device__ __forceinline__ i64 rmi_lookup(glb_rmi l2, glb_rmi l1, i64 n_l1, int 
     }
     err_out = err;
     double top = (double)n - 1.0;
-    if (f < 0.0) return 0;
+    if (!(f >= 0.0)) return 0;          // negative or NaN (a NaN fails every comparison: `f < 0.0` would let it through to the cast)
     if (f > top) return n - 1;
     return (i64)f;
 }

@@ -112,6 +112,11 @@ static uint32_t locate(const orc_index* idx, const uint8_t* q, int64_t valid_len
     return m_hi;
 }
 
+static void count_search(orc_counters* ctr, int64_t valid_len) {
+    ctr->searches++;
+    if (ctr->shortest_query == 0 || valid_len < ctr->shortest_query) ctr->shortest_query = valid_len;
+}
+
 /* Level search shared by right_smem_search (src/LearnedIndex_seeding.cpp:2359-2574), mem_search
  * (:2898-2943, 3155-3196) and their ISA-seeded twins (:3417-3461 ...):
  *   L = maxLCP; loop { [s,e] = maximal SA run around best with LCP >= L; if (e-s+1 >= min_intv) stop;
@@ -121,7 +126,7 @@ uint32_t orc_search(const orc_index* idx, const uint8_t* q, int64_t valid_len, i
     int64_t best;
     uint32_t L = locate(idx, q, valid_len, &best);
     int64_t s = best, e = best;
-    if (ctr) ctr->searches++;
+    if (ctr) count_search(ctr, valid_len);
     for (;;) {
         s = extend_down(idx, q, L, s);
         e = extend_up(idx, q, L, e);
@@ -385,7 +390,7 @@ static void seed_strategy(rstate* r) {
         const uint8_t* q = r->fw + r->pivot;
         int64_t best;
         uint32_t L = locate(idx, q, valid, &best);
-        if (r->ctr) r->ctr->searches++;
+        if (r->ctr) count_search(r->ctr, valid);
         if (g_census_plcp) {                 /* third round: the longest match and whether it is alone -- what a diagonal with plcp[u] < L_d also tells */
             int64_t s1 = extend_down(idx, q, L, best), e1 = extend_up(idx, q, L, best);
             r->round_tag = 2;
@@ -494,6 +499,7 @@ int orc_seed_batch(const orc_index* idx, const uint8_t* reads, const int64_t* re
         {
             total.searches += mine.searches; total.level_steps += mine.level_steps;
             total.smems += mine.smems; total.hits += mine.hits;
+            if (mine.shortest_query && (!total.shortest_query || mine.shortest_query < total.shortest_query)) total.shortest_query = mine.shortest_query;
         }
     }
     if (ctr) *ctr = total;

@@ -43,6 +43,7 @@ typedef struct {
     int64_t searches;        /* locate operations (right/left, any round) */
     int64_t level_steps;     /* interval (count) evaluations */
     int64_t smems, hits;
+    int64_t shortest_query;  /* fewest valid bases any search was handed (0: no search) */
 } orc_counters;
 
 /* Seeds one read (codes 0..3, >=4 = N).  Returns 0, or -1 if a capacity was exceeded. */

@@ -38,7 +38,7 @@ class OrcSeedParams(C.Structure):
 
 class OrcCounters(C.Structure):
     _fields_ = [("searches", C.c_int64), ("level_steps", C.c_int64), ("smems", C.c_int64),
-                ("hits", C.c_int64)]
+                ("hits", C.c_int64), ("shortest_query", C.c_int64)]
 
 
 class OrcBswParams(C.Structure):
@@ -100,6 +100,28 @@ def seed_batch(index: Index, reads: np.ndarray, read_off: np.ndarray, params=Non
     if rc != 0:
         raise RuntimeError("oracle capacity exceeded (raise smem_cap / hit_cap)")
     return smems, n_smems, hits, n_hits, ctr
+
+
+def shortest_queries(index: Index, reads: np.ndarray, read_off: np.ndarray, params=None):
+    """Per read, the fewest valid bases the pivot logic hands to any search (orc_seed_read's shortest_query; 0 for a read
+    that is never searched).  A query shorter than 32 bases is looked up under a T-padded key."""
+    params = params or default_seed_params()
+    reads = np.ascontiguousarray(reads, dtype=np.uint8).reshape(-1)
+    read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+    n = read_off.shape[0] - 1
+    smems = np.zeros(8192, dtype=MEM_TL_DTYPE)
+    hits = np.zeros(1 << 20, dtype=np.uint64)
+    out = np.zeros(n, np.int64)
+    ns, nh = C.c_int32(0), C.c_int64(0)
+    for r in range(n):
+        ctr = OrcCounters()
+        rc = lib().orc_seed_read(C.byref(index.c), C.c_void_p(reads.ctypes.data + int(read_off[r])), C.c_int32(int(read_off[r + 1] - read_off[r])),
+                                 C.byref(params), C.c_void_p(smems.ctypes.data), C.c_int32(smems.shape[0]), C.byref(ns),
+                                 C.c_void_p(hits.ctypes.data), C.c_int64(hits.shape[0]), C.byref(nh), C.byref(ctr))
+        if rc != 0:
+            raise RuntimeError("oracle capacity exceeded (read %d)" % r)
+        out[r] = ctr.shortest_query
+    return out
 
 
 REFPATH_COUNTERS = ("lookups", "partial_lookups", "compares", "extra_words", "hits", "smems", "searches")

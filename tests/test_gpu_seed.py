@@ -231,6 +231,15 @@ def test_index_files_loader_errors_and_equals_host_loader(g1, tmp_path):
         assert _gpu_dump(c, reads, off) == want
         c.load_index_files(g1)                                   # a ctx can be re-loaded
         assert _gpu_dump(c, reads, off) == want
+        # meme_index_attach: a third layer that is announced has to be there (rmi_lookup would follow a route into it)
+        ia = c.describe_index()
+        c2 = hipapi.Context(0)
+        try:
+            with pytest.raises(hipapi.MemeError, match="null d_l1"):
+                c2.attach_index(hipapi.IndexArrays(ia.sa_num, ia.d_sa_ent, ia.d_pac64, ia.d_l2, ia.l2_records, None, 5))
+        finally:
+            c2.close()
+        assert _gpu_dump(c, reads, off) == want
     finally:
         c.close()
 

@@ -67,6 +67,19 @@ def test_refpath_restatement_agrees_with_semantic_oracle(g1_index, length):
     assert ctr["compares"] > ctr["lookups"] > 0 and ctr["smems"] == int(ns.sum())
 
 
+def test_shortest_query_counter(g1_index):
+    """orc_counters.shortest_query, the fewest valid bases any search of a read was handed: a read without N is never searched below
+    min_seed_len bases' worth of tail, two N's three bases apart leave a query of the two bases between them, an all-N read is not searched."""
+    a = g1_index.text[1000:1150].copy()
+    b = a.copy()
+    b[[100, 103]] = 4
+    reads = np.concatenate([a, b, np.full(30, 4, np.uint8)])
+    off = np.array([0, 150, 300, 330], np.int64)
+    v = O.shortest_queries(g1_index, reads, off)
+    assert v[0] >= 19 and v[1] == 2 and v[2] == 0
+    assert O.seed_batch(g1_index, reads, off, threads=2)[4].shortest_query == 2        # the batch's counter: the least over its reads
+
+
 def test_chain_oracle_equals_reference_golden():
     """orc_chain_read (restatement of mem_chain_Learned + test_and_merge + mem_chain_weight + mem_chain_flt, klib sort order
     included) against the chains the compiled reference made of the same seeds (tests/golden/chain_golden.npz, 2 800 reads of a
