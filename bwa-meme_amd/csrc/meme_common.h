@@ -196,6 +196,14 @@ struct PrimaryWs {     // regs / reg_off / out / n_pri / mapq / status: the host
     bool log_ready = false;
 };
 
+struct FinishWs {      // regs / reg_off / out / reg_off_out / ums / status / counters: the host form's staging; stage: the records a read keeps, at the read's input offsets, before the
+                       // pack; cnt: records kept per read; live / first: live records of a read and the first of them; list: the wavefront tier's reads; cols_l / cols_c: the
+                       // columns of reads too large for LDS; contigs: ContigTab, h_contigs what it was staged from (restaged only when it changes)
+    DevBuf regs, reg_off, out, reg_off_out, ums, status, counters, stage, cnt, live, first, list, cols_l, cols_c, contigs;
+    HostBuf h_regs, h_reg_off, h_ums, h_status; Events<2> ev;
+    std::vector<unsigned char> h_contigs; std::vector<meme_contig> last_contigs; i64 last_l_pac = -1;
+};
+
 struct SideStreams {   // beside ctx->stream: the routed chaining tiers, the early overflow tier of seeding (meme_side_stream creates stream i with its event)
     Stream st[3];
     Events<3> done;    // done[i]: what was launched on st[i] has finished
@@ -212,7 +220,7 @@ struct meme_ctx {
     // workspaces (scan_tmp: tiles of the prefix sums, meme_scan_exclusive and the seeding gather)
     ResidentBatch batch;
     DevBuf scan_tmp;
-    ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam; PrimaryWs primary; SeedWs seed;
+    ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam; PrimaryWs primary; FinishWs finish; SeedWs seed;
     // Streams.  Order of destruction: meme_ctx_destroy synchronises every stream of the ctx; then the members go in reverse order of declaration, so the streams
     // and their fork / join events -- these two and, last member of the last workspace, the seeding stage's -- are destroyed BEFORE any DevBuf / HostBuf above is
     // freed.  A new stream holder goes below the buffers too: here, or last in SeedWs.  (A stage's timing events go with the stage; they are idle by then.)
@@ -234,6 +242,8 @@ struct meme_ctx {
     i64 sam_max_batch = 0;             // > 0: meme_sam_format_batch_host refuses more record slots than this with MEME_E_CAPACITY (the caller then formats in pieces)
     i64 primary_split = 8;             // primary marking: reads with more records than this go to the wavefront-per-read tier (0: every non-empty read; at most 8, the lanes of the light tier's group)
     i64 primary_blocks = 0;            // > 0: cap on the workgroups of the primary-marking kernels (0 = none)
+    i64 finish_blocks = 0;             // > 0: cap on the workgroups of the record-finishing kernels (0 = none)
+    i64 finish_lds_recs = 0;           // > 0: reads handed over with more records than this are walked in HBM by the wavefront tier (0, and anything above it: 128)
     i64 ext_live_only = 0;             // 1: meme_extend_last_batch_host hands over the surviving records only (qe > qb: what src/bwamem.cpp:1680-1693 keeps)
     i64 ext_rounds = 1;                // with ext_live_only: rounds of one seed per read before everything still ahead is extended at once (0: the reference's batch, then compaction)
     i64 gcig_groups = 1;               // 1: CIGAR jobs with bands of at most 16 / 32 / 64 columns run 4 / 2 / 1 to a wavefront as one chunk per row (k_gcig_grp); 0: a wavefront each, 64-column chunks

@@ -141,6 +141,28 @@ def default_primary_opt(**kw):
     return o
 
 
+class FinishOpt(C.Structure):       # meme_finish_opt
+    _fields_ = [(n, C.c_int32) for n in ("a", "b", "o_del", "e_del", "o_ins", "e_ins", "w", "max_chain_gap")] + [("mask_level_redun", C.c_float), ("pad", C.c_int32)]
+
+
+class FinishHost(C.Structure):      # meme_finish_host_result
+    _fields_ = [("nreads", C.c_int64), ("total_regs", C.c_int64), ("regs", C.c_void_p), ("reg_off", C.c_void_p), ("use_mate_sort", C.c_void_p), ("status", C.c_void_p),
+                ("n_wave", C.c_int64), ("n_patch_jobs", C.c_int64), ("n_patched", C.c_int64), ("kernel_ms", C.c_float)]
+
+
+class FinishDeviceOut(C.Structure):     # meme_finish_device_out
+    _fields_ = [(n, C.c_void_p) for n in ("d_regs_out", "d_reg_off_out", "d_use_mate_sort", "d_status", "d_counters")]
+
+
+def default_finish_opt(**kw):
+    # mem_opt_init (reference src/bwamem.cpp:126-162): a 1, b 4, gaps 6 + 1, w 100, max_chain_gap 10000, mask_level_redun 0.95
+    o = FinishOpt(1, 4, 6, 1, 6, 1, 100, 10000, 0.95, 0)
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
+
+
 class MateOpt(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("a", "b", "o_del", "e_del", "o_ins", "e_ins", "pen_unpaired", "max_matesw", "min_seed_len", "batch_reads")]
 
@@ -179,7 +201,7 @@ EXPORTS = ["meme_device_count", "meme_ctx_create", "meme_ctx_destroy", "meme_las
            "meme_index_pos5_bytes",
            "meme_index_attach", "meme_index_describe", "meme_index_share", "meme_index_replicate", "meme_host_alloc",
            "meme_host_free", "meme_stage_pack_text", "meme_stage_pos5_from_sa", "meme_stage_build_entries", "meme_stage_build_plcp",
-           "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_primary_batch_host", "meme_primary_batch_device", "meme_seed_batch_device",
+           "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_primary_batch_host", "meme_primary_batch_device", "meme_finish_batch_host", "meme_finish_batch_device", "meme_seed_batch_device",
            "meme_bsw_batch", "meme_bsw_batch_device", "meme_get_timings", "meme_set_tuning", "meme_debug_packed_reads"]
 
 _lib = None
@@ -521,6 +543,34 @@ class Context:
         out = PrimaryDeviceOut(d_regs_out_ptr, d_n_pri_ptr, d_mapq_ptr, d_status_ptr, d_n_heavy_ptr)
         _check(lib().meme_primary_batch_device(C.c_void_p(self.h), C.c_void_p(d_regs_ptr), C.c_void_p(d_reg_off_ptr), C.c_int64(nreads), C.c_int64(total_regs), C.c_int64(int(id_base)),
                                                C.byref(opt or default_primary_opt()), C.byref(out)))
+
+    def finish_batch_host(self, regs, reg_off, contigs, l_pac, opt=None):
+        """meme_finish_batch_host: record finishing (compaction to the live records, mem_sort_dedup_patch_mate_sort, is_alt) of the records regs (ALNREG) per read;
+        read r is read r of the batch the last seeding call left on the ctx; contigs: (offset, len, is_alt).  Returns dict(regs in the final order, reg_off,
+        use_mate_sort, status, n_wave, n_patch_jobs, n_patched, kernel_ms)."""
+        opt = opt or default_finish_opt()
+        assert regs.dtype == ALNREG and regs.flags.c_contiguous
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
+        n = reg_off.shape[0] - 1
+        arr = (Contig * len(contigs))(*[Contig(int(o), int(l), int(a)) for o, l, a in contigs])
+        res = FinishHost()
+        _check(lib().meme_finish_batch_host(C.c_void_p(self.h), _p(regs), _p(reg_off), C.c_int64(n), arr, C.c_int32(len(contigs)), C.c_int64(int(l_pac)), C.byref(opt), C.byref(res)))
+
+        def view(ptr, count, dtype):
+            if count == 0 or not ptr:
+                return np.zeros(0, dtype=dtype)
+            buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
+            return np.frombuffer(buf, dtype=dtype, count=count).copy()
+        return {"regs": view(res.regs, res.total_regs, ALNREG), "reg_off": view(res.reg_off, res.nreads + 1, np.int64), "use_mate_sort": view(res.use_mate_sort, res.nreads, np.uint8),
+                "status": view(res.status, res.nreads, np.uint8), "n_wave": int(res.n_wave), "n_patch_jobs": int(res.n_patch_jobs), "n_patched": int(res.n_patched),
+                "kernel_ms": float(res.kernel_ms)}
+
+    def finish_batch_device(self, d_regs_ptr, d_reg_off_ptr, nreads, total_regs, contigs, l_pac, opt, d_regs_out_ptr, d_reg_off_out_ptr, d_use_mate_sort_ptr, d_status_ptr, d_counters_ptr):
+        """meme_finish_batch_device: the same on device arrays the caller owns, asynchronous on the ctx's stream (sync() before reading the results)."""
+        arr = (Contig * len(contigs))(*[Contig(int(o), int(l), int(a)) for o, l, a in contigs])
+        out = FinishDeviceOut(d_regs_out_ptr, d_reg_off_out_ptr, d_use_mate_sort_ptr, d_status_ptr, d_counters_ptr)
+        _check(lib().meme_finish_batch_device(C.c_void_p(self.h), C.c_void_p(d_regs_ptr), C.c_void_p(d_reg_off_ptr), C.c_int64(nreads), C.c_int64(total_regs), arr, C.c_int32(len(contigs)),
+                                              C.c_int64(int(l_pac)), C.byref(opt or default_finish_opt()), C.byref(out)))
 
     def chain_batch_host(self, smems, smem_off, hits, hit_off, read_len, contigs, opt):
         """meme_chain_batch_host: chains of seeds the caller brings (numpy arrays laid out as seed_batch_host returns them)."""

@@ -13,6 +13,7 @@
  *                                       host consumer mem_chain_Learned(), src/bwamem.cpp:1122-1204)
  *   meme_chain_last_batch_host      <- mem_chain_Learned() + mem_chain_flt()          src/bwamem.cpp:1122-1204, 599-717
  *   meme_extend_last_batch_host     <- mem_chain2aln_across_reads_V2()              src/bwamem.cpp:2573-3497 (behind the chaining stage)
+ *   meme_finish_batch_host          <- the tail of mem_kernel2_core(): mem_sort_dedup_patch_mate_sort(), is_alt   src/bwamem.cpp:1681-1719, 312-383
  *   meme_global_batch_host          <- ksw_global2() under bwa_gen_cigar2()         src/ksw.cpp:560-670, src/bwa.cpp:274-362
  *   meme_gen_cigar_batch_host       <- bwa_gen_cigar2() whole: CIGAR + NM + MD       src/bwa.cpp:274-362
  *   meme_sam_format_batch_host      <- mem_aln2sam() for a chunk's plain records     src/bwamem.cpp:2174-2312
@@ -430,6 +431,44 @@ typedef struct { meme_alnreg* d_regs_out; int32_t* d_n_pri; uint8_t* d_mapq; uin
 int meme_primary_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs, const int64_t* d_reg_off, int64_t nreads, int64_t total_regs, int64_t id_base,
                               const meme_primary_opt* opt, const meme_primary_device_out* out);
 
+/* ---- record finishing: the tail of mem_kernel2_core ----------------------------------------------------------------------------------------
+ * What mem_kernel2_core does behind the extension (reference src/bwamem.cpp:1681-1719) with the alignment records of every read of a batch: the
+ * compaction to the live records (qe > qb), mem_sort_dedup_patch_mate_sort (:312-383: the order by end, the exclusion of redundant hits, mem_patch_reg
+ * :194-244 with the score of bwa_gen_cigar2's alignment, the merge, the useMateSort scan, the order by score and the exclusion of identical hits) and
+ * the is_alt flag.  regs[reg_off[r] .. reg_off[r+1]) is what meme_extend_last_batch_host hands over for read r: one record per chained seed with the
+ * purged ones marked, or the live ones only.  Read r of the call is read r of the batch the last seeding call left on the ctx (a patch aligns a span of
+ * its bases against the index's text): MEME_E_STATE without such a batch or without an index, MEME_E_ARG when nreads exceeds it.  The records that are
+ * left come back per read in the reference's final order with compact offsets; rb, re, qb, qe, score, truesc, sub, csub, seedcov, w and n_comp:30 /
+ * is_alt:2 as the function leaves them (a lone record keeps its n_comp; rid < 0 or beyond n_contigs never sets is_alt), every other field (frac_rep,
+ * hash, c, flg ...) bit for bit; use_mate_sort[r] = what the function leaves in *useMateSort (initialised true).
+ * status[r] = 1: a patch of read r would call bwa_gen_cigar2 on a target that bridges the strands, leaves the text or is empty -- the reference returns
+ * from there without writing the score and mem_patch_reg reads it uninitialised --, or on an alignment beyond the stage's bounds (a target span of more
+ * than 65536 bases, a query span outside the read); the read's records are then unspecified and the call succeeds.  status[r] = 2 (device form only):
+ * reg_off[r], reg_off[r+1] are no span inside [0, total_regs]; the read is skipped and keeps no record.
+ * opt: mem_opt_t fields of the same names; w >= 0, e_del >= 1 and e_ins >= 1 (the band of the alignment divides by them), else MEME_E_ARG.
+ * l_pac must be the index's.  Reads with at most one live record are copied a lane each; every other read is taken by one wavefront from start to
+ * end (n_wave of them), which aligns the patches itself (n_patch_jobs alignments asked for, n_patched merges).
+ * Host form: results in pinned memory of the ctx until its next call of this function. */
+typedef struct { int32_t a, b, o_del, e_del, o_ins, e_ins, w, max_chain_gap; float mask_level_redun; int32_t pad; } meme_finish_opt;
+typedef struct {
+    int64_t nreads, total_regs;            /* records left */
+    const meme_alnreg* regs;               /* final order per read */
+    const int64_t* reg_off;                /* nreads + 1, compact */
+    const uint8_t* use_mate_sort;          /* nreads: what the function leaves in *useMateSort (initialised true) */
+    const uint8_t* status;                 /* nreads */
+    int64_t n_wave, n_patch_jobs, n_patched;   /* reads the wavefront tier took; score alignments run; merges */
+    float kernel_ms;                       /* HIP events around the stage's kernels */
+} meme_finish_host_result;
+int meme_finish_batch_host(meme_ctx* ctx, const meme_alnreg* regs, const int64_t* reg_off /* nreads + 1, from 0 */, int64_t nreads,
+                           const meme_contig* contigs, int32_t n_contigs, int64_t l_pac, const meme_finish_opt* opt, meme_finish_host_result* out);
+/* The same on device arrays the caller owns, asynchronous on the ctx's stream: nothing is copied and the host does not wait.  d_regs_out: room for
+ * total_regs records (16-byte aligned, not d_regs); d_reg_off_out: nreads + 1; d_use_mate_sort, d_status: nreads; d_counters: 8 words, [0] n_wave,
+ * [1] n_patch_jobs, [2] n_patched.  d_regs_out and d_reg_off_out can be handed to meme_primary_batch_device as they are, with this call's total_regs as
+ * the bound of the record array. */
+typedef struct { meme_alnreg* d_regs_out; int64_t* d_reg_off_out; uint8_t* d_use_mate_sort; uint8_t* d_status; uint64_t* d_counters; } meme_finish_device_out;
+int meme_finish_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs, const int64_t* d_reg_off, int64_t nreads, int64_t total_regs,
+                             const meme_contig* contigs, int32_t n_contigs, int64_t l_pac, const meme_finish_opt* opt, const meme_finish_device_out* out);
+
 /* ---- measurement ---------------------------------------------------------------------------------
  * HIP-event timings of the kernels of the last *_device call, measured on the ctx's stream.          */
 typedef struct {
@@ -448,7 +487,7 @@ typedef struct {
     int64_t gcig_class_jobs[6];   /* the last CIGAR call's jobs by kernel: 16-lane groups, 32-lane groups, a wavefront each in 64-column chunks, the gap-free shortcut, 64-lane "groups"; the last entry is always 0 (the two-columns-per-lane kernel it counted was removed) */
 } meme_timings;
 int meme_get_timings(meme_ctx* ctx, meme_timings* out);
-int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value);   /* "group_lanes", "seed_blocks_per_cu", "seed_blocks", "smem_cap", "bsw_blocks", "bsw_lane_min_pairs", "chain_wave_tiers", "chain_lane_hits", "chain_light_hits", "seed_defer", "ext_live_only" (1: meme_extend_last_batch_host hands over only the records mem_kernel2_core keeps, src/bwamem.cpp:1680-1693 -- qe > qb, in order -- instead of one per chained seed with the purged ones marked; the stage then also runs in rounds -- "ext_rounds" (default 1; 0: off): a read's seeds are taken in extension order, tested against the read's surviving alignments first and extended only if they survive, one seed per read and round, after that many rounds everything still ahead at once: the same surviving records, without the banded SW of seeds the purge drops), "gcig_groups" (1, default: CIGAR jobs whose band has at most 16 / 32 / 64 columns run 4 / 2 / 1 to a wavefront with one chunk per row; 0: one wavefront per job in 64-column chunks; any other value: MEME_E_ARG), "gcig_zcap" (>= 0: bytes of LDS a CIGAR job keeps for its backtrack matrix or the window it is walked back through; default: chosen per call, 8192 where a typical matrix of the batch fits, else 2048; results do not depend on it), "ext_census" (1: meme_extend_last_batch_host also counts the extension jobs whose query is a prefix of its target), "max_batch" (> 0: meme_extend_last_batch_host / meme_global_batch_host refuse larger batches with MEME_E_CAPACITY), "ext_slab_jobs" (default 8 Mi, at least 1: the extension stage poses and aligns its jobs in slabs of whole reads with at most this many jobs per side, and at least one read, each -- a bound, and how the tests reach the multi-slab path; same records), "ext_split" (default 1: the extension stage's kernels that walk a read's chains run eight lanes per read for reads with at most 8 chained seeds and a wavefront per read for the others; 0: a wavefront per read throughout; same records), "bsw_circ" (default 1: the lane-per-pair banded-SW kernel keeps the columns of queries longer than its band in a ring of 2w + 2 columns -- same results, more wavefronts per CU; 0: one LDS word per query column as before), "sam_max_batch" (> 0: meme_sam_format_batch_host refuses more record slots than this with MEME_E_CAPACITY; the caller formats in pieces), "helper_blocks" (> 0: at most this many workgroups in the read packer, the offsets scan and the hit gather of a seeding call, as "seed_blocks" does for the search kernel -- how the tests drive their loops round with small batches; 0, default: no cap; same results), "primary_split" (default 8, its maximum: meme_primary_batch_host / _device run reads with at most this many records eight lanes to a read with the records in registers, reads with more a wavefront each with the records in HBM; 0 sends every non-empty read to the wavefront tier; larger values count as 8; same results), "primary_blocks" (> 0: at most this many workgroups in each kernel of that stage, so that a small batch goes round their grid-stride loops; 0, default: no cap; same results) */
+int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value);   /* "group_lanes", "seed_blocks_per_cu", "seed_blocks", "smem_cap", "bsw_blocks", "bsw_lane_min_pairs", "chain_wave_tiers", "chain_lane_hits", "chain_light_hits", "seed_defer", "ext_live_only" (1: meme_extend_last_batch_host hands over only the records mem_kernel2_core keeps, src/bwamem.cpp:1680-1693 -- qe > qb, in order -- instead of one per chained seed with the purged ones marked; the stage then also runs in rounds -- "ext_rounds" (default 1; 0: off): a read's seeds are taken in extension order, tested against the read's surviving alignments first and extended only if they survive, one seed per read and round, after that many rounds everything still ahead at once: the same surviving records, without the banded SW of seeds the purge drops), "gcig_groups" (1, default: CIGAR jobs whose band has at most 16 / 32 / 64 columns run 4 / 2 / 1 to a wavefront with one chunk per row; 0: one wavefront per job in 64-column chunks; any other value: MEME_E_ARG), "gcig_zcap" (>= 0: bytes of LDS a CIGAR job keeps for its backtrack matrix or the window it is walked back through; default: chosen per call, 8192 where a typical matrix of the batch fits, else 2048; results do not depend on it), "ext_census" (1: meme_extend_last_batch_host also counts the extension jobs whose query is a prefix of its target), "max_batch" (> 0: meme_extend_last_batch_host / meme_global_batch_host refuse larger batches with MEME_E_CAPACITY), "ext_slab_jobs" (default 8 Mi, at least 1: the extension stage poses and aligns its jobs in slabs of whole reads with at most this many jobs per side, and at least one read, each -- a bound, and how the tests reach the multi-slab path; same records), "ext_split" (default 1: the extension stage's kernels that walk a read's chains run eight lanes per read for reads with at most 8 chained seeds and a wavefront per read for the others; 0: a wavefront per read throughout; same records), "bsw_circ" (default 1: the lane-per-pair banded-SW kernel keeps the columns of queries longer than its band in a ring of 2w + 2 columns -- same results, more wavefronts per CU; 0: one LDS word per query column as before), "sam_max_batch" (> 0: meme_sam_format_batch_host refuses more record slots than this with MEME_E_CAPACITY; the caller formats in pieces), "helper_blocks" (> 0: at most this many workgroups in the read packer, the offsets scan and the hit gather of a seeding call, as "seed_blocks" does for the search kernel -- how the tests drive their loops round with small batches; 0, default: no cap; same results), "primary_split" (default 8, its maximum: meme_primary_batch_host / _device run reads with at most this many records eight lanes to a read with the records in registers, reads with more a wavefront each with the records in HBM; 0 sends every non-empty read to the wavefront tier; larger values count as 8; same results), "primary_blocks" (> 0: at most this many workgroups in each kernel of that stage, so that a small batch goes round their grid-stride loops; 0, default: no cap; same results), "finish_blocks" (> 0: the same cap for the kernels of meme_finish_batch_host / _device; 0, default: no cap; same results), "finish_lds_recs" (> 0: reads handed over with more records than this are walked by the wavefront tier of that stage in a workspace in HBM instead of in LDS; 0, default, and anything above it: 128; same results) */
 
 /* Debug: the packed image of the last seeded batch (what the search kernels read), copied to the host.  Per read `stride` 64-bit
  * words: fw[W] rc[W] nfw[MW] nrc[MW] len | hasN << 31 (2 bits per base, first base in the top bits, N packed as A; mask bit j of word m =
