@@ -16,11 +16,11 @@
 // every loop is bounded by a record count, a sequence length or a band known when it starts, list lengths are read once, and every barrier, DPP and readlane
 // stands in control flow that is the same on all lanes of its workgroup.
 #include <limits.h>
-#include <stddef.h>
 #include <string.h>
 #include <string>
 
 #include "meme_common.h"
+#include "meme_alnreg_words.h"
 #include "meme_finish_rules.h"
 
 #pragma clang fp contract(off)
@@ -44,37 +44,10 @@ struct FinArgs {
     meme_alnreg* out; const i64* off_out;
 };
 
-__device__ __forceinline__ bool fin_span(const FinArgs& A, i64 r, i64* base, int* n) {      // (pri_span of the primary stage)
-    const i64 s = A.reg_off[r], e = A.reg_off[r + 1];
-    const bool ok = s >= 0 && e >= s && e <= A.total_regs && e - s <= INT_MAX;
-    *base = ok ? s : 0;
-    *n = ok ? (int)(e - s) : 0;
-    return ok;
-}
-
-// A record in registers: seven 16-byte words (the record arrays are 16-byte aligned), the fields the stage writes by position.
-struct FinRec {
-    uint4 q0, q1, q2, q3, q4, q5, q6;
-    __device__ __forceinline__ int rid() const { return (int)q1.z; }
-    __device__ __forceinline__ int word() const { return (int)q5.y; }                            // n_comp:30, is_alt:2
-    __device__ __forceinline__ void set_word(int v) { q5.y = (uint32_t)v; }
-    __device__ __forceinline__ void set_span(i64 rb, i64 re, int qb, int qe) {
-        q0.x = (uint32_t)(u64)rb; q0.y = (uint32_t)((u64)rb >> 32); q0.z = (uint32_t)(u64)re; q0.w = (uint32_t)((u64)re >> 32); q1.x = (uint32_t)qb; q1.y = (uint32_t)qe;
-    }
-    __device__ __forceinline__ void set_scores(int score, int truesc, int sub, int csub, int w, int seedcov) {
-        q2.z = (uint32_t)score; q2.w = (uint32_t)truesc; q3.x = (uint32_t)sub; q3.z = (uint32_t)csub; q4.x = (uint32_t)w; q4.y = (uint32_t)seedcov;
-    }
-};
-static_assert(sizeof(meme_alnreg) == 112 && offsetof(meme_alnreg, re) == 8 && offsetof(meme_alnreg, qb) == 16 && offsetof(meme_alnreg, qe) == 20 && offsetof(meme_alnreg, rid) == 24 &&
-              offsetof(meme_alnreg, score) == 40 && offsetof(meme_alnreg, truesc) == 44 && offsetof(meme_alnreg, sub) == 48 && offsetof(meme_alnreg, csub) == 56 && offsetof(meme_alnreg, w) == 64 &&
-              offsetof(meme_alnreg, seedcov) == 68 && offsetof(meme_alnreg, n_comp_is_alt) == 84, "FinRec names meme_alnreg's fields by position");
-__device__ __forceinline__ FinRec fin_load(const meme_alnreg* p) { const uint4* s = (const uint4*)p; FinRec r; r.q0 = s[0]; r.q1 = s[1]; r.q2 = s[2]; r.q3 = s[3]; r.q4 = s[4]; r.q5 = s[5]; r.q6 = s[6]; return r; }
-__device__ __forceinline__ void fin_store(meme_alnreg* p, const FinRec& r) { uint4* d = (uint4*)p; d[0] = r.q0; d[1] = r.q1; d[2] = r.q2; d[3] = r.q3; d[4] = r.q4; d[5] = r.q5; d[6] = r.q6; }
-
 __global__ void __launch_bounds__(256) k_finish_route(FinArgs A) {
     for (i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x; r < A.nreads; r += (i64)gridDim.x * blockDim.x) {
         i64 base; int n;
-        A.status[r] = fin_span(A, r, &base, &n) ? 0 : 2;
+        A.status[r] = reg_span(A.reg_off, r, A.total_regs, &base, &n) ? 0 : 2;
         int live = 0, first = 0;
         for (int k = 0; k < n; ++k) {
             const meme_alnreg& R = A.in[base + k];
@@ -90,10 +63,10 @@ __global__ void __launch_bounds__(256) k_finish_light(FinArgs A) {
     for (i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x; r < A.nreads; r += (i64)gridDim.x * blockDim.x) {
         if (A.live[r] != 1) continue;
         i64 base; int n;
-        fin_span(A, r, &base, &n);
-        FinRec R = fin_load(A.in + base + A.first[r]);
+        reg_span(A.reg_off, r, A.total_regs, &base, &n);
+        RegWords R = reg_load(A.in + base + A.first[r]);
         R.set_word(fin_word(R.word(), R.word(), R.rid(), A.alt, A.n_contigs));
-        fin_store(A.stage + base, R);
+        reg_store(A.stage + base, R);
         A.cnt[r] = 1;
     }
 }
@@ -184,7 +157,7 @@ __global__ void __launch_bounds__(64) k_finish_wave(FinArgs A) {
     for (i64 hi = blockIdx.x; hi < n_wave; hi += gridDim.x) {                       // (uniform over the workgroup, and so is everything below)
         const i64 r = A.list[hi];
         i64 base; int n_in;
-        fin_span(A, r, &base, &n_in);
+        reg_span(A.reg_off, r, A.total_regs, &base, &n_in);
         n_in = __builtin_amdgcn_readfirstlane(n_in);
         const bool in_lds = n_in <= A.lds_recs;
         const FinColsWave s = {in_lds ? lds_c : A.cols_c + base * FIN_INTS, in_lds ? lds_l : A.cols_l + base * FIN_LONGS, in_lds ? FIN_LDS_RECS : n_in};
@@ -209,11 +182,11 @@ __global__ void __launch_bounds__(64) k_finish_wave(FinArgs A) {
         for (int k = lane; k < m; k += 64) {
             const int x = s.c[(size_t)FIN_ORD * s.cap + k];
             const auto ci = [&](int f) -> int { return s.c[(size_t)f * s.cap + x]; };
-            FinRec R = fin_load(in + x);
+            RegWords R = reg_load(in + x);
             R.set_span(s.l[(size_t)FIN_RB * s.cap + x], s.l[(size_t)FIN_RE * s.cap + x], ci(FIN_QB), ci(FIN_QE));
             R.set_scores(ci(FIN_SCORE), ci(FIN_TRUESC), ci(FIN_SUB), ci(FIN_CSUB), ci(FIN_W), ci(FIN_SEEDCOV));
             R.set_word(fin_word(R.word(), ci(FIN_NCOMP), R.rid(), A.alt, A.n_contigs));
-            fin_store(A.stage + base + k, R);
+            reg_store(A.stage + base + k, R);
         }
         if (lane == 0) {
             A.cnt[r] = m; A.ums[r] = (uint8_t)res.use_mate_sort;
@@ -232,7 +205,7 @@ __global__ void __launch_bounds__(256) k_finish_pack(FinArgs A) {
         const i64 m = A.cnt[r];
         if (m <= 0 || p >= 7) continue;
         i64 base; int n;
-        fin_span(A, r, &base, &n);
+        reg_span(A.reg_off, r, A.total_regs, &base, &n);
         if (A.off_out[r] < 0 || A.off_out[r] + m > A.total_regs) continue;       // (spans of the device form that overlap: more records kept than the output holds)
         const uint4* src = reinterpret_cast<const uint4*>(A.stage + base);
         uint4* dst = reinterpret_cast<uint4*>(A.out + A.off_out[r]);
@@ -306,14 +279,9 @@ int finish_launch(meme_ctx* ctx, const meme_alnreg* d_regs, const i64* d_reg_off
 extern "C" int meme_finish_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs, const int64_t* d_reg_off, int64_t nreads, int64_t total_regs, const meme_contig* contigs,
                                         int32_t n_contigs, int64_t l_pac, const meme_finish_opt* opt, const meme_finish_device_out* out) {
     static const char* const who = "meme_finish_batch_device";
-    if (!ctx || !opt || !out || nreads < 0 || total_regs < 0 || !out->d_counters || !out->d_reg_off_out || (nreads > 0 && (!d_reg_off || !out->d_use_mate_sort || !out->d_status)) ||
-        (total_regs > 0 && (!d_regs || !out->d_regs_out || d_regs == out->d_regs_out))) {
-        meme_set_error("%s: null argument (or the output records are the input records)", who);
-        return MEME_E_ARG;
-    }
-    if (((uintptr_t)d_regs | (uintptr_t)out->d_regs_out) & 15) { meme_set_error("%s: the record arrays must be 16-byte aligned", who); return MEME_E_ARG; }
-    int rc = finish_check_opt(who, opt);
-    if (rc) return rc;
+    const bool rest = ctx && opt && out && out->d_counters && out->d_reg_off_out && (nreads <= 0 || (out->d_use_mate_sort && out->d_status));
+    int rc;
+    if ((rc = reg_check_device(who, rest, d_regs, out ? out->d_regs_out : nullptr, d_reg_off, nreads, total_regs)) || (rc = finish_check_opt(who, opt))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     ContigTab ct(nullptr, 0, true);
     if ((rc = finish_prepare(ctx, who, nreads, contigs, n_contigs, l_pac, &ct))) return rc;
@@ -340,11 +308,8 @@ extern "C" int meme_finish_batch_host(meme_ctx* ctx, const meme_alnreg* regs, co
     out->reg_off = (const int64_t*)F.h_reg_off.p;
     ((i64*)F.h_reg_off.p)[0] = 0;
     if (nreads == 0) return MEME_OK;
-    if (reg_off[0] != 0) { meme_set_error("%s: reg_off must start at 0", who); return MEME_E_ARG; }
-    for (i64 r = 0; r < nreads; ++r)
-        if (reg_off[r + 1] < reg_off[r] || reg_off[r + 1] - reg_off[r] > INT_MAX) { meme_set_error("%s: reg_off decreases (or spans more than 2^31 records) at read %lld", who, (long long)r); return MEME_E_ARG; }
+    if ((rc = reg_check_host(who, regs, reg_off, nreads))) return rc;
     const i64 total = reg_off[nreads];
-    if (total > 0 && !regs) { meme_set_error("%s: null argument", who); return MEME_E_ARG; }
     const size_t rbytes = (size_t)total * sizeof(meme_alnreg);
     if ((rc = meme_buf_reserve(ctx, F.regs, rbytes + 64)) || (rc = meme_buf_reserve(ctx, F.out, rbytes + 64)) || (rc = meme_buf_reserve(ctx, F.reg_off, (size_t)(nreads + 1) * 8)) ||
         (rc = meme_buf_reserve(ctx, F.reg_off_out, (size_t)(nreads + 1) * 8)) || (rc = meme_buf_reserve(ctx, F.ums, (size_t)nreads + 64)) || (rc = meme_buf_reserve(ctx, F.status, (size_t)nreads + 64)) ||

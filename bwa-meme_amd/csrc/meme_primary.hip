@@ -13,110 +13,44 @@
 //                    (what the walk touches of a read's first 256 records is kept in LDS meanwhile)
 // k_primary_route lists the heavy reads.  Every loop is bounded by the read's record count; no kernel waits for another workgroup.
 //
+// Everything that decides a result is meme_primary_rules.h (the orders, the overlap test, the score distance, what a hit does, alt_sc, the remap, the
+// primary5 choice, the quality); this file holds where the records live and who runs what.  The record in registers and a read's span of the record
+// array are meme_alnreg_words.h, shared with the record-finishing stage.
+//
 // Arithmetic: the overlap test is float as in the reference (one multiply, nothing to contract); the quality is IEEE double with contraction off, its
 // logarithms looked up in a table the host's libm filled (the device's log is not glibc's; the arguments are small integers).
-#include <limits.h>
-#include <stddef.h>
 #include <math.h>
 #include <string.h>
 
 #include "meme_common.h"
+#include "meme_alnreg_words.h"
+#include "meme_primary_rules.h"
 
 #pragma clang fp contract(off)
 
 constexpr int PRI_G = 8;             // lanes per read in the light tier = the most records it takes
-constexpr int PRI_LOG = 65536;       // entries of the table of logarithms
 
 struct PriArgs {
     const meme_alnreg* in; const i64* reg_off; i64 nreads, total_regs; u64 id_base;
-    meme_primary_opt o; int tmp, split;                       // tmp: the score distance up to which a secondary hit counts in sub_n (:1977-1979)
+    meme_primary_opt o; int tmp, split;                       // tmp: pri_score_distance(o)
     meme_alnreg *out, *sorted; int* rank;
     int* n_pri; uint8_t *mapq, *status;
     i64* list; unsigned long long* n_heavy;
     const double* logtab;
 };
 
-// read r's records: [*base, *base + *n); a pair of offsets that is no span inside the record array gives no records (false)
-__device__ __forceinline__ bool pri_span(const PriArgs& A, i64 r, i64* base, int* n) {
-    const i64 s = A.reg_off[r], e = A.reg_off[r + 1];
-    const bool ok = s >= 0 && e >= s && e <= A.total_regs && e - s <= INT_MAX;
-    *base = ok ? s : 0;
-    *n = ok ? (int)(e - s) : 0;
-    return ok;
+// the quality of a record in registers, its logarithms from the table
+__device__ __forceinline__ int pri_mapq_of(const PriArgs& A, const RegWords& R, bool* beyond) {
+    const PriQual Q = {R.score(), R.sub(), R.csub(), R.sub_n(), R.qb(), R.qe(), R.rb(), R.re(), R.frac_rep()};
+    const double* __restrict__ logtab = A.logtab;
+    return pri_mapq(Q, A.o, [&](int k) -> double { return logtab[k]; }, beyond);
 }
-__device__ __forceinline__ u64 pri_hash64(u64 key) {    // hash_64, reference src/utils.h:117
-    key += ~(key << 32); key ^= (key >> 22); key += ~(key << 13); key ^= (key >> 8); key += (key << 3); key ^= (key >> 15); key += ~(key << 27); key ^= (key >> 31);
-    return key;
-}
-__device__ __forceinline__ int pri_is_alt(int n_comp_is_alt) { return n_comp_is_alt >> 30; }     // int n_comp:30, is_alt:2
-// alnreg_hlt / alnreg_hlt2 (:174, :177): x before y
-__device__ __forceinline__ bool pri_hlt(int sx, int ax, u64 hx, int sy, int ay, u64 hy) { return sx > sy || (sx == sy && (ax < ay || (ax == ay && hx < hy))); }
-__device__ __forceinline__ bool pri_hlt2(int sx, int ax, u64 hx, int sy, int ay, u64 hy) { return ax < ay || (ax == ay && (sx > sy || (sx == sy && hx < hy))); }
-// significant overlap of two query spans (:1985-1989), the comparison in float
-__device__ __forceinline__ bool pri_overlap(int qbj, int qej, int qbi, int qei, float mask_level) {
-    const int b_max = qbj > qbi ? qbj : qbi, e_min = qej < qei ? qej : qei;
-    if (e_min <= b_max) return false;
-    const int min_l = qei - qbi < qej - qbj ? qei - qbi : qej - qbj;
-    return (float)(e_min - b_max) >= (float)min_l * mask_level;
-}
-// A record in registers: seven 16-byte words (a record is 112 bytes and 16-byte aligned: the arrays are), the fields the stage touches by name.
-struct PriRec {
-    uint4 q0, q1, q2, q3, q4, q5, q6;
-    __device__ __forceinline__ i64 rb() const { return (i64)((u64)q0.x | ((u64)q0.y << 32)); }
-    __device__ __forceinline__ i64 re() const { return (i64)((u64)q0.z | ((u64)q0.w << 32)); }
-    __device__ __forceinline__ int qb() const { return (int)q1.x; }
-    __device__ __forceinline__ int qe() const { return (int)q1.y; }
-    __device__ __forceinline__ int score() const { return (int)q2.z; }
-    __device__ __forceinline__ int sub() const { return (int)q3.x; }
-    __device__ __forceinline__ int csub() const { return (int)q3.z; }
-    __device__ __forceinline__ int sub_n() const { return (int)q3.w; }
-    __device__ __forceinline__ int secondary() const { return (int)q4.z; }
-    __device__ __forceinline__ int is_alt() const { return (int)q5.y >> 30; }                   // int n_comp:30, is_alt:2
-    __device__ __forceinline__ float frac_rep() const { return __uint_as_float(q5.z); }
-    __device__ __forceinline__ void set_marks(int sub, int alt_sc, int sub_n, int secondary, int secondary_all) { q3.x = (uint32_t)sub; q3.y = (uint32_t)alt_sc; q3.w = (uint32_t)sub_n; q4.z = (uint32_t)secondary; q4.w = (uint32_t)secondary_all; }
-    __device__ __forceinline__ void set_hash(u64 h) { q6.x = (uint32_t)h; q6.y = (uint32_t)(h >> 32); }
-};
-static_assert(sizeof(meme_alnreg) == 112 && offsetof(meme_alnreg, qb) == 16 && offsetof(meme_alnreg, score) == 40 && offsetof(meme_alnreg, sub) == 48 && offsetof(meme_alnreg, csub) == 56 &&
-              offsetof(meme_alnreg, sub_n) == 60 && offsetof(meme_alnreg, secondary) == 72 && offsetof(meme_alnreg, secondary_all) == 76 && offsetof(meme_alnreg, n_comp_is_alt) == 84 &&
-              offsetof(meme_alnreg, frac_rep) == 88 && offsetof(meme_alnreg, hash) == 96, "PriRec names meme_alnreg's fields by position");
-__device__ __forceinline__ PriRec pri_load(const meme_alnreg* p) { const uint4* s = (const uint4*)p; PriRec r; r.q0 = s[0]; r.q1 = s[1]; r.q2 = s[2]; r.q3 = s[3]; r.q4 = s[4]; r.q5 = s[5]; r.q6 = s[6]; return r; }
-__device__ __forceinline__ void pri_store(meme_alnreg* p, const PriRec& r) { uint4* d = (uint4*)p; d[0] = r.q0; d[1] = r.q1; d[2] = r.q2; d[3] = r.q3; d[4] = r.q4; d[5] = r.q5; d[6] = r.q6; }
-// mem_approx_mapq_se, the mapQ_coef_len > 0 branch; *beyond: a logarithm outside the table was asked for (the value returned then means nothing)
-__device__ __forceinline__ int pri_mapq(const meme_primary_opt& o, const double* __restrict__ logtab, const PriRec& R, bool* beyond) {
-    const int score = R.score(), sub_n = R.sub_n();
-    int sub = R.sub() ? R.sub() : o.min_seed_len * o.a;
-    sub = R.csub() > sub ? R.csub() : sub;
-    if (sub >= score) return 0;
-    const int l = (int)(R.qe() - R.qb() > R.re() - R.rb() ? R.qe() - R.qb() : R.re() - R.rb());
-    const double identity = 1. - (double)(l * o.a - score) / (o.a + o.b) / l;
-    int mapq;
-    if (score == 0) mapq = 0;
-    else {
-        double t = 1.;
-        if (!((float)l < o.mapQ_coef_len)) {
-            if (l < 0 || l >= PRI_LOG) { *beyond = true; return 0; }
-            t = o.mapQ_coef_fac / logtab[l];
-        }
-        t *= identity * identity;
-        mapq = (int)(6.02 * (score - sub) / o.a * t * t + .499);
-    }
-    if (sub_n > 0) {
-        if (sub_n >= PRI_LOG - 1) { *beyond = true; return 0; }
-        mapq -= (int)(4.343 * logtab[sub_n + 1] + .499);
-    }
-    if (mapq > 60) mapq = 60;
-    if (mapq < 0) mapq = 0;
-    return (int)(mapq * (1. - R.frac_rep()) + .499);
-}
-__device__ __forceinline__ uint8_t pri_byte(int q) { return (uint8_t)(q < 0 ? 0 : q > 255 ? 255 : q); }
-// mem_reorder_primary5's index update (:2093-2099) for the records behind the first
-__device__ __forceinline__ int pri_swapped(int s, int left_k) { return s == 0 ? left_k : s == left_k ? 0 : s; }
 
 // ---- routing --------------------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_primary_route(PriArgs A) {
     for (i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x; r < A.nreads; r += (i64)gridDim.x * blockDim.x) {
         i64 base; int n;
-        A.status[r] = pri_span(A, r, &base, &n) ? 0 : 2;
+        A.status[r] = reg_span(A.reg_off, r, A.total_regs, &base, &n) ? 0 : 2;
         A.n_pri[r] = 0;
         if (n > A.split) A.list[atomicAdd(A.n_heavy, 1ull)] = r;      // (at most nreads entries; their order does not matter)
     }
@@ -148,10 +82,7 @@ __device__ __forceinline__ void pri_core_group(PriLane& x, int p, int n, float m
         const unsigned m = pri_group_ballot(p < i && x.secondary < 0 && pri_overlap(x.qb, x.qe, qbi, qei, mask_level));
         if (m) {
             const int j = __ffs(m) - 1;
-            if (p == j) {
-                if (x.sub == 0) x.sub = sci;
-                if (x.score - sci <= tmp && (x.alt || !alti)) ++x.sub_n;
-            }
+            if (p == j) { const PriHit h = pri_hit(x.sub, x.sub_n, x.score, x.alt, sci, alti, tmp); x.sub = h.sub; x.sub_n = h.sub_n; }
             if (p == i) x.secondary = j;
         }
     }
@@ -162,7 +93,7 @@ __global__ void __launch_bounds__(256) k_primary_light(PriArgs A) {
     const i64 groups = (i64)gridDim.x * (256 / PRI_G);
     for (i64 r = (i64)blockIdx.x * (256 / PRI_G) + threadIdx.x / PRI_G; r < A.nreads; r += groups) {     // (control flow below is uniform within a group: its lanes stay together)
         i64 base; int n;
-        pri_span(A, r, &base, &n);
+        reg_span(A.reg_off, r, A.total_regs, &base, &n);
         if (n == 0 || n > A.split) continue;
         const bool live = p < n;
         PriLane x;
@@ -188,7 +119,7 @@ __global__ void __launch_bounds__(256) k_primary_light(PriArgs A) {
         {
             const int s = x.secondary < 0 ? 0 : x.secondary;
             const int s_alt = __shfl(x.alt, s, PRI_G), s_score = __shfl(x.score, s, PRI_G);
-            if (live && !x.alt && x.secondary >= 0 && s_alt) x.alt_sc = s_score;
+            if (live) x.alt_sc = pri_alt_sc(x.alt_sc, x.alt, x.secondary, s_alt, s_score);
         }
         const int n_pri = __popc(pri_group_ballot(live && !x.alt));
         if (n_pri < n) {
@@ -204,38 +135,37 @@ __global__ void __launch_bounds__(256) k_primary_light(PriArgs A) {
                 if (!live) rank2 = p;
             }
             const int mapped = __shfl(rank2, x.secondary < 0 || x.secondary >= PRI_G ? 0 : x.secondary, PRI_G);
-            if (live) {
-                if (x.secondary >= 0) { x.secondary_all = mapped; if (x.alt) x.secondary = INT_MAX; }
-                else x.secondary_all = -1;
+            if (live) {                                                  // (rank2 is the position the record is about to take)
+                const PriMarks m = pri_remap(x.sub, x.secondary, x.alt, rank2, n_pri, mapped);
+                x.sub = m.sub; x.secondary = m.secondary; x.secondary_all = m.secondary_all;
             }
             if (n_pri > 0) {
                 x = pri_take(x, pri_inverse(rank2, p));
-                if (p < n_pri) { x.sub = 0; x.secondary = -1; }
                 pri_core_group(x, p, n_pri, A.o.mask_level, A.tmp);
             }
         } else x.secondary_all = x.secondary;
         if (A.o.primary5) {
-            const unsigned cand = pri_group_ballot(p < n && x.secondary < 0 && !x.alt && x.score >= A.o.T);
+            const unsigned cand = pri_group_ballot(p < n && pri_candidate(x.secondary, x.alt, x.score, A.o.T));
             if (__popc(cand) > 1) {
-                int left_st = INT_MAX, left_k = 0;
+                PriLeft left = pri_left_none();
 #pragma unroll
                 for (int j = 0; j < PRI_G; ++j) {
-                    const int qbj = __shfl(x.qb, j, PRI_G);
-                    if (((cand >> j) & 1u) && qbj < left_st) { left_st = qbj; left_k = j; }
+                    const PriLeft c = {__shfl(x.qb, j, PRI_G), j};
+                    if ((cand >> j) & 1u) left = pri_leftmost(left, c);
                 }
-                if (left_k != 0) {
-                    x = pri_take(x, pri_swapped(p, left_k));
-                    if (p >= 1) { x.secondary = pri_swapped(x.secondary, left_k); x.secondary_all = pri_swapped(x.secondary_all, left_k); }
+                if (left.k != 0) {
+                    x = pri_take(x, pri_swapped(p, left.k));
+                    if (p >= 1) { x.secondary = pri_swapped(x.secondary, left.k); x.secondary_all = pri_swapped(x.secondary_all, left.k); }
                 }
             }
         }
         if (live) {
-            PriRec R = pri_load(A.in + base + x.src);
+            RegWords R = reg_load(A.in + base + x.src);
             R.set_marks(x.sub, x.alt_sc, x.sub_n, x.secondary, x.secondary_all);
             R.set_hash(x.hash);
             bool beyond = false;
-            const int q = pri_mapq(A.o, A.logtab, R, &beyond);
-            pri_store(A.out + base + p, R);
+            const int q = pri_mapq_of(A, R, &beyond);
+            reg_store(A.out + base + p, R);
             A.mapq[base + p] = pri_byte(q);
             if (beyond) A.status[r] = 1;
             if (p == 0) A.n_pri[r] = n_pri;
@@ -283,10 +213,9 @@ __device__ __forceinline__ void pri_core_wave(PriWalk w, int n, float mask_level
             if (m) { found = c + __ffsll(m) - 1; break; }
         }
         if (found >= 0 && lane == 0) {
-            const int sci = w.get_score(i);
             int *sub = w.at_sub(found), *sub_n = w.at_sub_n(found);
-            if (*sub == 0) *sub = sci;
-            if (w.get_score(found) - sci <= tmp && (w.get_alt(found) || !w.get_alt(i))) ++*sub_n;
+            const PriHit h = pri_hit(*sub, *sub_n, w.get_score(found), w.get_alt(found), w.get_score(i), w.get_alt(i), tmp);
+            *sub = h.sub; *sub_n = h.sub_n;
             *w.at_secondary(i) = found;
         }
         __syncthreads();
@@ -335,7 +264,7 @@ __global__ void __launch_bounds__(64) k_primary_heavy(PriArgs A) {
     for (i64 hi = blockIdx.x; hi < n_heavy; hi += gridDim.x) {                       // (uniform over the workgroup, and so is every branch around a barrier below)
         const i64 r = A.list[hi];
         i64 base; int n;
-        pri_span(A, r, &base, &n);
+        reg_span(A.reg_off, r, A.total_regs, &base, &n);
         const meme_alnreg* in = A.in + base;
         meme_alnreg *t = A.sorted + base, *out = A.out + base;
         int* rk = A.rank + base;
@@ -344,10 +273,10 @@ __global__ void __launch_bounds__(64) k_primary_heavy(PriArgs A) {
         pri_ranks_wave(in, n, false, id, keys, rk);
         int pri = 0;
         for (int k = lane; k < n; k += 64) {
-            PriRec R = pri_load(in + k);
+            RegWords R = reg_load(in + k);
             R.set_marks(0, 0, R.sub_n(), -1, -1);
             R.set_hash(pri_hash64(id + (u64)k));
-            pri_store(t + rk[k], R);
+            reg_store(t + rk[k], R);
             pri += R.is_alt() == 0;
         }
         const int n_pri = pri_wave_sum(pri);
@@ -356,8 +285,9 @@ __global__ void __launch_bounds__(64) k_primary_heavy(PriArgs A) {
         pri_core_wave(walk, n, A.o.mask_level, A.tmp);
         for (int k = lane; k < n; k += 64) {
             const int s = t[k].secondary;
+            const meme_alnreg& parent = t[s < 0 ? 0 : s];
             t[k].secondary_all = k;
-            if (!pri_is_alt(t[k].n_comp_is_alt) && s >= 0 && pri_is_alt(t[s].n_comp_is_alt)) t[k].alt_sc = t[s].score;
+            t[k].alt_sc = pri_alt_sc(t[k].alt_sc, pri_is_alt(t[k].n_comp_is_alt), s, pri_is_alt(parent.n_comp_is_alt), parent.score);
         }
         __syncthreads();
         if (n_pri < n) {
@@ -367,31 +297,31 @@ __global__ void __launch_bounds__(64) k_primary_heavy(PriArgs A) {
                 __syncthreads();
             }
             for (int k = lane; k < n; k += 64) {
-                PriRec R = pri_load(t + k);
-                int sub = R.sub(), secondary = R.secondary(), secondary_all = -1;
-                if (secondary >= 0) { secondary_all = rk[secondary]; if (R.is_alt()) secondary = INT_MAX; }
+                RegWords R = reg_load(t + k);
                 const int d = rk[k];
-                if (n_pri > 0 && d < n_pri) { sub = 0; secondary = -1; }
-                R.set_marks(sub, (int)R.q3.y, R.sub_n(), secondary, secondary_all);
-                pri_store(out + d, R);
+                const PriMarks m = pri_remap(R.sub(), R.secondary(), R.is_alt(), d, n_pri, rk[R.secondary() < 0 ? 0 : R.secondary()]);
+                R.set_marks(m.sub, R.alt_sc(), R.sub_n(), m.secondary, m.secondary_all);
+                reg_store(out + d, R);
             }
             __syncthreads();
             walk.a = out;
             if (n_pri > 0) pri_core_wave(walk, n_pri, A.o.mask_level, A.tmp);
         } else {
-            for (int k = lane; k < n; k += 64) { PriRec R = pri_load(t + k); R.q4.w = R.q4.z; pri_store(out + k, R); }      // secondary_all = secondary
+            for (int k = lane; k < n; k += 64) { RegWords R = reg_load(t + k); R.set_secondary_all(R.secondary()); reg_store(out + k, R); }
             __syncthreads();
         }
         if (A.o.primary5) {
-            int cnt = 0, left_st = INT_MAX, left_k = INT_MAX;
+            int cnt = 0;
+            PriLeft left = pri_left_none();
             for (int k = lane; k < n; k += 64)
-                if (out[k].secondary < 0 && !pri_is_alt(out[k].n_comp_is_alt) && out[k].score >= A.o.T) { ++cnt; if (out[k].qb < left_st) { left_st = out[k].qb; left_k = k; } }
+                if (pri_candidate(out[k].secondary, pri_is_alt(out[k].n_comp_is_alt), out[k].score, A.o.T)) { ++cnt; const PriLeft c = {out[k].qb, k}; left = pri_leftmost(left, c); }
             cnt = pri_wave_sum(cnt);
 #pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {                                       // the smallest qb, the earliest record among equals
-                const int os = __shfl_xor(left_st, d), ok = __shfl_xor(left_k, d);
-                if (os < left_st || (os == left_st && ok < left_k)) { left_st = os; left_k = ok; }
+            for (int d = 32; d >= 1; d >>= 1) {                                       // the leftmost over the lanes
+                const PriLeft other = {__shfl_xor(left.qb, d), __shfl_xor(left.k, d)};
+                left = pri_leftmost(left, other);
             }
+            const int left_k = left.k;
             if (cnt > 1 && left_k != 0 && left_k < n) {
                 if (lane < (int)(sizeof(meme_alnreg) / 4)) {                          // swap the two records a 32-bit word per lane
                     uint32_t *x = (uint32_t*)&out[0] + lane, *y = (uint32_t*)&out[left_k] + lane;
@@ -403,7 +333,7 @@ __global__ void __launch_bounds__(64) k_primary_heavy(PriArgs A) {
             }
         }
         bool beyond = false;
-        for (int k = lane; k < n; k += 64) A.mapq[base + k] = pri_byte(pri_mapq(A.o, A.logtab, pri_load(out + k), &beyond));
+        for (int k = lane; k < n; k += 64) A.mapq[base + k] = pri_byte(pri_mapq_of(A, reg_load(out + k), &beyond));
         if (beyond) A.status[r] = 1;
         if (lane == 0) A.n_pri[r] = n_pri;
         __syncthreads();
@@ -434,9 +364,7 @@ static int primary_launch(meme_ctx* ctx, const meme_alnreg* d_regs, const i64* d
     HIP_TRY(P.ev.ensure());
     PriArgs A;
     A.in = d_regs; A.reg_off = d_reg_off; A.nreads = nreads; A.total_regs = total_regs; A.id_base = (u64)id_base; A.o = *opt;
-    A.tmp = opt->a + opt->b;
-    A.tmp = opt->o_del + opt->e_del > A.tmp ? opt->o_del + opt->e_del : A.tmp;
-    A.tmp = opt->o_ins + opt->e_ins > A.tmp ? opt->o_ins + opt->e_ins : A.tmp;
+    A.tmp = pri_score_distance(*opt);
     A.split = (int)(ctx->primary_split < 0 ? 0 : ctx->primary_split > PRI_G ? PRI_G : ctx->primary_split);
     A.out = o->d_regs_out; A.sorted = (meme_alnreg*)P.sorted.p; A.rank = (int*)P.rank.p; A.n_pri = o->d_n_pri; A.mapq = o->d_mapq; A.status = o->d_status;
     A.list = (i64*)P.list.p; A.n_heavy = (unsigned long long*)o->d_n_heavy; A.logtab = (const double*)P.logtab.p;
@@ -454,14 +382,9 @@ static int primary_launch(meme_ctx* ctx, const meme_alnreg* d_regs, const i64* d
 extern "C" int meme_primary_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs, const int64_t* d_reg_off, int64_t nreads, int64_t total_regs, int64_t id_base,
                                          const meme_primary_opt* opt, const meme_primary_device_out* out) {
     static const char* const who = "meme_primary_batch_device";
-    if (!ctx || !opt || !out || nreads < 0 || total_regs < 0 || (nreads > 0 && (!d_reg_off || !out->d_n_pri || !out->d_status)) || !out->d_n_heavy ||
-        (total_regs > 0 && (!d_regs || !out->d_regs_out || !out->d_mapq)) || (total_regs > 0 && d_regs == out->d_regs_out)) {
-        meme_set_error("%s: null argument (or the output records are the input records)", who);
-        return MEME_E_ARG;
-    }
-    if (((uintptr_t)d_regs | (uintptr_t)out->d_regs_out) & 15) { meme_set_error("%s: the record arrays must be 16-byte aligned", who); return MEME_E_ARG; }
-    int rc = primary_check_opt(who, opt);
-    if (rc) return rc;
+    const bool rest = ctx && opt && out && out->d_n_heavy && (nreads <= 0 || (out->d_n_pri && out->d_status)) && (total_regs <= 0 || out->d_mapq);
+    int rc;
+    if ((rc = reg_check_device(who, rest, d_regs, out ? out->d_regs_out : nullptr, d_reg_off, nreads, total_regs)) || (rc = primary_check_opt(who, opt))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     if (nreads == 0) { HIP_TRY(hipMemsetAsync(out->d_n_heavy, 0, 8, ctx->stream)); return MEME_OK; }
     return primary_launch(ctx, d_regs, (const i64*)d_reg_off, nreads, total_regs, id_base, opt, out);
@@ -476,11 +399,8 @@ extern "C" int meme_primary_batch_host(meme_ctx* ctx, const meme_alnreg* regs, c
     HIP_TRY(hipSetDevice(ctx->device));
     memset(out, 0, sizeof(*out));
     if (nreads == 0) return MEME_OK;
-    if (reg_off[0] != 0) { meme_set_error("%s: reg_off must start at 0", who); return MEME_E_ARG; }
-    for (i64 r = 0; r < nreads; ++r)
-        if (reg_off[r + 1] < reg_off[r] || reg_off[r + 1] - reg_off[r] > INT_MAX) { meme_set_error("%s: reg_off decreases (or spans more than 2^31 records) at read %lld", who, (long long)r); return MEME_E_ARG; }
+    if ((rc = reg_check_host(who, regs, reg_off, nreads))) return rc;
     const i64 total = reg_off[nreads];
-    if (total > 0 && !regs) { meme_set_error("%s: null argument", who); return MEME_E_ARG; }
     PrimaryWs& P = ctx->primary;
     const size_t rbytes = (size_t)total * sizeof(meme_alnreg);
     if ((rc = meme_buf_reserve(ctx, P.regs, rbytes + 64)) || (rc = meme_buf_reserve(ctx, P.out, rbytes + 64)) || (rc = meme_buf_reserve(ctx, P.reg_off, (size_t)(nreads + 1) * 8)) ||
