@@ -148,14 +148,19 @@ struct ResidentBatch {
     int packed_geom[3] = {0, 0, 0};
     bool reads_resident = false;       // reads holds the bases of that batch (false after meme_chain_batch_host: seeds brought by the caller)
 };
-// a seeding counter set (u64): slot cursor of the tier, searches, reads left for the next tier (the length of its overflow list), window loads, eight SEED_PROF sums,
-// searches of the re-seeding kernels' lanes, length of the pending list, the two blocked-region cursors
+// a seeding counter set (u64): slot cursor of the tier, searches, reads left for the next tier (the length of its overflow list), window loads, eight diagnostic sums
+// (SEED_PROF, or RESEED_PROF's census), searches of the re-seeding kernels' lanes, length of the pending list, the two blocked-region cursors; then what
+// meme_debug_reseed_counts reports: the length of the blocked list each batch search met (one per round), the blocked regions' lane searches by the region's
+// stage, how many of them ended without an interval / walked a run for one, and their probes of a neighbour slot outside the cached window
 enum { SEED_CTR_SLOT = 0, SEED_CTR_SEARCHES = 1, SEED_CTR_OVERFLOW = 2, SEED_CTR_WINDOWS = 3, SEED_CTR_PROF = 4, SEED_CTR_LANE = 12, SEED_CTR_PEND = 13, SEED_CTR_BLK = 14, SEED_CTR_BLK_OUT = 15,
-       SEED_CTRS = 16 };
+       SEED_CTR_RS_ROUND = 16, SEED_CTR_RS_STAGE = 24, SEED_CTR_RS_NOINTV = 27, SEED_CTR_RS_WALKED = 28, SEED_CTR_RS_NBPROBE = 29, SEED_CTRS = 32 };
+constexpr int RESEED_MAX_ROUNDS = SEED_CTR_RS_STAGE - SEED_CTR_RS_ROUND;
 enum { SEED_EV_PACK0, SEED_EV_PACK1, SEED_EV_SEARCH0, SEED_EV_SEARCH1, SEED_EV_RESEED0, SEED_EV_GATHER0, SEED_EV_GATHER1, SEED_EVS };   // SeedWs::ev: begin / end of packing, of a tier's search, begin of re-seeding, begin / end of offsets + gather
 struct SeedWs {
     DevBuf slots[3], ovf[2];           // SMEM slots of a tier; reads that overflow it (tier & 1)
     DevBuf slot_cnt, slot_hits, slot_loc, counters, pend, blk;
+    long long reseed_counts[SEED_CTRS - SEED_CTR_RS_ROUND] = {0};   // the re-seeding counters of the last seeding call (meme_debug_reseed_counts); valid while reseed_rounds > 0
+    int reseed_rounds = 0;
     HostBuf h_smems, h_hits, h_smem_off, h_hit_off;   // results of meme_seed_batch_host
     unsigned long long* counter_set(int cset) { return (unsigned long long*)counters.p + SEED_CTRS * cset; }   // two sets: an overflow tier may run beside the re-seeding kernels
     Events<SEED_EVS> ev;

@@ -340,6 +340,16 @@ void tally(SeedRun& R, const unsigned long long* h) {
 
 // The re-seeding kernels behind tier 0's k_seed: k_reseed (a walk on the plcp table, one lane per read), then the pending intervals on a stream of
 // their own beside the rounds over the blocked regions.
+// Batch searches before the last pass searches for itself, and whether k_reseed_emit runs beside the rounds or behind them: compile-time
+// constants, re-measured whenever the searches change (profiles/reseed_early_stop.md §6; named configuration: with 4 rounds the last pass
+// still does 0.23 M one-by-one searches, the fifth batch takes 0.13 ms off the series, a sixth gives it back in launches; behind the
+// rounds k_reseed_emit adds 0.3 ms to the series).
+#ifndef RESEED_ROUNDS
+#define RESEED_ROUNDS 5
+#endif
+#ifndef RESEED_EMIT_BESIDE
+#define RESEED_EMIT_BESIDE 1
+#endif
 int launch_reseed(SeedRun& R) {
     meme_ctx* ctx = R.ctx;
     SeedWs& S = ctx->seed;
@@ -351,6 +361,7 @@ int launch_reseed(SeedRun& R) {
     A.ovf_list = (i64*)S.ovf[0].p; A.counters = S.counter_set(0); A.pend_list = (i64*)S.pend.p;
     A.blk = (BlkRec*)S.blk.p; A.blk_out = A.blk + nreads * BLK_PER_READ; A.blk_cap = nreads * BLK_PER_READ;
     A.blk_ctr = SEED_CTR_BLK; A.blk_out_ctr = SEED_CTR_BLK_OUT;
+    A.read_off = R.d_read_off; A.round = 0;
     i64 rblocks = (nreads + 255) / 256;
     if (rblocks > (i64)ctx->n_cus * 32) rblocks = (i64)ctx->n_cus * 32;
     hipLaunchKernelGGL(k_reseed, dim3((unsigned)rblocks), dim3(256), 0, ctx->stream, A);
@@ -361,18 +372,27 @@ int launch_reseed(SeedRun& R) {
     // kernels; they touch different slots of the reads they share)
     if (!S.emit.s) HIP_TRY(hipStreamCreateWithFlags(&S.emit.s, hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) if (!S.emit_ev[i]) HIP_TRY(hipEventCreateWithFlags(&S.emit_ev[i], hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(S.emit_ev[0], ctx->stream));
-    HIP_TRY(hipStreamWaitEvent(S.emit, S.emit_ev[0], 0));
-    hipLaunchKernelGGL(k_reseed_emit, dim3(sblocks), dim3(256), 0, S.emit, A);
-    HIP_TRY(hipEventRecord(S.emit_ev[1], S.emit));
-    constexpr int ROUNDS = 4;                           // (named configuration: 3 rounds leave 2.2 ms of one-by-one searches to the last pass)
+    if (RESEED_EMIT_BESIDE) {
+        HIP_TRY(hipEventRecord(S.emit_ev[0], ctx->stream));
+        HIP_TRY(hipStreamWaitEvent(S.emit, S.emit_ev[0], 0));
+        hipLaunchKernelGGL(k_reseed_emit, dim3(sblocks), dim3(256), 0, S.emit, A);
+        HIP_TRY(hipEventRecord(S.emit_ev[1], S.emit));
+    }
+    constexpr int ROUNDS = RESEED_ROUNDS;
+    static_assert(ROUNDS >= 1 && ROUNDS <= RESEED_MAX_ROUNDS, "one counter per round");
+    S.reseed_rounds = ROUNDS;
     for (int round = 0; round < ROUNDS; ++round) {     // blocked regions ping-pong between two lists; the last pass searches for itself
+        A.round = round;
         hipLaunchKernelGGL(k_reseed_search, dim3(sblocks), dim3(256), 0, ctx->stream, A);
         if (round < ROUNDS - 1) {
             hipLaunchKernelGGL(k_reseed_resume<false>, dim3(sblocks), dim3(256), 0, ctx->stream, A);
             HIP_TRY(hipMemsetAsync(S.counter_set(0) + A.blk_ctr, 0, sizeof(unsigned long long), ctx->stream));
             std::swap(A.blk, A.blk_out); std::swap(A.blk_ctr, A.blk_out_ctr);
         } else hipLaunchKernelGGL(k_reseed_resume<true>, dim3(sblocks), dim3(256), 0, ctx->stream, A);
+    }
+    if (!RESEED_EMIT_BESIDE) {
+        hipLaunchKernelGGL(k_reseed_emit, dim3(sblocks), dim3(256), 0, ctx->stream, A);
+        HIP_TRY(hipEventRecord(S.emit_ev[1], ctx->stream));
     }
     HIP_TRY(hipGetLastError());
     return MEME_OK;
@@ -405,6 +425,7 @@ int seed_tier0(SeedRun& R) {
     SeedWs& S = ctx->seed;
     int rc;
     R.defer = ctx->seed_defer != 0 && ctx->idx.plcp != nullptr && R.opt->rounds >= 2;
+    S.reseed_rounds = 0;
     if (R.defer && (rc = meme_buf_reserve(ctx, S.pend, (size_t)R.nreads * sizeof(i64)))) return rc;
     if (R.defer && (rc = meme_buf_reserve(ctx, S.blk, (size_t)R.nreads * BLK_PER_READ * 2 * sizeof(BlkRec)))) return rc;
     if ((rc = launch_tier(R, 0, R.nreads, nullptr, 0, ctx->stream, R.defer))) return rc;
@@ -425,6 +446,19 @@ int seed_tier0(SeedRun& R) {
         HIP_TRY(hipEventElapsedTime(&a, S.ev[SEED_EV_RESEED0], S.ev[SEED_EV_SEARCH1]));
         R.ms_reseed += a;
         R.lane_searches += (i64)h[SEED_CTR_LANE];
+        for (int k = SEED_CTR_RS_ROUND; k < SEED_CTRS; ++k) S.reseed_counts[k - SEED_CTR_RS_ROUND] = (long long)h[k];
+#ifdef RESEED_PROF
+        {
+            // the census of the blocked regions' lane searches: single-entry probes by kind and the region's stage
+            const unsigned long long* c = h + SEED_CTR_PROF;
+            fprintf(stderr, "[reseed prof] lists per round:");
+            for (int k = 0; k < S.reseed_rounds; ++k) fprintf(stderr, " %llu", h[SEED_CTR_RS_ROUND + k]);
+            fprintf(stderr, "\n[reseed prof] stage searches partition_probes run_probes\n");
+            for (int k = 0; k < 3; ++k) fprintf(stderr, "[reseed prof] %d %llu %llu %llu\n", k, h[SEED_CTR_RS_STAGE + k], c[k], c[3 + k]);
+            fprintf(stderr, "[reseed prof] interval read %llu, without interval %llu, walked %llu, neighbour probes %llu, last-pass searches %llu\n", c[6],
+                    h[SEED_CTR_RS_NOINTV], h[SEED_CTR_RS_WALKED], h[SEED_CTR_RS_NBPROBE], h[SEED_CTR_LANE]);
+        }
+#endif
         if (getenv("MEME_SEED_TRACE")) fprintf(stderr, "[meme] seed tier 0: search kernel + re-seeding kernels %.2f ms, of which behind k_seed %.2f ms (%lld lane searches; %lld reads of the "
                                                "overflow tier beside them)\n", ms, a, (long long)h[SEED_CTR_LANE], (long long)(R.n_early < 0 ? 0 : R.n_early));
     }
@@ -635,6 +669,17 @@ extern "C" int meme_debug_packed_reads(meme_ctx* ctx, uint64_t* out, int64_t cap
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipMemcpyAsync(out, B.packed.p, (size_t)words * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return MEME_OK;
+}
+
+extern "C" int meme_debug_reseed_counts(meme_ctx* ctx, int64_t* out, int32_t capacity, int32_t* rounds) {
+    if (!ctx || !out || !rounds) return MEME_E_ARG;
+    const SeedWs& S = ctx->seed;
+    if (S.reseed_rounds <= 0) { meme_set_error("meme_debug_reseed_counts: the last seeding call on this ctx ran no re-seeding kernels"); return MEME_E_STATE; }
+    if (capacity < MEME_RESEED_COUNTS) { meme_set_error("meme_debug_reseed_counts: %d values needed", MEME_RESEED_COUNTS); return MEME_E_CAPACITY; }
+    static_assert(MEME_RESEED_COUNTS == RESEED_MAX_ROUNDS + 6 && SEED_CTR_RS_NBPROBE - SEED_CTR_RS_ROUND + 1 == MEME_RESEED_COUNTS, "layout of meme_hip.h");
+    for (int k = 0; k < MEME_RESEED_COUNTS; ++k) out[k] = S.reseed_counts[k];
+    *rounds = S.reseed_rounds;
     return MEME_OK;
 }
 

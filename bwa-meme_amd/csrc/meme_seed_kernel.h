@@ -1069,15 +1069,42 @@ constexpr int LANE_W = 16;
 struct LaneWin {
     uint32_t* lw;          // this lane's column
     i64 base;              // first slot of the cached window, -1: none
+    i64 ms0, ms1;          // the slots below and above the best slot, once probed outside the window (-1: not), and their LCPs (capped by the query length)
+    int mv0, mv1;
     __device__ __forceinline__ bool has(i64 slot) const { return base >= 0 && slot >= base && slot < base + LANE_W; }
     __device__ __forceinline__ int get(i64 slot) const { const int i = (int)(slot - base); return (int)((lw[(i >> 1) * 256] >> (16 * (i & 1))) & 0xffffu); }
 };
+// What a lane's searches cost, for meme_debug_reseed_counts (and, in a RESEED_PROF build, the census of single-entry probes by kind).
+// RESEED_PROF=2 is the census of the searches as they were before the early stop: every search measures its runs.
+struct LaneTally {
+    unsigned no_intv, walked, nb_probes;
+#ifdef RESEED_PROF
+    unsigned part_probes, run_probes;
+#endif
+};
+#ifdef RESEED_PROF
+#define RESEED_COUNT(x_) (++(x_))
+#else
+#define RESEED_COUNT(x_) do { } while (0)
+#endif
+#if defined(RESEED_PROF) && RESEED_PROF == 2
+#define RESEED_EARLY_STOP 0
+#else
+#define RESEED_EARLY_STOP 1
+#endif
+// 0: a measurement build without the counters of meme_debug_reseed_counts (they read 0), to see what keeping them costs
+#ifndef RESEED_TALLY
+#define RESEED_TALLY 1
+#endif
 // LCP of slot with the query, from the cached window when it holds the slot (values there are capped by the query length only,
-// which compares the same way against any level L <= that)
-__device__ __forceinline__ int lane_lcp(const DevIndex& I, const LaneQuery& q, const LaneWin& C, int cap, i64 slot) {
+// which compares the same way against any level L <= that), or from the two neighbours already probed
+__device__ __forceinline__ int lane_lcp(const DevIndex& I, const LaneQuery& q, const LaneWin& C, int cap, i64 slot, LaneTally& T) {
     if (C.has(slot)) return C.get(slot);
+    if (slot == C.ms0) return C.mv0;
+    if (slot == C.ms1) return C.mv1;
     int lc; bool ls;
     lane_compare(I, q, cap, slot, lc, ls);
+    RESEED_COUNT(T.run_probes);
     return lc;
 }
 
@@ -1126,7 +1153,23 @@ __device__ __forceinline__ unsigned quad_window_compare(const DevIndex& I, const
     return (unsigned)group_or<4>((int)m);
 }
 
-__device__ __forceinline__ void lane_search(const DevIndex& I, const LaneQuery& q, bool active, int min_intv, uint32_t* lw, int& r_L, i64& r_start, i64& r_count) {
+//
+// What a search returns.  min_intv == 1 (k_reseed_emit: the SMEM is the query): L = maxLCP and the run of slots that share L bases.
+// min_intv == 2 (every search of a blocked region) is asked by region_apply, which reads the interval in ONE case: stage 2 with r_L >= msl
+// (the SMEM it emits); stages 0 and 1 move the pivot by r_L alone.  `want_intv` says whether the caller is in that case, and the search
+// measures a run only when it is and r_L >= msl.  r_L itself needs no run.  Let c be the slot of the longest match (L0 bases: one of
+// the two slots at the partition point, as before), a and b the LCPs with the query of slots c - 1 and c + 1, capped by L0 (a slot beyond
+// either end of the array: 0).  Then r_L = max(a, b):
+//   * the reference shrinks the match until its interval holds min_intv suffixes (mem_search :2365-2574, right_smem_search :2902-2942);
+//     restated below as: measure the run at level L; if it is narrower than min_intv, L = max(nlo, nhi), the LCPs of the two slots just
+//     outside the run (`L = nlo > nhi ? nlo : nhi`), and again.
+//   * If a or b reaches L0, the run at L0 holds c and that neighbour: two suffixes, the loop stops at L0 = max(a, b).
+//   * Otherwise the run at L0 is c alone, the slots outside it are c - 1 and c + 1, the next level is max(a, b), and the run at that level
+//     holds c and the neighbour that gave the maximum: two suffixes, the loop stops.  (max(a, b) = 0: the run is the whole array.)
+// Either way the interval, when wanted, is the run at level max(a, b), measured once; the neighbours' LCPs are fetched once each (from the
+// cached window, or one probe, remembered for the walk).
+__device__ __forceinline__ void lane_search(const DevIndex& I, const LaneQuery& q, bool active, int min_intv, bool want_intv, int msl, uint32_t* lw,
+                                            LaneTally& T, int& r_L, i64& r_start, i64& r_count) {
     const i64 n = I.n;
     const int t = threadIdx.x & 3;
     i64 p = 0, base = 0;
@@ -1155,7 +1198,7 @@ __device__ __forceinline__ void lane_search(const DevIndex& I, const LaneQuery& 
         lds_handoff();
     }
     if (!active) return;
-    LaneWin C; C.lw = lw; C.base = base;
+    LaneWin C; C.lw = lw; C.base = base; C.ms0 = -1; C.ms1 = -1; C.mv0 = 0; C.mv1 = 0;
     int L = 0;
     i64 s = 0, e = 0;
     bool located = false;
@@ -1173,11 +1216,13 @@ __device__ __forceinline__ void lane_search(const DevIndex& I, const LaneQuery& 
         // partition point by single probes: [0, P) sort before the query.  lo = highest slot known to, hi = lowest slot known not to.
         i64 lo = -1, hi = n;
         lane_compare(I, q, q.vlen, p, lc, ls);
+        RESEED_COUNT(T.part_probes);
         if (ls) {
             lo = p;
             for (i64 st = 1; hi == n && lo < n - 1; st <<= 1) {
                 i64 pr = lo + st; if (pr > n - 1) pr = n - 1;
                 lane_compare(I, q, q.vlen, pr, lc, ls);
+                RESEED_COUNT(T.part_probes);
                 if (ls) lo = pr; else hi = pr;
             }
         } else {
@@ -1185,19 +1230,53 @@ __device__ __forceinline__ void lane_search(const DevIndex& I, const LaneQuery& 
             for (i64 st = 1; lo == -1 && hi > 0; st <<= 1) {
                 i64 pr = hi - st; if (pr < 0) pr = 0;
                 lane_compare(I, q, q.vlen, pr, lc, ls);
+                RESEED_COUNT(T.part_probes);
                 if (ls) lo = pr; else hi = pr;
             }
         }
         while (hi - lo > 1) {
             const i64 mid = lo + (hi - lo) / 2;
             lane_compare(I, q, q.vlen, mid, lc, ls);
+            RESEED_COUNT(T.part_probes);
             if (ls) lo = mid; else hi = mid;
         }
         const i64 P = hi;
-        const int lm = P > 0 ? lane_lcp(I, q, C, q.vlen, P - 1) : -1, lp = P < n ? lane_lcp(I, q, C, q.vlen, P) : -1;
+        int lm = -1, lp = -1;
+        if (P > 0) { if (C.has(P - 1)) lm = C.get(P - 1); else { lane_compare(I, q, q.vlen, P - 1, lm, ls); RESEED_COUNT(T.part_probes); } }
+        if (P < n) { if (C.has(P)) lp = C.get(P); else { lane_compare(I, q, q.vlen, P, lp, ls); RESEED_COUNT(T.part_probes); } }
         L = lm >= lp ? lm : lp;
         s = e = lm >= lp ? P - 1 : P;
+        // the slot of the pair that is not the best one is its neighbour: probed already (the early stop only: min_intv 1 and the census of
+        // the searches as they were keep no memo, lane_lcp never finds one)
+        if (RESEED_EARLY_STOP && min_intv == 2) {
+            if (lm >= lp) { if (P < n) { C.ms1 = P; C.mv1 = lp; } }
+            else if (P > 0) { C.ms0 = P - 1; C.mv0 = lm; }
+        }
     }
+#if RESEED_EARLY_STOP
+    if (min_intv == 2) {
+        // r_L = max(a, b), see above
+        const i64 c = s;
+        int a = 0, b = 0;
+        if (c > 0) {
+            if (C.has(c - 1)) a = C.get(c - 1);
+            else if (C.ms0 == c - 1) a = C.mv0;
+            else { lane_compare(I, q, q.vlen, c - 1, a, ls); C.ms0 = c - 1; C.mv0 = a; ++T.nb_probes; }
+        }
+        if (c < n - 1) {
+            if (C.has(c + 1)) b = C.get(c + 1);
+            else if (C.ms1 == c + 1) b = C.mv1;
+            else { lane_compare(I, q, q.vlen, c + 1, b, ls); C.ms1 = c + 1; C.mv1 = b; ++T.nb_probes; }
+        }
+        if (a > L) a = L;
+        if (b > L) b = L;
+        L = a > b ? a : b;
+        if (!(want_intv && L >= msl)) { ++T.no_intv; r_L = L; r_start = c; r_count = 1; return; }
+        ++T.walked;
+    }
+#else
+    if (min_intv == 2) ++T.walked;
+#endif
     for (;;) {
         // the run of slots around [s, e] that share >= L bases with the query: step by step through the cached window, beyond it
         // gallop and bisect (the predicate is true on a run)
@@ -1206,11 +1285,11 @@ __device__ __forceinline__ void lane_search(const DevIndex& I, const LaneQuery& 
             i64 good = s, bad = -1;
             for (i64 st = 1; good > 0; st <<= 1) {
                 i64 pr = good - st; if (pr < 0) pr = 0;
-                if (lane_lcp(I, q, C, L, pr) >= L) good = pr; else { bad = pr; break; }
+                if (lane_lcp(I, q, C, L, pr, T) >= L) good = pr; else { bad = pr; break; }
             }
             while (bad >= 0 && good - bad > 1) {
                 const i64 mid = bad + (good - bad) / 2;
-                if (lane_lcp(I, q, C, L, mid) >= L) good = mid; else bad = mid;
+                if (lane_lcp(I, q, C, L, mid, T) >= L) good = mid; else bad = mid;
             }
             s = good;
         }
@@ -1219,16 +1298,16 @@ __device__ __forceinline__ void lane_search(const DevIndex& I, const LaneQuery& 
             i64 good = e, bad = n;
             for (i64 st = 1; good < n - 1; st <<= 1) {
                 i64 pr = good + st; if (pr > n - 1) pr = n - 1;
-                if (lane_lcp(I, q, C, L, pr) >= L) good = pr; else { bad = pr; break; }
+                if (lane_lcp(I, q, C, L, pr, T) >= L) good = pr; else { bad = pr; break; }
             }
             while (bad < n && bad - good > 1) {
                 const i64 mid = good + (bad - good) / 2;
-                if (lane_lcp(I, q, C, L, mid) >= L) good = mid; else bad = mid;
+                if (lane_lcp(I, q, C, L, mid, T) >= L) good = mid; else bad = mid;
             }
             e = good;
         }
         if (e - s + 1 >= (i64)min_intv) break;
-        const int nlo = s > 0 ? lane_lcp(I, q, C, L, s - 1) : 0, nhi = e < n - 1 ? lane_lcp(I, q, C, L, e + 1) : 0;
+        const int nlo = s > 0 ? lane_lcp(I, q, C, L, s - 1, T) : 0, nhi = e < n - 1 ? lane_lcp(I, q, C, L, e + 1, T) : 0;
         L = nlo > nhi ? nlo : nhi;
     }
     r_L = L; r_start = s; r_count = e - s + 1;
@@ -1287,7 +1366,63 @@ struct ReseedArgs {
     BlkRec* blk_out;        // k_reseed_resume<false>: the regions that block again, length in counters[blk_out_ctr]
     i64 blk_cap;
     int blk_ctr, blk_out_ctr;
+    const i64* read_off;    // the batch's read offsets: k_reseed takes a read's length from them (a coalesced stream) instead of from its record's last word
+    int round;              // k_reseed_search: which batch search this is (counters[SEED_CTR_RS_ROUND + round] = the length of its list)
 };
+
+// The blocked regions' lane searches, tallied per lane, summed per workgroup and added to the counter set once per workgroup and counter.
+constexpr int RS_NSUM = 6 + 8;       // stage 0 / 1 / 2, no interval, walked, neighbour probes; RESEED_PROF: partition probes by stage, run probes by stage, intervals read
+struct RegionTally {
+    LaneTally T;
+    unsigned stage[3];
+#ifdef RESEED_PROF
+    unsigned part[3], run[3], read;
+#endif
+    __device__ __forceinline__ void clear() {
+        T.no_intv = T.walked = T.nb_probes = 0; stage[0] = stage[1] = stage[2] = 0;
+#ifdef RESEED_PROF
+        T.part_probes = T.run_probes = 0; part[0] = part[1] = part[2] = run[0] = run[1] = run[2] = read = 0;
+#endif
+    }
+    // after a search of a region in `stage` (0..2) that returned r_L
+    __device__ __forceinline__ void searched(int st, int r_L, int msl) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {                 // (no dynamic index: the tallies stay in registers)
+            stage[i] += st == i ? 1u : 0u;
+#ifdef RESEED_PROF
+            part[i] += st == i ? T.part_probes : 0u; run[i] += st == i ? T.run_probes : 0u;
+#endif
+        }
+#ifdef RESEED_PROF
+        T.part_probes = T.run_probes = 0;
+        if (st == 2 && r_L >= msl) ++read;
+#else
+        (void)r_L; (void)msl;
+#endif
+    }
+    // `sum`: RS_NSUM words of LDS, zeroed behind a barrier by the caller
+    __device__ __forceinline__ void to_lds(unsigned* sum) const {
+        if (!RESEED_TALLY) return;
+        const unsigned v[6] = {stage[0], stage[1], stage[2], T.no_intv, T.walked, T.nb_probes};
+#pragma unroll
+        for (int i = 0; i < 6; ++i) if (v[i]) atomicAdd(&sum[i], v[i]);
+#ifdef RESEED_PROF
+        const unsigned w[7] = {part[0], part[1], part[2], run[0], run[1], run[2], read};
+#pragma unroll
+        for (int i = 0; i < 7; ++i) if (w[i]) atomicAdd(&sum[6 + i], w[i]);
+#endif
+    }
+    // the workgroup's sums to the counter set, behind a barrier after the last to_lds(); every thread of the workgroup comes here
+    static __device__ __forceinline__ void publish(const unsigned* sum, unsigned long long* counters) {
+        if (!RESEED_TALLY) return;
+        if (threadIdx.x < 6 && sum[threadIdx.x]) atomicAdd(&counters[SEED_CTR_RS_STAGE + threadIdx.x], (unsigned long long)sum[threadIdx.x]);
+#ifdef RESEED_PROF
+        if (threadIdx.x >= 6 && threadIdx.x < 13 && sum[threadIdx.x]) atomicAdd(&counters[SEED_CTR_PROF + threadIdx.x - 6], (unsigned long long)sum[threadIdx.x]);
+#endif
+    }
+};
+static_assert(SEED_CTR_RS_NOINTV == SEED_CTR_RS_STAGE + 3 && SEED_CTR_RS_WALKED == SEED_CTR_RS_STAGE + 4 && SEED_CTR_RS_NBPROBE == SEED_CTR_RS_STAGE + 5,
+              "RegionTally::publish adds six consecutive counters");
 
 // One SMEM more for a read.  OWNED: the calling lane is the only one working on the read (plain counter in a register, published by the
 // caller); otherwise regions of one read may be in different lanes and the read's counters are bumped atomically.
@@ -1424,10 +1559,11 @@ __global__ void __launch_bounds__(256) k_reseed(ReseedArgs A) {
             const int c0 = have ? A.slot_cnt[r] : 0;
             const int c = c0 > DEFER_MAX_K ? DEFER_MAX_K : c0;
             SlotRec* sl = A.slots + (have ? r : 0) * cap;
-            const u64* rec = A.packed + (have ? r : 0) * A.geo.stride;   // fw[W] rc[W] nfw[MW] nrc[MW] len
             SmemAppender<true> ap;
             ap.sl = sl; ap.cap = cap; ap.hps = A.opt.hits_per_smem; ap.ns = c0; ap.hits_add = 0; ap.rid = r;
-            int l_seq = 0;
+            // the read's length (the walk's guard) is what the packer wrote into the record's last word: from the offsets, a coalesced stream,
+            // instead of one more random line of the packed image
+            const int l_seq = have ? (int)(A.read_off[r + 1] - A.read_off[r]) : 0;
             // the lanes of a wavefront take their j-th region together (a loop over the slot index would run the region code once per
             // slot position with a few lanes each), and stay in the loop until the last of them has none left: the table windows are
             // fetched by the quad
@@ -1447,7 +1583,6 @@ __global__ void __launch_bounds__(256) k_reseed(ReseedArgs A) {
                 RegionState S;
                 S.pivot = 0; S.next = 0; S.guard = 0; S.stage = 0;
                 if (live) {
-                    if (l_seq == 0) { const u64 lw = rec[A.geo.stride - 1]; l_seq = (int)(lw & 0x7fffffffull); }
                     qbeg = sl[k].start; qend = sl[k].end;
                     T0 = (f & SLOT_VAL) - qbeg;
                     S.pivot = (qbeg + qend) >> 1;
@@ -1503,6 +1638,7 @@ __global__ void __launch_bounds__(256) k_reseed(ReseedArgs A) {
 __global__ void __launch_bounds__(256) k_reseed_emit(ReseedArgs A) {
     __shared__ uint32_t lwin[(LANE_W / 2) * 256];
     const i64 n_list = (i64)A.counters[SEED_CTR_PEND];
+    LaneTally T = {};                                // (not reported: these searches always measure their run)
     for (i64 i0 = (i64)blockIdx.x * blockDim.x; i0 < n_list; i0 += (i64)gridDim.x * blockDim.x) {
         // (runs beside the blocked regions' passes, which append to the same reads: only the slots the first pass filled are looked
         // at, and the hit count is bumped atomically)
@@ -1529,7 +1665,7 @@ __global__ void __launch_bounds__(256) k_reseed_emit(ReseedArgs A) {
                 q.wq = ext_g(q.s, q.off);
             }
             int r_L = 0; i64 r_start = 0, r_count = 0;
-            lane_search(A.I, q, live, 1, lwin + threadIdx.x, r_L, r_start, r_count);
+            lane_search(A.I, q, live, 1, true, 0, lwin + threadIdx.x, T, r_L, r_start, r_count);
             if (live) {
                 sl[k].sa_start = r_start; sl[k].count = r_count;
                 hits_add += (A.opt.hits_per_smem > 0 && r_count > A.opt.hits_per_smem) ? (i64)A.opt.hits_per_smem : r_count;
@@ -1542,25 +1678,38 @@ __global__ void __launch_bounds__(256) k_reseed_emit(ReseedArgs A) {
 // The searches the blocked regions wait for, as a dense batch: one lane per region.
 __global__ void __launch_bounds__(256) k_reseed_search(ReseedArgs A) {
     __shared__ uint32_t lwin[(LANE_W / 2) * 256];
+    __shared__ unsigned sum[RS_NSUM];
+    if (threadIdx.x < RS_NSUM) sum[threadIdx.x] = 0;
+    __syncthreads();
     i64 n_blk = (i64)A.counters[A.blk_ctr];
     if (n_blk > A.blk_cap) n_blk = A.blk_cap;
+    if (blockIdx.x == 0 && threadIdx.x == 0) A.counters[SEED_CTR_RS_ROUND + A.round] = (unsigned long long)n_blk;
+    const int msl = A.opt.min_seed_len;
+    RegionTally tl;
+    tl.clear();
     for (i64 i0 = (i64)blockIdx.x * blockDim.x; i0 < n_blk; i0 += (i64)gridDim.x * blockDim.x) {
         const i64 i = i0 + threadIdx.x;
         const bool have = i < n_blk;                  // (the list's last wavefront: lanes without a region serve their quad)
         LaneQuery q;
         q.s = A.packed; q.off = 0; q.vlen = 0; q.wq = 0;
+        int stage = 0;
         if (have) {
             const BlkRec b = A.blk[i];
             const u64* rec = A.packed + b.rid * A.geo.stride;
             const u64 lw = rec[A.geo.stride - 1];
             RegionState S;
             S.pivot = b.pivot; S.next = b.next; S.guard = b.guard; S.stage = b.stage & ~BLK_MORE;
+            stage = S.stage;
             q = region_query(rec, A.geo, (int)(lw & 0x7fffffffull), ((lw >> 31) & 1ull) != 0, S);
         }
         int r_L = 0; i64 r_start = 0, r_count = 0;
-        lane_search(A.I, q, have, 2, lwin + threadIdx.x, r_L, r_start, r_count);
-        if (have) { A.blk[i].r_L = r_L; A.blk[i].r_start = r_start; A.blk[i].r_count = r_count; }
+        // only a region in stage 2 can go on to read the interval (region_apply)
+        lane_search(A.I, q, have, 2, stage == 2, msl, lwin + threadIdx.x, tl.T, r_L, r_start, r_count);
+        if (have) { A.blk[i].r_L = r_L; A.blk[i].r_start = r_start; A.blk[i].r_count = r_count; tl.searched(stage, r_L, msl); }
     }
+    tl.to_lds(sum);
+    __syncthreads();
+    RegionTally::publish(sum, A.counters);
 }
 
 // Pass 2 (and 3, 4): one lane per blocked region: the search's result, then on with the table.  A region that blocks again goes to the
@@ -1574,6 +1723,8 @@ __global__ void __launch_bounds__(256, 3) k_reseed_resume(ReseedArgs A) {
     __shared__ uint32_t lwin[(LANE_W / 2) * 256];
     __shared__ unsigned long long acc_total, acc_lane, out_base;
     __shared__ unsigned out_n;
+    __shared__ unsigned sum[LAST ? RS_NSUM : 1];
+    if (LAST && threadIdx.x < RS_NSUM) sum[threadIdx.x] = 0;
     const uint8_t* __restrict__ plcp = A.I.plcp;
     const i64 n = A.I.n;
     const int msl = A.opt.min_seed_len;
@@ -1644,9 +1795,13 @@ __global__ void __launch_bounds__(256, 3) k_reseed_resume(ReseedArgs A) {
                     q.s = rec; q.off = 0; q.vlen = 0; q.wq = 0;
                     if (need) q = region_query(rec, A.geo, l_seq, has_n, S);
                     int r_L = 0; i64 r_start = 0, r_count = 0;
-                    lane_search(A.I, q, need, 2, lwin + threadIdx.x, r_L, r_start, r_count);
+                    RegionTally tl;              // (summed in LDS search by search: this pass has no registers to spare, and few searches)
+                    tl.clear();
+                    lane_search(A.I, q, need, 2, S.stage == 2, msl, lwin + threadIdx.x, tl.T, r_L, r_start, r_count);
                     if (need) {
                         ++lsearches; ++hops;
+                        tl.searched(S.stage, r_L, msl);
+                        tl.to_lds(sum);
                         region_apply<false>(S, msl, r_L, r_start, r_count, ap);
                     }
                 }
@@ -1675,6 +1830,7 @@ __global__ void __launch_bounds__(256, 3) k_reseed_resume(ReseedArgs A) {
         if (acc_total) atomicAdd(&A.counters[SEED_CTR_SEARCHES], acc_total);
         if (acc_lane) atomicAdd(&A.counters[SEED_CTR_LANE], acc_lane);
     }
+    if (LAST) RegionTally::publish(sum, A.counters);
 }
 
 }  // namespace seedk

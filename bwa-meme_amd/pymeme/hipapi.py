@@ -202,7 +202,11 @@ EXPORTS = ["meme_device_count", "meme_ctx_create", "meme_ctx_destroy", "meme_las
            "meme_index_attach", "meme_index_describe", "meme_index_share", "meme_index_replicate", "meme_host_alloc",
            "meme_host_free", "meme_stage_pack_text", "meme_stage_pos5_from_sa", "meme_stage_build_entries", "meme_stage_build_plcp",
            "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_primary_batch_host", "meme_primary_batch_device", "meme_finish_batch_host", "meme_finish_batch_device", "meme_seed_batch_device",
-           "meme_bsw_batch", "meme_bsw_batch_device", "meme_get_timings", "meme_set_tuning", "meme_debug_packed_reads"]
+           "meme_bsw_batch", "meme_bsw_batch_device", "meme_get_timings", "meme_set_tuning", "meme_debug_packed_reads",
+           "meme_debug_reseed_counts"]
+
+RESEED_MAX_ROUNDS = 8                    # meme_hip.h: MEME_RESEED_COUNTS = RESEED_MAX_ROUNDS + 6 values from meme_debug_reseed_counts
+RESEED_COUNTS = RESEED_MAX_ROUNDS + 6
 
 _lib = None
 
@@ -392,6 +396,15 @@ class Context:
         words = np.zeros((n.value, geom[2]), dtype=np.uint64)
         _check(lib().meme_debug_packed_reads(C.c_void_p(self.h), _p(words), C.c_int64(words.size), geom, C.byref(n)))
         return words, int(geom[0]), int(geom[1])
+
+    def debug_reseed_counts(self):
+        """meme_debug_reseed_counts: the blocked regions of the last seeding call.  Returns a dict: `rounds` (blocked regions each batch search met),
+        `stage` (lane searches by the region's stage 0 / 1 / 2), `no_interval`, `walked`, `neighbour_probes`."""
+        out, rounds = np.zeros(RESEED_COUNTS, dtype=np.int64), C.c_int32(0)
+        _check(lib().meme_debug_reseed_counts(C.c_void_p(self.h), _p(out), C.c_int32(out.size), C.byref(rounds)))
+        st = RESEED_MAX_ROUNDS                         # layout: one list length per round, then stage 0 / 1 / 2, no interval, walked, neighbour probes
+        return {"rounds": [int(v) for v in out[:rounds.value]], "stage": [int(v) for v in out[st:st + 3]], "no_interval": int(out[st + 3]),
+                "walked": int(out[st + 4]), "neighbour_probes": int(out[st + 5])}
 
     def seed_reserve(self, nreads, total_bases):
         _check(lib().meme_seed_reserve(C.c_void_p(self.h), C.c_int64(nreads), C.c_int64(total_bases)))

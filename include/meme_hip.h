@@ -495,6 +495,15 @@ int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value);   /* "group_
  * sizing call), otherwise capacity_words < nreads * stride is MEME_E_CAPACITY.  MEME_E_STATE when no batch was packed on the ctx. */
 int meme_debug_packed_reads(meme_ctx* ctx, uint64_t* out, int64_t capacity_words, int32_t* geom, int64_t* nreads);
 
+/* Debug: what the re-seeding kernels of the last seeding call did with the regions the plcp table could not answer ("blocked" regions).
+ * out[0..7]: blocked regions each batch search met, one per round (*rounds of them are in use); out[8..10]: lane searches of blocked
+ * regions by the region's stage (0 right of the middle, 1 left of the pivot, 2 right of the new pivot); out[11]: of these, answered with a
+ * length alone; out[12]: walked a run of suffix-array slots for the interval; out[13]: probes of a slot next to the best one that lay outside
+ * the search's cached window.  capacity < MEME_RESEED_COUNTS is MEME_E_CAPACITY; MEME_E_STATE when the last seeding call ran no re-seeding
+ * kernels (seed_defer 0, no plcp table, one round, or no call yet). */
+#define MEME_RESEED_COUNTS 14
+int meme_debug_reseed_counts(meme_ctx* ctx, int64_t* out, int32_t capacity, int32_t* rounds);
+
 #ifdef __cplusplus
 }
 #endif
