@@ -201,6 +201,14 @@ struct PrimaryWs {     // regs / reg_off / out / n_pri / mapq / status: the host
     bool log_ready = false;
 };
 
+struct PairWs {        // regs / reg_off / n_pri / res / status / counter: the host form's staging (res: score, sub, n_sub, n_cand and z, six ints a pair); keys: a heavy pair's sorted keys
+                       // behind the LDS cap; list: the heavy pairs; tab: PairDirs and the penalty table, h_tab what it is copied from (tab_ev: the copy has passed); contigs: ContigTab,
+                       // h_contigs what it was staged from (restaged only when it changes)
+    DevBuf regs, reg_off, n_pri, res, status, counter, keys, list, tab, contigs; HostBuf h_res, h_status, h_tab; Events<2> ev; Events<1> tab_ev;
+    bool tab_in_flight = false;
+    std::vector<unsigned char> h_contigs; std::vector<meme_contig> last_contigs; i64 last_l_pac = -1;
+};
+
 struct FinishWs {      // regs / reg_off / out / reg_off_out / ums / status / counters: the host form's staging; stage: the records a read keeps, at the read's input offsets, before the
                        // pack; cnt: records kept per read; live / first: live records of a read and the first of them; list: the wavefront tier's reads; cols_l / cols_c: the
                        // columns of reads too large for LDS; contigs: ContigTab, h_contigs what it was staged from (restaged only when it changes)
@@ -225,7 +233,7 @@ struct meme_ctx {
     // workspaces (scan_tmp: tiles of the prefix sums, meme_scan_exclusive and the seeding gather)
     ResidentBatch batch;
     DevBuf scan_tmp;
-    ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam; PrimaryWs primary; FinishWs finish; SeedWs seed;
+    ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam; PrimaryWs primary; PairWs pair; FinishWs finish; SeedWs seed;
     // Streams.  Order of destruction: meme_ctx_destroy synchronises every stream of the ctx; then the members go in reverse order of declaration, so the streams
     // and their fork / join events -- these two and, last member of the last workspace, the seeding stage's -- are destroyed BEFORE any DevBuf / HostBuf above is
     // freed.  A new stream holder goes below the buffers too: here, or last in SeedWs.  (A stage's timing events go with the stage; they are idle by then.)
@@ -247,6 +255,9 @@ struct meme_ctx {
     i64 sam_max_batch = 0;             // > 0: meme_sam_format_batch_host refuses more record slots than this with MEME_E_CAPACITY (the caller then formats in pieces)
     i64 primary_split = 8;             // primary marking: reads with more records than this go to the wavefront-per-read tier (0: every non-empty read; at most 8, the lanes of the light tier's group)
     i64 primary_blocks = 0;            // > 0: cap on the workgroups of the primary-marking kernels (0 = none)
+    i64 pair_split = 8;                // pair scoring: pairs with more keys (records of both ends that take part) than this go to the wavefront-per-pair tier (0: every non-empty pair; at most 8)
+    i64 pair_blocks = 0;               // > 0: cap on the workgroups of the pair-scoring kernels (0 = none)
+    i64 pair_lds_keys = 0;             // > 0: the wavefront tier keeps this many sorted keys of a pair in LDS, the rest in HBM (0, and anything above it: 512)
     i64 finish_blocks = 0;             // > 0: cap on the workgroups of the record-finishing kernels (0 = none)
     i64 finish_lds_recs = 0;           // > 0: reads handed over with more records than this are walked in HBM by the wavefront tier (0, and anything above it: 128)
     i64 ext_live_only = 0;             // 1: meme_extend_last_batch_host hands over the surviving records only (qe > qb: what src/bwamem.cpp:1680-1693 keeps)

@@ -141,6 +141,38 @@ def default_primary_opt(**kw):
     return o
 
 
+class PairPes(C.Structure):         # meme_pair_pes = mem_pestat_t
+    _fields_ = [(n, C.c_int32) for n in ("low", "high", "failed", "pad")] + [("avg", C.c_double), ("std", C.c_double)]
+
+
+class PairOpt(C.Structure):         # meme_pair_opt
+    _fields_ = [(n, C.c_int32) for n in ("a", "b", "o_del", "e_del", "o_ins", "e_ins")]
+
+
+class PairHost(C.Structure):        # meme_pair_host_result
+    _fields_ = [("npairs", C.c_int64), ("score", C.c_void_p), ("sub", C.c_void_p), ("n_sub", C.c_void_p), ("n_cand", C.c_void_p), ("z", C.c_void_p), ("status", C.c_void_p),
+                ("n_heavy", C.c_int64), ("kernel_ms", C.c_float)]
+
+
+class PairDeviceOut(C.Structure):   # meme_pair_device_out
+    _fields_ = [(n, C.c_void_p) for n in ("d_score", "d_sub", "d_n_sub", "d_n_cand", "d_z", "d_status", "d_n_heavy")]
+
+
+def default_pair_opt(**kw):
+    # mem_opt_init (reference src/bwamem.cpp:126-162): a 1, b 4, gaps 6 + 1
+    o = PairOpt(1, 4, 6, 1, 6, 1)
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
+
+
+def pair_pes(pes):
+    """four (low, high, failed, avg, std) -> the meme_pair_pes[4] of the pair stage"""
+    assert len(pes) == 4
+    return (PairPes * 4)(*[PairPes(int(lo), int(hi), int(failed), 0, float(avg), float(std)) for lo, hi, failed, avg, std in pes])
+
+
 class FinishOpt(C.Structure):       # meme_finish_opt
     _fields_ = [(n, C.c_int32) for n in ("a", "b", "o_del", "e_del", "o_ins", "e_ins", "w", "max_chain_gap")] + [("mask_level_redun", C.c_float), ("pad", C.c_int32)]
 
@@ -201,7 +233,7 @@ EXPORTS = ["meme_device_count", "meme_ctx_create", "meme_ctx_destroy", "meme_las
            "meme_index_pos5_bytes",
            "meme_index_attach", "meme_index_describe", "meme_index_share", "meme_index_replicate", "meme_host_alloc",
            "meme_host_free", "meme_stage_pack_text", "meme_stage_pos5_from_sa", "meme_stage_build_entries", "meme_stage_build_plcp",
-           "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_primary_batch_host", "meme_primary_batch_device", "meme_finish_batch_host", "meme_finish_batch_device", "meme_seed_batch_device",
+           "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_primary_batch_host", "meme_primary_batch_device", "meme_finish_batch_host", "meme_finish_batch_device", "meme_pair_batch_host", "meme_pair_batch_device", "meme_seed_batch_device",
            "meme_bsw_batch", "meme_bsw_batch_device", "meme_get_timings", "meme_set_tuning", "meme_debug_packed_reads",
            "meme_debug_reseed_counts"]
 
@@ -556,6 +588,39 @@ class Context:
         out = PrimaryDeviceOut(d_regs_out_ptr, d_n_pri_ptr, d_mapq_ptr, d_status_ptr, d_n_heavy_ptr)
         _check(lib().meme_primary_batch_device(C.c_void_p(self.h), C.c_void_p(d_regs_ptr), C.c_void_p(d_reg_off_ptr), C.c_int64(nreads), C.c_int64(total_regs), C.c_int64(int(id_base)),
                                                C.byref(opt or default_primary_opt()), C.byref(out)))
+
+    def pair_batch_host(self, regs, reg_off, n_pri, contigs, l_pac, pes, id_base=0, opt=None):
+        """meme_pair_batch_host: pair scoring (mem_pair) of the records regs (ALNREG) per read -- reads 2p and 2p + 1 are pair p with id id_base + p, the first n_pri[r]
+        records of read r take part; contigs: (offset, len, is_alt); pes: four (low, high, failed, avg, std).  Returns dict(score, sub, n_sub, n_cand, z (pairs x 2),
+        status, n_heavy, kernel_ms)."""
+        opt = opt or default_pair_opt()
+        assert regs.dtype == ALNREG and regs.flags.c_contiguous
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
+        n_pri = np.ascontiguousarray(n_pri, dtype=np.int32)
+        n = reg_off.shape[0] - 1
+        assert n_pri.shape[0] == n
+        arr = (Contig * len(contigs))(*[Contig(int(o), int(l), int(a)) for o, l, a in contigs])
+        res = PairHost()
+        _check(lib().meme_pair_batch_host(C.c_void_p(self.h), _p(regs), _p(reg_off), _p(n_pri), C.c_int64(n), arr, C.c_int32(len(contigs)), C.c_int64(int(l_pac)), pair_pes(pes),
+                                          C.c_int64(int(id_base)), C.byref(opt), C.byref(res)))
+
+        def view(ptr, count):
+            if count == 0 or not ptr:
+                return np.zeros(0, dtype=np.int32)
+            return np.frombuffer((C.c_char * (count * 4)).from_address(ptr), dtype=np.int32, count=count).copy()
+        m = int(res.npairs)
+        status = np.frombuffer((C.c_char * m).from_address(res.status), dtype=np.uint8, count=m).copy() if m and res.status else np.zeros(0, np.uint8)
+        return {"score": view(res.score, m), "sub": view(res.sub, m), "n_sub": view(res.n_sub, m), "n_cand": view(res.n_cand, m), "z": view(res.z, 2 * m).reshape(m, 2),
+                "status": status, "n_heavy": int(res.n_heavy), "kernel_ms": float(res.kernel_ms)}
+
+    def pair_batch_device(self, d_regs_ptr, d_reg_off_ptr, d_n_pri_ptr, nreads, total_regs, contigs, l_pac, pes, id_base, opt, d_score_ptr, d_sub_ptr, d_n_sub_ptr, d_n_cand_ptr, d_z_ptr,
+                          d_status_ptr, d_n_heavy_ptr):
+        """meme_pair_batch_device: the same on device arrays the caller owns (d_regs_out, d_reg_off and d_n_pri of primary_batch_device as they are), asynchronous on the ctx's
+        stream (sync() before reading the results)."""
+        arr = (Contig * len(contigs))(*[Contig(int(o), int(l), int(a)) for o, l, a in contigs])
+        out = PairDeviceOut(d_score_ptr, d_sub_ptr, d_n_sub_ptr, d_n_cand_ptr, d_z_ptr, d_status_ptr, d_n_heavy_ptr)
+        _check(lib().meme_pair_batch_device(C.c_void_p(self.h), C.c_void_p(d_regs_ptr), C.c_void_p(d_reg_off_ptr), C.c_void_p(d_n_pri_ptr), C.c_int64(nreads), C.c_int64(total_regs), arr,
+                                            C.c_int32(len(contigs)), C.c_int64(int(l_pac)), pair_pes(pes), C.c_int64(int(id_base)), C.byref(opt or default_pair_opt()), C.byref(out)))
 
     def finish_batch_host(self, regs, reg_off, contigs, l_pac, opt=None):
         """meme_finish_batch_host: record finishing (compaction to the live records, mem_sort_dedup_patch_mate_sort, is_alt) of the records regs (ALNREG) per read;

@@ -19,6 +19,7 @@
  *   meme_sam_format_batch_host      <- mem_aln2sam() for a chunk's plain records     src/bwamem.cpp:2174-2312
  *   meme_matesw_batch_host          <- mem_sam_pe_batch_pre() + mem_sam_pe_batch()   src/bwamem_pair.cpp:660-716, 1060-1223, 719-818
  *   meme_primary_batch_host         <- mem_mark_primary_se() + mem_reorder_primary5() + mem_approx_mapq_se()   src/bwamem.cpp:1974-2100
+ *   meme_pair_batch_host            <- mem_pair()                                    src/bwamem_pair.cpp:372-433
  *   meme_bsw_batch                  <- BandedPairWiseSW::getScores8 / getScores16 /
  *                                      scalarBandedSWAWrapper                 src/bandedSWA.h:118-135,257-297
  *
@@ -431,6 +432,44 @@ typedef struct { meme_alnreg* d_regs_out; int32_t* d_n_pri; uint8_t* d_mapq; uin
 int meme_primary_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs, const int64_t* d_reg_off, int64_t nreads, int64_t total_regs, int64_t id_base,
                               const meme_primary_opt* opt, const meme_primary_device_out* out);
 
+/* ---- pair scoring: the second step of mem_sam_pe ---------------------------------------------------------------------------------------------
+ * What mem_pair (reference src/bwamem_pair.cpp:372-433) computes for the two ends of every pair of a batch: reads 2p and 2p + 1 of the call are pair p, the
+ * first n_pri[r] records of read r (what mem_mark_primary_se returned; regs, reg_off and n_pri as the primary stage leaves them) take part.  Per pair:
+ * score = what mem_pair returns (the best candidate's q), sub, n_sub, n_cand (u.n, the number of candidate pairings), z[2] = the indices of the best
+ * pairing's records in their reads (-1, -1 where n_cand == 0).  Every output is an integer that equals the compiled reference's.
+ * The id: pair p of the call has id id_base + p, mem_pair's `id`, which the aligner passes as (n_processed >> 1) + p (src/bwamem_pair.cpp:931); it is
+ * truncated to an int and shifted by 8 as the reference's prototype does, and seeds the hash that orders candidates of equal q.
+ * pes[4]: mem_pestat_t of the four orientations, whole.  The penalty term of q, .721 * log(2 erfc(|dist - avg| / std / sqrt 2)) * a, is evaluated on the HOST
+ * by its libm for every distance low .. high of every orientation that has not failed, per call, and staged on the ctx's stream as a table: no erfc or log
+ * runs on the device.  high - low + 1 > 1 << 20 for such an orientation is MEME_E_ARG.  std == 0 is no special case (its infinite / NaN entries score 0, as
+ * in the reference).
+ * What it does NOT do: the pairing decision behind mem_pair (is_multi, q_pe, q_se, the secondary_all swap, src/bwamem_pair.cpp:938-992) and mate rescue in
+ * front of it stay with the caller.
+ * Conventions: a pair one of whose ends has n_pri == 0 gets zeros and z = -1, -1 (the reference does not call mem_pair there).  status[p] = 1: a record that
+ * takes part has rid outside [0, n_contigs) or a negative score; the pair is skipped, zeros and z = -1, -1.  status[p] = 2 (device form only): reg_off of one
+ * of its reads is no span inside [0, total_regs], or n_pri is negative or exceeds the span; skipped likewise.  nreads odd, a null argument, opt->a < 1:
+ * MEME_E_ARG.  Host form: results in pinned memory of the ctx until its next call of this function. */
+typedef struct { int32_t low, high, failed, pad; double avg, std; } meme_pair_pes;   /* mem_pestat_t, whole */
+typedef struct { int32_t a, b, o_del, e_del, o_ins, e_ins; } meme_pair_opt;         /* mem_opt_t fields of the same names */
+typedef struct {
+    int64_t npairs;
+    const int32_t *score, *sub, *n_sub, *n_cand;   /* npairs each */
+    const int32_t* z;             /* 2 * npairs */
+    const uint8_t* status;        /* npairs */
+    int64_t n_heavy;              /* pairs the wavefront-per-pair tier took (tuning "pair_split") */
+    float kernel_ms;              /* HIP events around the stage's kernels */
+} meme_pair_host_result;
+int meme_pair_batch_host(meme_ctx* ctx, const meme_alnreg* regs, const int64_t* reg_off /* nreads + 1, from 0 */, const int32_t* n_pri /* nreads */, int64_t nreads,
+                         const meme_contig* contigs, int32_t n_contigs, int64_t l_pac, const meme_pair_pes* pes /* 4 */, int64_t id_base, const meme_pair_opt* opt,
+                         meme_pair_host_result* out);
+/* The same on device arrays the caller owns -- d_regs, d_reg_off, d_n_pri: d_regs_out, d_reg_off and d_n_pri of meme_primary_batch_device as they are; the
+ * outputs: nreads / 2 entries each, d_z twice as many, d_n_heavy one counter -- asynchronous on the ctx's stream: only the table is built (and copied from)
+ * on the host, which does not wait for the kernels. */
+typedef struct { int32_t *d_score, *d_sub, *d_n_sub, *d_n_cand, *d_z; uint8_t* d_status; uint64_t* d_n_heavy; } meme_pair_device_out;
+int meme_pair_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs, const int64_t* d_reg_off, const int32_t* d_n_pri, int64_t nreads, int64_t total_regs,
+                           const meme_contig* contigs, int32_t n_contigs, int64_t l_pac, const meme_pair_pes* pes /* 4 */, int64_t id_base, const meme_pair_opt* opt,
+                           const meme_pair_device_out* out);
+
 /* ---- record finishing: the tail of mem_kernel2_core ----------------------------------------------------------------------------------------
  * What mem_kernel2_core does behind the extension (reference src/bwamem.cpp:1681-1719) with the alignment records of every read of a batch: the
  * compaction to the live records (qe > qb), mem_sort_dedup_patch_mate_sort (:312-383: the order by end, the exclusion of redundant hits, mem_patch_reg
@@ -487,7 +526,7 @@ typedef struct {
     int64_t gcig_class_jobs[6];   /* the last CIGAR call's jobs by kernel: 16-lane groups, 32-lane groups, a wavefront each in 64-column chunks, the gap-free shortcut, 64-lane "groups"; the last entry is always 0 (the two-columns-per-lane kernel it counted was removed) */
 } meme_timings;
 int meme_get_timings(meme_ctx* ctx, meme_timings* out);
-int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value);   /* "group_lanes", "seed_blocks_per_cu", "seed_blocks", "smem_cap", "bsw_blocks", "bsw_lane_min_pairs", "chain_wave_tiers", "chain_lane_hits", "chain_light_hits", "seed_defer", "ext_live_only" (1: meme_extend_last_batch_host hands over only the records mem_kernel2_core keeps, src/bwamem.cpp:1680-1693 -- qe > qb, in order -- instead of one per chained seed with the purged ones marked; the stage then also runs in rounds -- "ext_rounds" (default 1; 0: off): a read's seeds are taken in extension order, tested against the read's surviving alignments first and extended only if they survive, one seed per read and round, after that many rounds everything still ahead at once: the same surviving records, without the banded SW of seeds the purge drops), "gcig_groups" (1, default: CIGAR jobs whose band has at most 16 / 32 / 64 columns run 4 / 2 / 1 to a wavefront with one chunk per row; 0: one wavefront per job in 64-column chunks; any other value: MEME_E_ARG), "gcig_zcap" (>= 0: bytes of LDS a CIGAR job keeps for its backtrack matrix or the window it is walked back through; default: chosen per call, 8192 where a typical matrix of the batch fits, else 2048; results do not depend on it), "ext_census" (1: meme_extend_last_batch_host also counts the extension jobs whose query is a prefix of its target), "max_batch" (> 0: meme_extend_last_batch_host / meme_global_batch_host refuse larger batches with MEME_E_CAPACITY), "ext_slab_jobs" (default 8 Mi, at least 1: the extension stage poses and aligns its jobs in slabs of whole reads with at most this many jobs per side, and at least one read, each -- a bound, and how the tests reach the multi-slab path; same records), "ext_split" (default 1: the extension stage's kernels that walk a read's chains run eight lanes per read for reads with at most 8 chained seeds and a wavefront per read for the others; 0: a wavefront per read throughout; same records), "bsw_circ" (default 1: the lane-per-pair banded-SW kernel keeps the columns of queries longer than its band in a ring of 2w + 2 columns -- same results, more wavefronts per CU; 0: one LDS word per query column as before), "sam_max_batch" (> 0: meme_sam_format_batch_host refuses more record slots than this with MEME_E_CAPACITY; the caller formats in pieces), "helper_blocks" (> 0: at most this many workgroups in the read packer, the offsets scan and the hit gather of a seeding call, as "seed_blocks" does for the search kernel -- how the tests drive their loops round with small batches; 0, default: no cap; same results), "primary_split" (default 8, its maximum: meme_primary_batch_host / _device run reads with at most this many records eight lanes to a read with the records in registers, reads with more a wavefront each with the records in HBM; 0 sends every non-empty read to the wavefront tier; larger values count as 8; same results), "primary_blocks" (> 0: at most this many workgroups in each kernel of that stage, so that a small batch goes round their grid-stride loops; 0, default: no cap; same results), "finish_blocks" (> 0: the same cap for the kernels of meme_finish_batch_host / _device; 0, default: no cap; same results), "finish_lds_recs" (> 0: reads handed over with more records than this are walked by the wavefront tier of that stage in a workspace in HBM instead of in LDS; 0, default, and anything above it: 128; same results) */
+int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value);   /* "group_lanes", "seed_blocks_per_cu", "seed_blocks", "smem_cap", "bsw_blocks", "bsw_lane_min_pairs", "chain_wave_tiers", "chain_lane_hits", "chain_light_hits", "seed_defer", "ext_live_only" (1: meme_extend_last_batch_host hands over only the records mem_kernel2_core keeps, src/bwamem.cpp:1680-1693 -- qe > qb, in order -- instead of one per chained seed with the purged ones marked; the stage then also runs in rounds -- "ext_rounds" (default 1; 0: off): a read's seeds are taken in extension order, tested against the read's surviving alignments first and extended only if they survive, one seed per read and round, after that many rounds everything still ahead at once: the same surviving records, without the banded SW of seeds the purge drops), "gcig_groups" (1, default: CIGAR jobs whose band has at most 16 / 32 / 64 columns run 4 / 2 / 1 to a wavefront with one chunk per row; 0: one wavefront per job in 64-column chunks; any other value: MEME_E_ARG), "gcig_zcap" (>= 0: bytes of LDS a CIGAR job keeps for its backtrack matrix or the window it is walked back through; default: chosen per call, 8192 where a typical matrix of the batch fits, else 2048; results do not depend on it), "ext_census" (1: meme_extend_last_batch_host also counts the extension jobs whose query is a prefix of its target), "max_batch" (> 0: meme_extend_last_batch_host / meme_global_batch_host refuse larger batches with MEME_E_CAPACITY), "ext_slab_jobs" (default 8 Mi, at least 1: the extension stage poses and aligns its jobs in slabs of whole reads with at most this many jobs per side, and at least one read, each -- a bound, and how the tests reach the multi-slab path; same records), "ext_split" (default 1: the extension stage's kernels that walk a read's chains run eight lanes per read for reads with at most 8 chained seeds and a wavefront per read for the others; 0: a wavefront per read throughout; same records), "bsw_circ" (default 1: the lane-per-pair banded-SW kernel keeps the columns of queries longer than its band in a ring of 2w + 2 columns -- same results, more wavefronts per CU; 0: one LDS word per query column as before), "sam_max_batch" (> 0: meme_sam_format_batch_host refuses more record slots than this with MEME_E_CAPACITY; the caller formats in pieces), "helper_blocks" (> 0: at most this many workgroups in the read packer, the offsets scan and the hit gather of a seeding call, as "seed_blocks" does for the search kernel -- how the tests drive their loops round with small batches; 0, default: no cap; same results), "primary_split" (default 8, its maximum: meme_primary_batch_host / _device run reads with at most this many records eight lanes to a read with the records in registers, reads with more a wavefront each with the records in HBM; 0 sends every non-empty read to the wavefront tier; larger values count as 8; same results), "primary_blocks" (> 0: at most this many workgroups in each kernel of that stage, so that a small batch goes round their grid-stride loops; 0, default: no cap; same results), "finish_blocks" (> 0: the same cap for the kernels of meme_finish_batch_host / _device; 0, default: no cap; same results), "finish_lds_recs" (> 0: reads handed over with more records than this are walked by the wavefront tier of that stage in a workspace in HBM instead of in LDS; 0, default, and anything above it: 128; same results), "pair_split" (default 8, its maximum: meme_pair_batch_host / _device run pairs with at most this many keys -- records of both ends that take part -- eight lanes to a pair with the keys in registers, pairs with more a wavefront each; 0 sends every non-empty pair to the wavefront tier; larger values count as 8; same results), "pair_blocks" (> 0: at most this many workgroups in each kernel of that stage; 0, default: no cap; same results), "pair_lds_keys" (> 0: the wavefront tier keeps this many of a pair's sorted keys in LDS and the rest in a workspace in HBM; 0, default, and anything above it: 512; same results) */
 
 /* Debug: the packed image of the last seeded batch (what the search kernels read), copied to the host.  Per read `stride` 64-bit
  * words: fw[W] rc[W] nfw[MW] nrc[MW] len | hasN << 31 (2 bits per base, first base in the top bits, N packed as A; mask bit j of word m =
