@@ -1,8 +1,10 @@
-// What the two record stages (record finishing, meme_finish.hip; primary marking, meme_primary.hip) share of their plumbing: an alignment record in
-// registers, a read's span of the record array, and the argument checks of their host and device forms.  Nothing here decides a result.
+// What the record stages (record finishing, meme_finish.hip; primary marking, meme_primary.hip; pair scoring, meme_pair.hip) share of their plumbing: an
+// alignment record in registers, a read's span of the record array, the argument checks of their host and device forms, the steps of a host form around its
+// launch (upload, reserve, download, timing) and the clamps of their tuning keys.  Nothing here decides a result.
 #pragma once
 #include <limits.h>
 #include <stddef.h>
+#include <initializer_list>
 
 #include "meme_common.h"
 
@@ -68,3 +70,51 @@ inline int reg_check_device(const char* who, bool rest, const meme_alnreg* d_reg
     if (((uintptr_t)d_regs | (uintptr_t)d_regs_out) & 15) { meme_set_error("%s: the record arrays must be 16-byte aligned", who); return MEME_E_ARG; }
     return MEME_OK;
 }
+
+// ---- the steps of a host form: check, prepare, upload, reserve, launch, download, fill the result.  Every reserve of a call stands before its first launch, so
+// a capacity refusal comes before any work; every copy goes from or to memory that outlives the call (the caller's arrays, pinned buffers of the ctx) ----
+// upload: the records on their way into the stage's d_regs / d_reg_off; *total = the records.  reg_upload_host checks them first (reg_check_host); a stage with checks of
+// its own between the two (pair scoring's n_pri) calls both: nothing is copied from the caller's arrays before the last check that can refuse them
+inline int reg_upload(meme_ctx* ctx, const meme_alnreg* regs, const int64_t* reg_off, i64 nreads, DevBuf& d_regs, DevBuf& d_reg_off, i64* total) {
+    *total = reg_off[nreads];
+    const size_t rbytes = (size_t)*total * sizeof(meme_alnreg), obytes = (size_t)(nreads + 1) * 8;
+    int rc;
+    if ((rc = meme_buf_reserve(ctx, d_regs, rbytes + 64)) || (rc = meme_buf_reserve(ctx, d_reg_off, obytes))) return rc;
+    if (*total) HIP_TRY(hipMemcpyAsync(d_regs.p, regs, rbytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_reg_off.p, reg_off, obytes, hipMemcpyHostToDevice, ctx->stream));
+    return MEME_OK;
+}
+inline int reg_upload_host(meme_ctx* ctx, const char* who, const meme_alnreg* regs, const int64_t* reg_off, i64 nreads, DevBuf& d_regs, DevBuf& d_reg_off, i64* total) {
+    const int rc = reg_check_host(who, regs, reg_off, nreads);
+    return rc ? rc : reg_upload(ctx, regs, reg_off, nreads, d_regs, d_reg_off, total);
+}
+// the stage's device buffers of a call: each at least `bytes` and 64 more
+struct DevNeed { DevBuf& buf; size_t bytes; };
+inline int reg_reserve(meme_ctx* ctx, std::initializer_list<DevNeed> needs) {
+    for (const DevNeed& n : needs) if (int rc = meme_buf_reserve(ctx, n.buf, n.bytes + 64)) return rc;
+    return MEME_OK;
+}
+// download: `bytes` of `from` into the pinned `to`, in two steps around the launch -- the host buffers reserved (64 bytes more each), then the copies issued (none of 0 bytes)
+struct Download { HostBuf& to; const DevBuf& from; size_t bytes; };
+inline int reg_download_reserve(meme_ctx* ctx, std::initializer_list<Download> list) {
+    for (const Download& d : list) if (int rc = meme_hostbuf_reserve(ctx, d.to, d.bytes + 64)) return rc;
+    return MEME_OK;
+}
+inline int reg_download(meme_ctx* ctx, std::initializer_list<Download> list) {
+    for (const Download& d : list) if (d.bytes) HIP_TRY(hipMemcpyAsync(d.to.p, d.from.p, d.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return MEME_OK;
+}
+// timing: ctx->stream synchronised (what was downloaded is there), then the GPU time between the stage's two events
+inline int reg_sync_ms(meme_ctx* ctx, Events<2>& ev, float* ms) {
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipEventElapsedTime(ms, ev[0], ev[1]));
+    return MEME_OK;
+}
+
+// ---- tuning keys of the stages ----
+// *_lds_recs, *_lds_keys: 0 and anything above the maximum mean the maximum
+inline int tune_at_most(i64 v, int most) { return (int)(v > 0 && v < most ? v : most); }
+// *_split: clamped to [0, g], the lanes of the light tier's group
+inline int tune_split(i64 v, int g) { return (int)(v < 0 ? 0 : v > g ? g : v); }
+// *_blocks: > 0 caps the grids, else 256 x 64 (grid_blocks' own cap)
+inline i64 tune_grid_cap(i64 blocks) { return blocks > 0 ? blocks : 256 * 64; }

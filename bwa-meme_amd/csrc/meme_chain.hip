@@ -1198,9 +1198,8 @@ int meme_chain_run(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs,
     const i64 n = ctx->batch.last_seed_reads;
     ChainWs& C = ctx->chain;
     int rc;
-    std::vector<unsigned char> tab;
-    ContigTab ct(nullptr, 0, true);
-    if ((rc = meme_stage_contigs(ctx, C.contigs, tab, contigs, n_contigs, opt->l_pac, true, "", &ct))) return rc;
+    ContigTab ct(nullptr, 0);
+    if ((rc = meme_contigs(ctx, "", contigs, n_contigs, opt->l_pac, &ct))) return rc;
     // however this function is left (the error returns below included), the kernels on the side streams have finished: a caller that
     // retries with a smaller batch or destroys the ctx must not race them
     struct SideGuard { meme_ctx* c; ~SideGuard() { for (Stream& st : c->side.st) if (st.s) (void)hipStreamSynchronize(st); } } side_guard{ctx};
@@ -1232,7 +1231,7 @@ int meme_chain_run(meme_ctx* ctx, const meme_contig* contigs, int32_t n_contigs,
                        L.cls, cc.route, L.list[0], L.work[0], L.list[1], L.work[1], L.list[2], L.work[2]);
     unsigned long long h_cnt[3] = {0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h_cnt, cc.route, 24, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                           // (also: `tab` is a local)
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < 3; ++k) T[k].n = (i64)h_cnt[k];
     // ---- four launches at once: the routed tiers, then the lane tier
     if ((rc = run_tiers(ctx, A, L, T, 3, true))) return rc;

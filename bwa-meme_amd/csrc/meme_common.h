@@ -86,9 +86,9 @@ struct Carve {
     template <class T> T* take(size_t count, size_t align = 1) { bytes = (bytes + align - 1) / align * align; T* q = base ? (T*)(base + bytes) : nullptr; bytes += count * sizeof(T); return q; }
     i64* col(i64 n) { return take<i64>((size_t)n + 1); }   // one column of n + 1 values
 };
-struct ContigTab {     // chaining and mate rescue: offset[n], len[n], is_alt[n] (chaining only), 64 bytes of padding
+struct ContigTab {     // ContigCache::dev: offset[n], len[n], is_alt[n] (chaining and record finishing read it), 64 bytes of padding
     i64* off; int* len; unsigned char* alt; size_t bytes;
-    ContigTab(void* base, i64 n, bool with_alt) { Carve c(base); off = c.take<i64>(n); len = c.take<int>(n); alt = c.take<unsigned char>((with_alt ? n : 0) + 64); bytes = c.bytes; }
+    ContigTab(void* base, i64 n) { Carve c(base); off = c.take<i64>(n); len = c.take<int>(n); alt = c.take<unsigned char>(n + 64); bytes = c.bytes; }
 };
 struct ChainCounts {   // per read, then the reads each wavefront launch takes (5 counters)
     i64 *chain_off, *seed_off, *nch, *nsd; int* tree; unsigned char* fb; unsigned long long* route; size_t bytes;
@@ -167,7 +167,7 @@ struct SeedWs {
     Stream emit; Events<2> emit_ev;    // k_reseed_emit runs beside the blocked regions' rounds: its stream, fork [0] and join [1]
 };
 struct ChainWs {
-    DevBuf ch1, sd1, hdr, frac, contigs, counts, chains, seeds, lists;   // lane-tier chains / seeds, read headers, frac_rep, ContigTab, ChainCounts, packed chains / seeds, ChainLists
+    DevBuf ch1, sd1, hdr, frac, counts, chains, seeds, lists;            // lane-tier chains / seeds, read headers, frac_rep, ChainCounts, packed chains / seeds, ChainLists
     DevBuf wave[5];                                                       // scratch sets of the five wavefront launches
     HostBuf h_chain_off, h_chains, h_seed_off, h_seeds, h_tree, h_frac, h_fallback;
     Events<5> ev;
@@ -188,8 +188,8 @@ struct GcigWs {        // cols: GcigCols; cig: CIGAR scratch, ops: packed; nm: n
 struct KswvWs {        // mate rescue poses into jobs, ref and qer; k_kswv reads them
     DevBuf jobs, order, ref, qer, res, rowmax, rm_off; HostBuf h_res; Events<2> ev;
 };
-struct MateWs {        // contigs: ContigTab; counts: MateCounts; batch_off: gar and job offsets of the worker batches
-    DevBuf regs, reg_off, contigs, counts, gar, aux, batch_off; HostBuf h_gar, h_batch_off, h_jobs;
+struct MateWs {        // counts: MateCounts; batch_off: gar and job offsets of the worker batches
+    DevBuf regs, reg_off, counts, gar, aux, batch_off; HostBuf h_gar, h_batch_off, h_jobs;
 };
 struct SamWs {         // cols: SamCols; contigs: contig name offsets + names + read group
     DevBuf names, name_off, quals, recs, blob, cols, scratch, text, contigs; HostBuf h_text_off, h_text; Events<2> ev;
@@ -202,19 +202,26 @@ struct PrimaryWs {     // regs / reg_off / out / n_pri / mapq / status: the host
 };
 
 struct PairWs {        // regs / reg_off / n_pri / res / status / counter: the host form's staging (res: score, sub, n_sub, n_cand and z, six ints a pair); keys: a heavy pair's sorted keys
-                       // behind the LDS cap; list: the heavy pairs; tab: PairDirs and the penalty table, h_tab what it is copied from (tab_ev: the copy has passed); contigs: ContigTab,
-                       // h_contigs what it was staged from (restaged only when it changes)
-    DevBuf regs, reg_off, n_pri, res, status, counter, keys, list, tab, contigs; HostBuf h_res, h_status, h_tab; Events<2> ev; Events<1> tab_ev;
+                       // behind the LDS cap; list: the heavy pairs; tab: PairDirs and the penalty table, h_tab what it is copied from (tab_ev: the copy has passed)
+    DevBuf regs, reg_off, n_pri, res, status, counter, keys, list, tab; HostBuf h_res, h_status, h_tab; Events<2> ev; Events<1> tab_ev;
     bool tab_in_flight = false;
-    std::vector<unsigned char> h_contigs; std::vector<meme_contig> last_contigs; i64 last_l_pac = -1;
 };
 
 struct FinishWs {      // regs / reg_off / out / reg_off_out / ums / status / counters: the host form's staging; stage: the records a read keeps, at the read's input offsets, before the
                        // pack; cnt: records kept per read; live / first: live records of a read and the first of them; list: the wavefront tier's reads; cols_l / cols_c: the
-                       // columns of reads too large for LDS; contigs: ContigTab, h_contigs what it was staged from (restaged only when it changes)
-    DevBuf regs, reg_off, out, reg_off_out, ums, status, counters, stage, cnt, live, first, list, cols_l, cols_c, contigs;
+                       // columns of reads too large for LDS
+    DevBuf regs, reg_off, out, reg_off_out, ums, status, counters, stage, cnt, live, first, list, cols_l, cols_c;
     HostBuf h_regs, h_reg_off, h_ums, h_status; Events<2> ev;
-    std::vector<unsigned char> h_contigs; std::vector<meme_contig> last_contigs; i64 last_l_pac = -1;
+};
+
+// The contig table of a ctx (meme_contigs): one for every stage that takes contigs -- chaining and extension, mate rescue, record finishing, pair scoring.
+// dev: ContigTab; host: the pinned image it was copied from; from / l_pac: the caller's array and genome length it was built from (l_pac -1: nothing valid).
+// Invariant: dev is only ever overwritten by a copy on ctx->stream issued after that stream has been synchronised, and that copy has passed before meme_contigs
+// returns; every kernel that reads dev runs on ctx->stream, or on a side stream that its call joins before it returns (SideGuard in meme_chain_run).  So a
+// new table never meets a reader of the old one, and host is idle whenever it is rewritten.  A ctx is driven by one host thread at a time.
+struct ContigCache {
+    DevBuf dev; HostBuf host;
+    std::vector<meme_contig> from; i64 l_pac = -1;
 };
 
 struct SideStreams {   // beside ctx->stream: the routed chaining tiers, the early overflow tier of seeding (meme_side_stream creates stream i with its event)
@@ -233,6 +240,9 @@ struct meme_ctx {
     // workspaces (scan_tmp: tiles of the prefix sums, meme_scan_exclusive and the seeding gather)
     ResidentBatch batch;
     DevBuf scan_tmp;
+    ContigCache contigs;
+    HostBuf h_ctr;                     // where a call's counters land on the host, read behind the call's own synchronise (never a stack variable: an error return
+                                       // between the copy and the synchronise would leave the copy writing into a dead frame)
     ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam; PrimaryWs primary; PairWs pair; FinishWs finish; SeedWs seed;
     // Streams.  Order of destruction: meme_ctx_destroy synchronises every stream of the ctx; then the members go in reverse order of declaration, so the streams
     // and their fork / join events -- these two and, last member of the last workspace, the seeding stage's -- are destroyed BEFORE any DevBuf / HostBuf above is
@@ -285,10 +295,10 @@ int meme_side_stream(meme_ctx* ctx, int i);
 int meme_hostbuf_reserve(meme_ctx* ctx, HostBuf& b, size_t bytes);
 // workgroups of a grid-stride launch over `items`, `per` to a workgroup: at least one, at most `cap` (256 x 64: 64 per CU of a 256-CU device)
 inline unsigned grid_blocks(i64 items, int per, i64 cap = 256 * 64) { i64 b = (items + per - 1) / per; return (unsigned)(b < cap ? (b < 1 ? 1 : b) : cap); }
-// the contigs checked (ascending, inside the forward strand of an l_pac-base genome; the error message starts with `prefix`) and staged into `buf` as a
-// ContigTab through `host`, which the caller keeps until its stream has passed the copy
-int meme_stage_contigs(meme_ctx* ctx, DevBuf& buf, std::vector<unsigned char>& host, const meme_contig* contigs, int32_t n_contigs, i64 l_pac, bool with_alt,
-                       const char* prefix, ContigTab* out);
+// the ctx's contig table for these contigs (ContigCache).  The array and l_pac of the call before: the resident table, no copy, no synchronisation.  Anything else:
+// ctx->stream synchronised, the contigs checked (ascending, inside the forward strand of an l_pac-base genome; the error message starts with `prefix`), staged,
+// synchronised again, remembered.  After a refusal nothing is remembered: the next call checks again.
+int meme_contigs(meme_ctx* ctx, const char* prefix, const meme_contig* contigs, int32_t n_contigs, i64 l_pac, ContigTab* out);
 // exclusive prefix sum of n 64-bit counts into out[0..n] (out[n] = total), asynchronous on ctx->stream (meme_scan.hip)
 int meme_scan_exclusive(meme_ctx* ctx, const i64* d_in, i64* d_out, i64 n);
 // the same, and the total on its way to *h_total (an asynchronous 8-byte copy: the caller synchronises ctx->stream before reading it)

@@ -101,22 +101,31 @@ extern "C" void meme_ctx_destroy(meme_ctx* ctx) {
     delete ctx;
 }
 
-int meme_stage_contigs(meme_ctx* ctx, DevBuf& buf, std::vector<unsigned char>& host, const meme_contig* contigs, int32_t n_contigs, i64 l_pac, bool with_alt,
-                       const char* prefix, ContigTab* out) {
+int meme_contigs(meme_ctx* ctx, const char* prefix, const meme_contig* contigs, int32_t n_contigs, i64 l_pac, ContigTab* out) {
+    ContigCache& K = ctx->contigs;
+    if (K.dev.p && K.l_pac == l_pac && (i64)K.from.size() == n_contigs && (n_contigs == 0 || !memcmp(K.from.data(), contigs, (size_t)n_contigs * sizeof(meme_contig)))) {
+        *out = ContigTab(K.dev.p, n_contigs);
+        return MEME_OK;
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));          // (the readers of the table before this one, and its copy, are over: dev and host may change)
+    K.l_pac = -1;
     for (int i = 0; i < n_contigs; ++i)            // bntann1_t: 64-bit offset, 32-bit length; ascending, inside the forward strand
         if (contigs[i].len < 1 || contigs[i].offset < 0 || contigs[i].offset + contigs[i].len > l_pac || (i > 0 && contigs[i].offset < contigs[i - 1].offset + contigs[i - 1].len)) {
             meme_set_error("%scontig %d (offset %lld, length %d) is not a valid reference sequence of a %lld-base genome", prefix, i, (long long)contigs[i].offset, contigs[i].len,
                            (long long)l_pac);
             return MEME_E_ARG;
         }
-    const size_t bytes = ContigTab(nullptr, n_contigs, with_alt).bytes;
-    int rc = meme_buf_reserve(ctx, buf, bytes);
-    if (rc) return rc;
-    host.assign(bytes, 0);
-    ContigTab t(host.data(), n_contigs, with_alt);
-    for (int i = 0; i < n_contigs; ++i) { t.off[i] = contigs[i].offset; t.len[i] = contigs[i].len; if (with_alt) t.alt[i] = contigs[i].is_alt ? 1 : 0; }
-    HIP_TRY(hipMemcpyAsync(buf.p, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-    *out = ContigTab(buf.p, n_contigs, with_alt);
+    const size_t bytes = ContigTab(nullptr, n_contigs).bytes;
+    int rc;
+    if ((rc = meme_buf_reserve(ctx, K.dev, bytes)) || (rc = meme_hostbuf_reserve(ctx, K.host, bytes))) return rc;
+    memset(K.host.p, 0, bytes);
+    const ContigTab t(K.host.p, n_contigs);
+    for (int i = 0; i < n_contigs; ++i) { t.off[i] = contigs[i].offset; t.len[i] = contigs[i].len; t.alt[i] = contigs[i].is_alt ? 1 : 0; }
+    HIP_TRY(hipMemcpyAsync(K.dev.p, K.host.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    K.from.assign(contigs, contigs + n_contigs);
+    K.l_pac = l_pac;
+    *out = ContigTab(K.dev.p, n_contigs);
     return MEME_OK;
 }
 

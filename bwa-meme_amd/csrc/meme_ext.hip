@@ -529,7 +529,7 @@ int ext_begin(ExtRun& R) {
     if ((rc = meme_buf_reserve(ctx, E.counters, EXT_CTR_BYTES))) return rc;
     R.ctr = E.counters.as<unsigned long long>();
     R.h_flt[0] = R.n_seeds;
-    const ContigTab ct(C.contigs.p, R.n_contigs, true);
+    const ContigTab ct(ctx->contigs.dev.p, R.n_contigs);      // (meme_chain_run has just asked for it: the table of this call's contigs)
     ExtArgs& A = R.A;
     memset(&A, 0, sizeof(A));
     A.reads = ctx->batch.reads.as<const uint8_t>(); A.read_off = ctx->batch.read_off.as<const i64>(); A.g0 = 0; A.ns = R.n;

@@ -228,18 +228,7 @@ int finish_prepare(meme_ctx* ctx, const char* who, i64 nreads, const meme_contig
     }
     if (nreads > ctx->batch.last_seed_reads) { meme_set_error("%s: %lld reads, the batch on the ctx has %lld", who, (long long)nreads, (long long)ctx->batch.last_seed_reads); return MEME_E_ARG; }
     if (n_contigs < 0 || (n_contigs > 0 && !contigs) || 2 * l_pac != ctx->idx.n) { meme_set_error("%s: null contigs, or l_pac is not the index's (%lld)", who, (long long)(ctx->idx.n >> 1)); return MEME_E_ARG; }
-    FinishWs& F = ctx->finish;
-    const bool same = F.contigs.p && F.last_l_pac == l_pac && (i64)F.last_contigs.size() == n_contigs &&
-                      (n_contigs == 0 || !memcmp(F.last_contigs.data(), contigs, (size_t)n_contigs * sizeof(meme_contig)));
-    if (same) { *ct = ContigTab(F.contigs.p, n_contigs, true); return MEME_OK; }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));          // (h_contigs is about to change: the copy of the table before this one has to be over)
-    F.last_l_pac = -1;
-    int rc = meme_stage_contigs(ctx, F.contigs, F.h_contigs, contigs, n_contigs, l_pac, true, (std::string(who) + ": ").c_str(), ct);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    F.last_contigs.assign(contigs, contigs + n_contigs);
-    F.last_l_pac = l_pac;
-    return MEME_OK;
+    return meme_contigs(ctx, (std::string(who) + ": ").c_str(), contigs, n_contigs, l_pac, ct);
 }
 
 // the stage's kernels on device arrays, asynchronous on ctx->stream; ev: recorded around them
@@ -256,11 +245,11 @@ int finish_launch(meme_ctx* ctx, const meme_alnreg* d_regs, const i64* d_reg_off
     A.in = d_regs; A.reg_off = d_reg_off; A.nreads = nreads; A.total_regs = total_regs;
     A.reads = (const uint8_t*)ctx->batch.reads.p; A.read_off = (const i64*)ctx->batch.read_off.p; A.pac = ctx->idx.pac; A.l_pac = l_pac;
     A.alt = ct.alt; A.n_contigs = n_contigs; A.o = *opt;
-    A.lds_recs = (int)(ctx->finish_lds_recs > 0 && ctx->finish_lds_recs < FIN_LDS_RECS ? ctx->finish_lds_recs : FIN_LDS_RECS);
+    A.lds_recs = tune_at_most(ctx->finish_lds_recs, FIN_LDS_RECS);
     A.stage = (meme_alnreg*)F.stage.p; A.cnt = (i64*)F.cnt.p; A.live = (int*)F.live.p; A.first = (int*)F.first.p; A.ums = o->d_use_mate_sort; A.status = o->d_status;
     A.list = (i64*)F.list.p; A.ctr = (unsigned long long*)o->d_counters; A.cols_l = (long long*)F.cols_l.p; A.cols_c = (int*)F.cols_c.p;
     A.out = o->d_regs_out; A.off_out = o->d_reg_off_out;
-    const i64 cap = ctx->finish_blocks > 0 ? ctx->finish_blocks : 256 * 64;
+    const i64 cap = tune_grid_cap(ctx->finish_blocks);
     HIP_TRY(hipEventRecord(F.ev[0], ctx->stream));
     HIP_TRY(hipMemsetAsync(o->d_counters, 0, FIN_CTRS * 8, ctx->stream));
     hipLaunchKernelGGL(k_finish_route, dim3(grid_blocks(nreads, 256, cap)), dim3(256), 0, ctx->stream, A);
@@ -283,7 +272,7 @@ extern "C" int meme_finish_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs
     int rc;
     if ((rc = reg_check_device(who, rest, d_regs, out ? out->d_regs_out : nullptr, d_reg_off, nreads, total_regs)) || (rc = finish_check_opt(who, opt))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    ContigTab ct(nullptr, 0, true);
+    ContigTab ct(nullptr, 0);
     if ((rc = finish_prepare(ctx, who, nreads, contigs, n_contigs, l_pac, &ct))) return rc;
     if (nreads == 0) {
         HIP_TRY(hipMemsetAsync(out->d_counters, 0, FIN_CTRS * 8, ctx->stream));
@@ -301,38 +290,31 @@ extern "C" int meme_finish_batch_host(meme_ctx* ctx, const meme_alnreg* regs, co
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     memset(out, 0, sizeof(*out));
-    ContigTab ct(nullptr, 0, true);
+    ContigTab ct(nullptr, 0);
     if ((rc = finish_prepare(ctx, who, nreads, contigs, n_contigs, l_pac, &ct))) return rc;
     FinishWs& F = ctx->finish;
-    if ((rc = meme_hostbuf_reserve(ctx, F.h_reg_off, (size_t)(nreads + 1) * 8))) return rc;
+    if ((rc = meme_hostbuf_reserve(ctx, F.h_reg_off, (size_t)(nreads + 1) * 8 + 64))) return rc;      // (an empty call has offsets too: one 0)
     out->reg_off = (const int64_t*)F.h_reg_off.p;
     ((i64*)F.h_reg_off.p)[0] = 0;
     if (nreads == 0) return MEME_OK;
-    if ((rc = reg_check_host(who, regs, reg_off, nreads))) return rc;
-    const i64 total = reg_off[nreads];
+    i64 total;
+    if ((rc = reg_upload_host(ctx, who, regs, reg_off, nreads, F.regs, F.reg_off, &total))) return rc;
     const size_t rbytes = (size_t)total * sizeof(meme_alnreg);
-    if ((rc = meme_buf_reserve(ctx, F.regs, rbytes + 64)) || (rc = meme_buf_reserve(ctx, F.out, rbytes + 64)) || (rc = meme_buf_reserve(ctx, F.reg_off, (size_t)(nreads + 1) * 8)) ||
-        (rc = meme_buf_reserve(ctx, F.reg_off_out, (size_t)(nreads + 1) * 8)) || (rc = meme_buf_reserve(ctx, F.ums, (size_t)nreads + 64)) || (rc = meme_buf_reserve(ctx, F.status, (size_t)nreads + 64)) ||
-        (rc = meme_buf_reserve(ctx, F.counters, FIN_CTRS * 8)) || (rc = meme_hostbuf_reserve(ctx, F.h_regs, rbytes + 64)) || (rc = meme_hostbuf_reserve(ctx, F.h_ums, (size_t)nreads + 64)) ||
-        (rc = meme_hostbuf_reserve(ctx, F.h_status, (size_t)nreads + 64))) return rc;
-    if (total) HIP_TRY(hipMemcpyAsync(F.regs.p, regs, rbytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(F.reg_off.p, reg_off, (size_t)(nreads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    const Download offs = {F.h_reg_off, F.reg_off_out, (size_t)(nreads + 1) * 8}, ums = {F.h_ums, F.ums, (size_t)nreads}, status = {F.h_status, F.status, (size_t)nreads},
+                   ctrs = {ctx->h_ctr, F.counters, FIN_CTRS * 8}, recs = {F.h_regs, F.out, rbytes};
+    if ((rc = reg_reserve(ctx, {{F.out, rbytes}, {F.reg_off_out, offs.bytes}, {F.ums, ums.bytes}, {F.status, status.bytes}, {F.counters, ctrs.bytes}})) ||
+        (rc = reg_download_reserve(ctx, {offs, ums, status, ctrs, recs}))) return rc;
     const meme_finish_device_out d = {(meme_alnreg*)F.out.p, (int64_t*)F.reg_off_out.p, (uint8_t*)F.ums.p, (uint8_t*)F.status.p, (uint64_t*)F.counters.p};
     if ((rc = finish_launch(ctx, (const meme_alnreg*)F.regs.p, (const i64*)F.reg_off.p, nreads, total, ct, n_contigs, l_pac, opt, &d))) return rc;
-    unsigned long long ctr[FIN_CTRS] = {};
-    HIP_TRY(hipMemcpyAsync(F.h_reg_off.p, F.reg_off_out.p, (size_t)(nreads + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(F.h_ums.p, F.ums.p, (size_t)nreads, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(F.h_status.p, F.status.p, (size_t)nreads, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctr, F.counters.p, sizeof(ctr), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    if ((rc = reg_download(ctx, {offs, ums, status, ctrs})) || (rc = reg_sync_ms(ctx, F.ev, &ms))) return rc;
     const i64 left = ((const i64*)F.h_reg_off.p)[nreads];
     if (left < 0 || left > total) { meme_set_error("%s: the stage left %lld records of %lld", who, (long long)left, (long long)total); return MEME_E_HIP; }
-    if (left) {
-        HIP_TRY(hipMemcpyAsync(F.h_regs.p, F.out.p, (size_t)left * sizeof(meme_alnreg), hipMemcpyDeviceToHost, ctx->stream));
+    if (left) {                                                // (what the stage kept: known only now)
+        if ((rc = reg_download(ctx, {{F.h_regs, F.out, (size_t)left * sizeof(meme_alnreg)}}))) return rc;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, F.ev[0], F.ev[1]));
+    const unsigned long long* ctr = (const unsigned long long*)ctx->h_ctr.p;
     out->nreads = nreads; out->total_regs = left; out->regs = (const meme_alnreg*)F.h_regs.p; out->use_mate_sort = (const uint8_t*)F.h_ums.p; out->status = (const uint8_t*)F.h_status.p;
     out->n_wave = (i64)ctr[FIN_CTR_WAVE]; out->n_patch_jobs = (i64)ctr[FIN_CTR_JOBS]; out->n_patched = (i64)ctr[FIN_CTR_MERGED]; out->kernel_ms = ms;
     return MEME_OK;

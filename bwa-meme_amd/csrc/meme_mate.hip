@@ -139,10 +139,9 @@ extern "C" int meme_matesw_batch_host(meme_ctx* ctx, meme_ctx* reads_of, const m
     const i64 n = nreads, nb = (n + opt->batch_reads - 1) / opt->batch_reads;
     int rc;
     MateWs& M = ctx->mate;
-    std::vector<unsigned char> tab;
-    ContigTab ct(nullptr, 0, false);
-    if ((rc = meme_stage_contigs(ctx, M.contigs, tab, contigs, n_contigs, l_pac, false, "meme_matesw_batch_host: ", &ct))) return rc;
-    if ((rc = meme_buf_reserve(ctx, M.regs, (size_t)(nrec + 1) * sizeof(meme_mate_reg))) || (rc = meme_buf_reserve(ctx, M.reg_off, (size_t)(n + 1) * 8)) ||
+    ContigTab ct(nullptr, 0);
+    if ((rc = meme_contigs(ctx, "meme_matesw_batch_host: ", contigs, n_contigs, l_pac, &ct))) return rc;
+    if ((rc = meme_hostbuf_reserve(ctx, ctx->h_ctr, 4 * 8)) || (rc = meme_buf_reserve(ctx, M.regs, (size_t)(nrec + 1) * sizeof(meme_mate_reg))) || (rc = meme_buf_reserve(ctx, M.reg_off, (size_t)(n + 1) * 8)) ||
         (rc = meme_buf_reserve(ctx, M.counts, MateCounts(nullptr, n).bytes)) || (rc = meme_buf_reserve(ctx, M.batch_off, (size_t)(nb + 1) * 16))) return rc;
     Events<2>& ev = ctx->kswv.ev;
     HIP_TRY(ev.ensure());
@@ -159,9 +158,9 @@ extern "C" int meme_matesw_batch_host(meme_ctx* ctx, meme_ctx* reads_of, const m
     HIP_TRY(hipEventRecord(ev[0], ctx->stream));
     hipLaunchKernelGGL((k_mate_plan<false>), dim3(grid_blocks(n, 256, 256 * 32)), dim3(256), 0, ctx->stream, A);
     for (int k = 0; k < 4; ++k) if ((rc = meme_scan_exclusive(ctx, mc.cntQ + k * (n + 1), mc.offQ + k * (n + 1), n))) return rc;
-    i64 tot[4] = {0, 0, 0, 0};
-    for (int k = 0; k < 4; ++k) HIP_TRY(hipMemcpyAsync(&tot[k], mc.offQ + k * (n + 1) + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                                       // (also: `tab` is a local)
+    const i64* tot = (const i64*)ctx->h_ctr.p;                                        // the four scans' totals
+    for (int k = 0; k < 4; ++k) HIP_TRY(hipMemcpyAsync(ctx->h_ctr.as<i64>() + k, mc.offQ + k * (n + 1) + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     const i64 nq = tot[0], nj = tot[1], ref_bytes = tot[2], qer_bytes = tot[3];
     if (nj > 0x7fffffff / 2 || 4 * nq > 0x7fffffff) { meme_set_error("%s: too many jobs in one call", who); return MEME_E_CAPACITY; }
     KswvWs& K = ctx->kswv;        // (k_kswv's jobs and sequences: written here, read there)

@@ -19,6 +19,7 @@
 // orientations that have not failed (the device's erfc and log are not glibc's): the device adds, compares and truncates.
 #include <math.h>
 #include <string.h>
+#include <string>
 
 #include "meme_common.h"
 #include "meme_alnreg_words.h"
@@ -230,7 +231,7 @@ __global__ void __launch_bounds__(64) k_pair_heavy(PairArgs A) {
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-// what both forms check and stage for the kernels: the options, the contigs (restaged only when they change), the orientations and their penalty table
+// what both forms check and stage for the kernels: the options, the contigs, the orientations and their penalty table
 int pair_prepare(meme_ctx* ctx, const char* who, i64 nreads, const meme_contig* contigs, int32_t n_contigs, i64 l_pac, const meme_pair_pes* pes, const meme_pair_opt* opt,
                  ContigTab* ct) {
     if (nreads & 1) { meme_set_error("%s: %lld reads are no pairs", who, (long long)nreads); return MEME_E_ARG; }
@@ -250,17 +251,7 @@ int pair_prepare(meme_ctx* ctx, const char* who, i64 nreads, const meme_contig* 
     }
     PairWs& P = ctx->pair;
     int rc;
-    const bool same = P.contigs.p && P.last_l_pac == l_pac && (i64)P.last_contigs.size() == n_contigs &&
-                      (n_contigs == 0 || !memcmp(P.last_contigs.data(), contigs, (size_t)n_contigs * sizeof(meme_contig)));
-    if (same) *ct = ContigTab(P.contigs.p, n_contigs, false);
-    else {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));          // (h_contigs is about to change: the copy of the table before this one has to be over)
-        P.last_l_pac = -1;
-        if ((rc = meme_stage_contigs(ctx, P.contigs, P.h_contigs, contigs, n_contigs, l_pac, false, (std::string(who) + ": ").c_str(), ct))) return rc;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        P.last_contigs.assign(contigs, contigs + n_contigs);
-        P.last_l_pac = l_pac;
-    }
+    if ((rc = meme_contigs(ctx, (std::string(who) + ": ").c_str(), contigs, n_contigs, l_pac, ct))) return rc;
     // the table: built per call by the host's libm, copied on the ctx's stream from pinned memory that the copy before it has left
     const size_t bytes = PAIR_TAB_HEAD + (size_t)(entries + 1) * 8;
     HIP_TRY(P.tab_ev.ensure());
@@ -292,11 +283,11 @@ int pair_launch(meme_ctx* ctx, const meme_alnreg* d_regs, const i64* d_reg_off, 
     A.contig_off = ct.off; A.n_contigs = n_contigs; A.l_pac = l_pac;
     A.dirs = (const PairDirs*)P.tab.p; A.tab = (const double*)((const unsigned char*)P.tab.p + PAIR_TAB_HEAD); A.id_base = (u64)id_base;
     A.tmp = pair_score_distance(*opt);
-    A.split = (int)(ctx->pair_split < 0 ? 0 : ctx->pair_split > PAIR_G ? PAIR_G : ctx->pair_split);
-    A.lds_keys = (int)(ctx->pair_lds_keys > 0 && ctx->pair_lds_keys < PAIR_LDS_KEYS ? ctx->pair_lds_keys : PAIR_LDS_KEYS);
+    A.split = tune_split(ctx->pair_split, PAIR_G);
+    A.lds_keys = tune_at_most(ctx->pair_lds_keys, PAIR_LDS_KEYS);
     A.score = o->d_score; A.sub = o->d_sub; A.n_sub = o->d_n_sub; A.n_cand = o->d_n_cand; A.z = o->d_z; A.status = o->d_status;
     A.keys = (PairKey*)P.keys.p; A.list = (i64*)P.list.p; A.n_heavy = (unsigned long long*)o->d_n_heavy;
-    const i64 cap = ctx->pair_blocks > 0 ? ctx->pair_blocks : 256 * 64;
+    const i64 cap = tune_grid_cap(ctx->pair_blocks);
     HIP_TRY(hipEventRecord(P.ev[0], ctx->stream));
     HIP_TRY(hipMemsetAsync(o->d_n_heavy, 0, 8, ctx->stream));
     hipLaunchKernelGGL(k_pair_route, dim3(grid_blocks(npairs, 256, cap)), dim3(256), 0, ctx->stream, A);
@@ -320,7 +311,7 @@ extern "C" int meme_pair_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs, 
     }
     if ((uintptr_t)d_regs & 15) { meme_set_error("%s: the record array must be 16-byte aligned", who); return MEME_E_ARG; }
     HIP_TRY(hipSetDevice(ctx->device));
-    ContigTab ct(nullptr, 0, false);
+    ContigTab ct(nullptr, 0);
     int rc;
     if ((rc = pair_prepare(ctx, who, nreads, contigs, n_contigs, l_pac, pes, opt, &ct))) return rc;
     if (nreads == 0) { HIP_TRY(hipMemsetAsync(out->d_n_heavy, 0, 8, ctx->stream)); return MEME_OK; }
@@ -333,7 +324,7 @@ extern "C" int meme_pair_batch_host(meme_ctx* ctx, const meme_alnreg* regs, cons
     if (!ctx || !opt || !pes || !out || nreads < 0 || (nreads > 0 && (!reg_off || !n_pri))) { meme_set_error("%s: null argument", who); return MEME_E_ARG; }
     HIP_TRY(hipSetDevice(ctx->device));
     memset(out, 0, sizeof(*out));
-    ContigTab ct(nullptr, 0, false);
+    ContigTab ct(nullptr, 0);
     int rc;
     if ((rc = pair_prepare(ctx, who, nreads, contigs, n_contigs, l_pac, pes, opt, &ct))) return rc;
     if (nreads == 0) return MEME_OK;
@@ -343,27 +334,21 @@ extern "C" int meme_pair_batch_host(meme_ctx* ctx, const meme_alnreg* regs, cons
             meme_set_error("%s: n_pri of read %lld is %d, the read has %lld records", who, (long long)r, n_pri[r], (long long)(reg_off[r + 1] - reg_off[r]));
             return MEME_E_ARG;
         }
-    const i64 total = reg_off[nreads], npairs = nreads / 2;
     PairWs& P = ctx->pair;
-    const size_t rbytes = (size_t)total * sizeof(meme_alnreg), res_bytes = (size_t)npairs * 6 * 4;
-    if ((rc = meme_buf_reserve(ctx, P.regs, rbytes + 64)) || (rc = meme_buf_reserve(ctx, P.reg_off, (size_t)(nreads + 1) * 8)) || (rc = meme_buf_reserve(ctx, P.n_pri, (size_t)nreads * 4)) ||
-        (rc = meme_buf_reserve(ctx, P.res, res_bytes)) || (rc = meme_buf_reserve(ctx, P.status, (size_t)npairs + 64)) || (rc = meme_buf_reserve(ctx, P.counter, 64)) ||
-        (rc = meme_hostbuf_reserve(ctx, P.h_res, res_bytes)) || (rc = meme_hostbuf_reserve(ctx, P.h_status, (size_t)npairs + 64))) return rc;
-    if (total) HIP_TRY(hipMemcpyAsync(P.regs.p, regs, rbytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(P.reg_off.p, reg_off, (size_t)(nreads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    i64 total;
+    if ((rc = reg_upload(ctx, regs, reg_off, nreads, P.regs, P.reg_off, &total))) return rc;
+    const i64 npairs = nreads / 2;
+    const Download res = {P.h_res, P.res, (size_t)npairs * 6 * 4}, status = {P.h_status, P.status, (size_t)npairs}, ctrs = {ctx->h_ctr, P.counter, 8};
+    if ((rc = reg_reserve(ctx, {{P.n_pri, (size_t)nreads * 4}, {P.res, res.bytes}, {P.status, status.bytes}, {P.counter, ctrs.bytes}})) ||
+        (rc = reg_download_reserve(ctx, {res, status, ctrs}))) return rc;
     HIP_TRY(hipMemcpyAsync(P.n_pri.p, n_pri, (size_t)nreads * 4, hipMemcpyHostToDevice, ctx->stream));
-    int32_t* res = (int32_t*)P.res.p;                          // columns: score, sub, n_sub, n_cand, then z (two a pair)
-    const meme_pair_device_out d = {res, res + npairs, res + 2 * npairs, res + 3 * npairs, res + 4 * npairs, (uint8_t*)P.status.p, (uint64_t*)P.counter.p};
+    int32_t* r = (int32_t*)P.res.p;                            // columns: score, sub, n_sub, n_cand, then z (two a pair)
+    const meme_pair_device_out d = {r, r + npairs, r + 2 * npairs, r + 3 * npairs, r + 4 * npairs, (uint8_t*)P.status.p, (uint64_t*)P.counter.p};
     if ((rc = pair_launch(ctx, (const meme_alnreg*)P.regs.p, (const i64*)P.reg_off.p, (const int32_t*)P.n_pri.p, npairs, total, ct, n_contigs, l_pac, id_base, opt, &d))) return rc;
-    unsigned long long n_heavy = 0;
-    HIP_TRY(hipMemcpyAsync(P.h_res.p, P.res.p, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(P.h_status.p, P.status.p, (size_t)npairs, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&n_heavy, P.counter.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, P.ev[0], P.ev[1]));
+    if ((rc = reg_download(ctx, {res, status, ctrs})) || (rc = reg_sync_ms(ctx, P.ev, &ms))) return rc;
     const int32_t* h = (const int32_t*)P.h_res.p;
     out->npairs = npairs; out->score = h; out->sub = h + npairs; out->n_sub = h + 2 * npairs; out->n_cand = h + 3 * npairs; out->z = h + 4 * npairs;
-    out->status = (const uint8_t*)P.h_status.p; out->n_heavy = (i64)n_heavy; out->kernel_ms = ms;
+    out->status = (const uint8_t*)P.h_status.p; out->n_heavy = (i64)*(const unsigned long long*)ctx->h_ctr.p; out->kernel_ms = ms;
     return MEME_OK;
 }

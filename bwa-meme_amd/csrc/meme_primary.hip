@@ -365,10 +365,10 @@ static int primary_launch(meme_ctx* ctx, const meme_alnreg* d_regs, const i64* d
     PriArgs A;
     A.in = d_regs; A.reg_off = d_reg_off; A.nreads = nreads; A.total_regs = total_regs; A.id_base = (u64)id_base; A.o = *opt;
     A.tmp = pri_score_distance(*opt);
-    A.split = (int)(ctx->primary_split < 0 ? 0 : ctx->primary_split > PRI_G ? PRI_G : ctx->primary_split);
+    A.split = tune_split(ctx->primary_split, PRI_G);
     A.out = o->d_regs_out; A.sorted = (meme_alnreg*)P.sorted.p; A.rank = (int*)P.rank.p; A.n_pri = o->d_n_pri; A.mapq = o->d_mapq; A.status = o->d_status;
     A.list = (i64*)P.list.p; A.n_heavy = (unsigned long long*)o->d_n_heavy; A.logtab = (const double*)P.logtab.p;
-    const i64 cap = ctx->primary_blocks > 0 ? ctx->primary_blocks : 256 * 64;
+    const i64 cap = tune_grid_cap(ctx->primary_blocks);
     HIP_TRY(hipEventRecord(P.ev[0], ctx->stream));
     HIP_TRY(hipMemsetAsync(o->d_n_heavy, 0, 8, ctx->stream));
     hipLaunchKernelGGL(k_primary_route, dim3(grid_blocks(nreads, 256, cap)), dim3(256), 0, ctx->stream, A);
@@ -399,28 +399,18 @@ extern "C" int meme_primary_batch_host(meme_ctx* ctx, const meme_alnreg* regs, c
     HIP_TRY(hipSetDevice(ctx->device));
     memset(out, 0, sizeof(*out));
     if (nreads == 0) return MEME_OK;
-    if ((rc = reg_check_host(who, regs, reg_off, nreads))) return rc;
-    const i64 total = reg_off[nreads];
     PrimaryWs& P = ctx->primary;
-    const size_t rbytes = (size_t)total * sizeof(meme_alnreg);
-    if ((rc = meme_buf_reserve(ctx, P.regs, rbytes + 64)) || (rc = meme_buf_reserve(ctx, P.out, rbytes + 64)) || (rc = meme_buf_reserve(ctx, P.reg_off, (size_t)(nreads + 1) * 8)) ||
-        (rc = meme_buf_reserve(ctx, P.n_pri, (size_t)nreads * 4)) || (rc = meme_buf_reserve(ctx, P.mapq, (size_t)total + 64)) || (rc = meme_buf_reserve(ctx, P.status, (size_t)nreads + 64)) ||
-        (rc = meme_buf_reserve(ctx, P.counter, 64)) || (rc = meme_hostbuf_reserve(ctx, P.h_regs, rbytes + 64)) || (rc = meme_hostbuf_reserve(ctx, P.h_n_pri, (size_t)nreads * 4)) ||
-        (rc = meme_hostbuf_reserve(ctx, P.h_mapq, (size_t)total + 64)) || (rc = meme_hostbuf_reserve(ctx, P.h_status, (size_t)nreads + 64))) return rc;
-    if (total) HIP_TRY(hipMemcpyAsync(P.regs.p, regs, rbytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(P.reg_off.p, reg_off, (size_t)(nreads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    meme_primary_device_out d = {(meme_alnreg*)P.out.p, (int32_t*)P.n_pri.p, (uint8_t*)P.mapq.p, (uint8_t*)P.status.p, (uint64_t*)P.counter.p};
+    i64 total;
+    if ((rc = reg_upload_host(ctx, who, regs, reg_off, nreads, P.regs, P.reg_off, &total))) return rc;
+    const Download recs = {P.h_regs, P.out, (size_t)total * sizeof(meme_alnreg)}, mapq = {P.h_mapq, P.mapq, (size_t)total}, n_pri = {P.h_n_pri, P.n_pri, (size_t)nreads * 4},
+                   status = {P.h_status, P.status, (size_t)nreads}, ctrs = {ctx->h_ctr, P.counter, 8};
+    if ((rc = reg_reserve(ctx, {{P.out, recs.bytes}, {P.n_pri, n_pri.bytes}, {P.mapq, mapq.bytes}, {P.status, status.bytes}, {P.counter, ctrs.bytes}})) ||
+        (rc = reg_download_reserve(ctx, {recs, mapq, n_pri, status, ctrs}))) return rc;
+    const meme_primary_device_out d = {(meme_alnreg*)P.out.p, (int32_t*)P.n_pri.p, (uint8_t*)P.mapq.p, (uint8_t*)P.status.p, (uint64_t*)P.counter.p};
     if ((rc = primary_launch(ctx, (const meme_alnreg*)P.regs.p, (const i64*)P.reg_off.p, nreads, total, id_base, opt, &d))) return rc;
-    unsigned long long n_heavy = 0;
-    if (total) HIP_TRY(hipMemcpyAsync(P.h_regs.p, P.out.p, rbytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (total) HIP_TRY(hipMemcpyAsync(P.h_mapq.p, P.mapq.p, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(P.h_n_pri.p, P.n_pri.p, (size_t)nreads * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(P.h_status.p, P.status.p, (size_t)nreads, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&n_heavy, P.counter.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, P.ev[0], P.ev[1]));
+    if ((rc = reg_download(ctx, {recs, mapq, n_pri, status, ctrs})) || (rc = reg_sync_ms(ctx, P.ev, &ms))) return rc;
     out->nreads = nreads; out->total_regs = total; out->regs = (const meme_alnreg*)P.h_regs.p; out->n_pri = (const int32_t*)P.h_n_pri.p; out->mapq = (const uint8_t*)P.h_mapq.p;
-    out->status = (const uint8_t*)P.h_status.p; out->n_heavy = (i64)n_heavy; out->kernel_ms = ms;
+    out->status = (const uint8_t*)P.h_status.p; out->n_heavy = (i64)*(const unsigned long long*)ctx->h_ctr.p; out->kernel_ms = ms;
     return MEME_OK;
 }

@@ -297,6 +297,19 @@ def _p(a):
     return C.c_void_p(a.ctypes.data)
 
 
+def _view(ptr, count, dtype):
+    """a copy of `count` items of `dtype` at the address `ptr` (a pinned result buffer of the ctx); nothing there: an empty array"""
+    if count == 0 or not ptr:
+        return np.zeros(0, dtype=dtype)
+    buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
+    return np.frombuffer(buf, dtype=dtype, count=count).copy()
+
+
+def _contig_array(contigs):
+    """(offset, len, is_alt) tuples -> the meme_contig[] of the stages that take contigs"""
+    return (Contig * len(contigs))(*[Contig(int(o), int(l), int(a)) for o, l, a in contigs])
+
+
 class Context:
     """One HIP device + stream + workspaces (meme_ctx)."""
 
@@ -392,14 +405,8 @@ class Context:
         res = SeedHostResult()
         _check(lib().meme_seed_batch_host(C.c_void_p(self.h), _p(reads), _p(read_off), C.c_int64(n), C.byref(opt),
                                           C.byref(res)))
-
-        def view(ptr, count, dtype):
-            if count == 0:
-                return np.zeros(0, dtype=dtype)
-            buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
-            return np.frombuffer(buf, dtype=dtype, count=count).copy()
-        return (view(res.smems, res.total_smems, MEM_TL), view(res.smem_off, n + 1, np.int64),
-                view(res.hits, res.total_hits, np.uint64), view(res.hit_off, n + 1, np.int64))
+        return (_view(res.smems, res.total_smems, MEM_TL), _view(res.smem_off, n + 1, np.int64),
+                _view(res.hits, res.total_hits, np.uint64), _view(res.hit_off, n + 1, np.int64))
 
     def seed_batch_resident(self, reads, read_off, opt=None):
         """meme_seed_batch_resident: SMEMs and hits stay in HBM for chain_last_batch_host / extend_last_batch_host; returns the totals."""
@@ -444,7 +451,7 @@ class Context:
     def chain_last_batch_host(self, contigs, opt):
         """meme_chain_last_batch_host on the batch the last seed_batch_host call seeded.  contigs: (offset, len, is_alt) tuples.
         Returns a dict of numpy arrays (copies of the ctx's pinned buffers)."""
-        arr = (Contig * len(contigs))(*[Contig(int(o), int(l), int(a)) for o, l, a in contigs])
+        arr = _contig_array(contigs)
         res = ChainHostResult()
         _check(lib().meme_chain_last_batch_host(C.c_void_p(self.h), arr, C.c_int32(len(contigs)), C.byref(opt), C.byref(res)))
         return self._chain_result(res)
@@ -453,17 +460,11 @@ class Context:
         """meme_extend_last_batch_host on the batch the last seed_batch_host call seeded: chaining + seed extension on the device.
         Returns {"reg_off", "regs" (ALNREG records, copies), stats...}."""
         ext_opt = ext_opt or default_ext_opt()
-        arr = (Contig * len(contigs))(*[Contig(int(o), int(l), int(a)) for o, l, a in contigs])
+        arr = _contig_array(contigs)
         res = ExtHostResult()
         _check(lib().meme_extend_last_batch_host(C.c_void_p(self.h), arr, C.c_int32(len(contigs)), C.byref(chain_opt), C.byref(ext_opt), C.byref(res)))
         n = res.nreads
-
-        def view(ptr, count, dtype):
-            if count == 0:
-                return np.zeros(0, dtype=dtype)
-            buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
-            return np.frombuffer(buf, dtype=dtype, count=count).copy()
-        return {"reg_off": view(res.reg_off, n + 1, np.int64), "regs": view(res.regs, res.total_regs, ALNREG), "total_chains": int(res.total_chains),
+        return {"reg_off": _view(res.reg_off, n + 1, np.int64), "regs": _view(res.regs, res.total_regs, ALNREG), "total_chains": int(res.total_chains),
                 "n_pairs": int(res.n_pairs), "n_retried": int(res.n_retried), "n_bsw_calls": int(res.n_bsw_calls), "n_tier2": int(res.n_tier2),
                 "chain_ms": float(res.chain_ms), "ext_ms": float(res.ext_ms), "bsw_ms": float(res.bsw_ms),
                 "n_flt_jobs": int(res.n_flt_jobs), "n_flt_dropped": int(res.n_flt_dropped), "n_exact_prefix": int(res.n_exact_prefix),
@@ -476,13 +477,7 @@ class Context:
         jobs = np.ascontiguousarray(jobs, dtype=GJOB)
         res = GresHost()
         _check(lib().meme_global_batch_host(C.c_void_p(self.h), _p(jobs), C.c_int64(jobs.shape[0]), C.byref(opt), C.byref(res)))
-
-        def view(ptr, count, dtype):
-            if count == 0:
-                return np.zeros(0, dtype=dtype)
-            buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
-            return np.frombuffer(buf, dtype=dtype, count=count).copy()
-        return view(res.res, res.njobs, GRES), view(res.cigars, res.total_ops, np.uint32), float(res.kernel_ms)
+        return _view(res.res, res.njobs, GRES), _view(res.cigars, res.total_ops, np.uint32), float(res.kernel_ms)
 
     def gen_cigar_batch_host(self, jobs, opt=None):
         """meme_gen_cigar_batch_host: bwa_gen_cigar2 whole for a batch of its calls (CJOB records: query span of a resident read, text span,
@@ -491,13 +486,7 @@ class Context:
         jobs = np.ascontiguousarray(jobs, dtype=CJOB)
         res = CresHost()
         _check(lib().meme_gen_cigar_batch_host(C.c_void_p(self.h), _p(jobs), C.c_int64(jobs.shape[0]), C.byref(opt), C.byref(res)))
-
-        def view(ptr, count, dtype):
-            if count == 0:
-                return np.zeros(0, dtype=dtype)
-            buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
-            return np.frombuffer(buf, dtype=dtype, count=count).copy()
-        return view(res.res, res.njobs, CRES), view(res.cigars, res.total_ops, np.uint32), view(res.md, res.md_bytes, np.uint8), float(res.kernel_ms)
+        return _view(res.res, res.njobs, CRES), _view(res.cigars, res.total_ops, np.uint32), _view(res.md, res.md_bytes, np.uint8), float(res.kernel_ms)
 
     def sam_stage_text(self, names, quals=None):
         """meme_sam_stage_text: names (list of bytes, one per read of the resident batch) and qualities (one bytes object laid out like the
@@ -523,9 +512,7 @@ class Context:
                                                  C.c_int32(len(contig_names)), C.c_int32(int(softclip)), C.c_char_p(rg_id), C.byref(res)))
         if res.nrecs == 0:
             return b"", np.zeros(1, np.int64), 0.0
-        off = np.frombuffer((C.c_char * ((res.nrecs + 1) * 8)).from_address(res.text_off), dtype=np.int64).copy()
-        text = bytes((C.c_char * res.text_bytes).from_address(res.text)) if res.text_bytes else b""
-        return text, off, float(res.kernel_ms)
+        return _view(res.text, res.text_bytes, np.uint8).tobytes(), _view(res.text_off, res.nrecs + 1, np.int64), float(res.kernel_ms)
 
     def kswv_batch_host(self, jobs, ref, qer, opt=None):
         """meme_kswv_batch_host: the mate-rescue Smith-Waterman batch (mem_sam_pe_batch with the kswv kernels).  jobs: KSWV_JOB records over the
@@ -537,10 +524,7 @@ class Context:
         res = KswvHost()
         _check(lib().meme_kswv_batch_host(C.c_void_p(self.h), _p(jobs), C.c_int64(jobs.shape[0]), _p(ref), C.c_int64(ref.shape[0]), _p(qer),
                                           C.c_int64(qer.shape[0]), C.byref(opt), C.byref(res)))
-        if res.njobs == 0:
-            return np.zeros(0, KSWR), float(res.kernel_ms)
-        buf = (C.c_char * (res.njobs * KSWR.itemsize)).from_address(res.res)
-        return np.frombuffer(buf, dtype=KSWR, count=res.njobs).copy(), float(res.kernel_ms)
+        return _view(res.res, res.njobs, KSWR), float(res.kernel_ms)
 
     def matesw_batch_host(self, regs, reg_off, pes, contigs, l_pac, a=1, b=4, o_del=6, e_del=1, o_ins=6, e_ins=1, pen_unpaired=17, max_matesw=50, min_seed_len=19,
                           batch_reads=512, reads_of=None, first_read=0):
@@ -551,19 +535,13 @@ class Context:
         reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
         pes4 = np.zeros((4, 4), np.int32)
         pes4[:, :3] = np.asarray(pes, np.int32).reshape(4, 3)
-        arr = (Contig * len(contigs))(*[Contig(int(o), int(l), int(al)) for o, l, al in contigs])
+        arr = _contig_array(contigs)
         opt = MateOpt(a, b, o_del, e_del, o_ins, e_ins, pen_unpaired, max_matesw, min_seed_len, batch_reads)
         res = MateHost()
         _check(lib().meme_matesw_batch_host(C.c_void_p(self.h), C.c_void_p(reads_of.h if reads_of is not None else None), _p(regs), _p(reg_off), C.c_int64(first_read), C.c_int64(reg_off.shape[0] - 1), _p(pes4), arr, C.c_int32(len(contigs)), C.c_int64(l_pac),
                                             C.byref(opt), C.byref(res)))
-
-        def view(ptr, count, dtype):
-            if count == 0 or not ptr:
-                return np.zeros(0, dtype=dtype)
-            buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
-            return np.frombuffer(buf, dtype=dtype, count=count).copy()
-        return {"gar": view(res.gar, res.n_gar, np.int32), "gar_off": view(res.gar_off, res.nbatches + 1, np.int64), "job_off": view(res.job_off, res.nbatches + 1, np.int64),
-                "jobs": view(res.jobs, res.njobs, KSWV_JOB), "res": view(res.res, res.njobs, KSWR), "pose_ms": float(res.pose_ms), "kernel_ms": float(res.kernel_ms)}
+        return {"gar": _view(res.gar, res.n_gar, np.int32), "gar_off": _view(res.gar_off, res.nbatches + 1, np.int64), "job_off": _view(res.job_off, res.nbatches + 1, np.int64),
+                "jobs": _view(res.jobs, res.njobs, KSWV_JOB), "res": _view(res.res, res.njobs, KSWR), "pose_ms": float(res.pose_ms), "kernel_ms": float(res.kernel_ms)}
 
     def primary_batch_host(self, regs, reg_off, id_base=0, opt=None):
         """meme_primary_batch_host: primary marking and mapping quality (mem_mark_primary_se, mem_reorder_primary5 under opt.primary5, mem_approx_mapq_se) of the
@@ -574,14 +552,8 @@ class Context:
         n = reg_off.shape[0] - 1
         res = PrimaryHost()
         _check(lib().meme_primary_batch_host(C.c_void_p(self.h), _p(regs), _p(reg_off), C.c_int64(n), C.c_int64(int(id_base)), C.byref(opt), C.byref(res)))
-
-        def view(ptr, count, dtype):
-            if count == 0 or not ptr:
-                return np.zeros(0, dtype=dtype)
-            buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
-            return np.frombuffer(buf, dtype=dtype, count=count).copy()
-        return {"regs": view(res.regs, res.total_regs, ALNREG), "n_pri": view(res.n_pri, res.nreads, np.int32), "mapq": view(res.mapq, res.total_regs, np.uint8),
-                "status": view(res.status, res.nreads, np.uint8), "n_heavy": int(res.n_heavy), "kernel_ms": float(res.kernel_ms)}
+        return {"regs": _view(res.regs, res.total_regs, ALNREG), "n_pri": _view(res.n_pri, res.nreads, np.int32), "mapq": _view(res.mapq, res.total_regs, np.uint8),
+                "status": _view(res.status, res.nreads, np.uint8), "n_heavy": int(res.n_heavy), "kernel_ms": float(res.kernel_ms)}
 
     def primary_batch_device(self, d_regs_ptr, d_reg_off_ptr, nreads, total_regs, id_base, opt, d_regs_out_ptr, d_n_pri_ptr, d_mapq_ptr, d_status_ptr, d_n_heavy_ptr):
         """meme_primary_batch_device: the same on device arrays the caller owns, asynchronous on the ctx's stream (sync() before reading the results)."""
@@ -599,25 +571,20 @@ class Context:
         n_pri = np.ascontiguousarray(n_pri, dtype=np.int32)
         n = reg_off.shape[0] - 1
         assert n_pri.shape[0] == n
-        arr = (Contig * len(contigs))(*[Contig(int(o), int(l), int(a)) for o, l, a in contigs])
+        arr = _contig_array(contigs)
         res = PairHost()
         _check(lib().meme_pair_batch_host(C.c_void_p(self.h), _p(regs), _p(reg_off), _p(n_pri), C.c_int64(n), arr, C.c_int32(len(contigs)), C.c_int64(int(l_pac)), pair_pes(pes),
                                           C.c_int64(int(id_base)), C.byref(opt), C.byref(res)))
 
-        def view(ptr, count):
-            if count == 0 or not ptr:
-                return np.zeros(0, dtype=np.int32)
-            return np.frombuffer((C.c_char * (count * 4)).from_address(ptr), dtype=np.int32, count=count).copy()
         m = int(res.npairs)
-        status = np.frombuffer((C.c_char * m).from_address(res.status), dtype=np.uint8, count=m).copy() if m and res.status else np.zeros(0, np.uint8)
-        return {"score": view(res.score, m), "sub": view(res.sub, m), "n_sub": view(res.n_sub, m), "n_cand": view(res.n_cand, m), "z": view(res.z, 2 * m).reshape(m, 2),
-                "status": status, "n_heavy": int(res.n_heavy), "kernel_ms": float(res.kernel_ms)}
+        return {"score": _view(res.score, m, np.int32), "sub": _view(res.sub, m, np.int32), "n_sub": _view(res.n_sub, m, np.int32), "n_cand": _view(res.n_cand, m, np.int32),
+                "z": _view(res.z, 2 * m, np.int32).reshape(m, 2), "status": _view(res.status, m, np.uint8), "n_heavy": int(res.n_heavy), "kernel_ms": float(res.kernel_ms)}
 
     def pair_batch_device(self, d_regs_ptr, d_reg_off_ptr, d_n_pri_ptr, nreads, total_regs, contigs, l_pac, pes, id_base, opt, d_score_ptr, d_sub_ptr, d_n_sub_ptr, d_n_cand_ptr, d_z_ptr,
                           d_status_ptr, d_n_heavy_ptr):
         """meme_pair_batch_device: the same on device arrays the caller owns (d_regs_out, d_reg_off and d_n_pri of primary_batch_device as they are), asynchronous on the ctx's
         stream (sync() before reading the results)."""
-        arr = (Contig * len(contigs))(*[Contig(int(o), int(l), int(a)) for o, l, a in contigs])
+        arr = _contig_array(contigs)
         out = PairDeviceOut(d_score_ptr, d_sub_ptr, d_n_sub_ptr, d_n_cand_ptr, d_z_ptr, d_status_ptr, d_n_heavy_ptr)
         _check(lib().meme_pair_batch_device(C.c_void_p(self.h), C.c_void_p(d_regs_ptr), C.c_void_p(d_reg_off_ptr), C.c_void_p(d_n_pri_ptr), C.c_int64(nreads), C.c_int64(total_regs), arr,
                                             C.c_int32(len(contigs)), C.c_int64(int(l_pac)), pair_pes(pes), C.c_int64(int(id_base)), C.byref(opt or default_pair_opt()), C.byref(out)))
@@ -630,29 +597,23 @@ class Context:
         assert regs.dtype == ALNREG and regs.flags.c_contiguous
         reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
         n = reg_off.shape[0] - 1
-        arr = (Contig * len(contigs))(*[Contig(int(o), int(l), int(a)) for o, l, a in contigs])
+        arr = _contig_array(contigs)
         res = FinishHost()
         _check(lib().meme_finish_batch_host(C.c_void_p(self.h), _p(regs), _p(reg_off), C.c_int64(n), arr, C.c_int32(len(contigs)), C.c_int64(int(l_pac)), C.byref(opt), C.byref(res)))
-
-        def view(ptr, count, dtype):
-            if count == 0 or not ptr:
-                return np.zeros(0, dtype=dtype)
-            buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
-            return np.frombuffer(buf, dtype=dtype, count=count).copy()
-        return {"regs": view(res.regs, res.total_regs, ALNREG), "reg_off": view(res.reg_off, res.nreads + 1, np.int64), "use_mate_sort": view(res.use_mate_sort, res.nreads, np.uint8),
-                "status": view(res.status, res.nreads, np.uint8), "n_wave": int(res.n_wave), "n_patch_jobs": int(res.n_patch_jobs), "n_patched": int(res.n_patched),
+        return {"regs": _view(res.regs, res.total_regs, ALNREG), "reg_off": _view(res.reg_off, res.nreads + 1, np.int64), "use_mate_sort": _view(res.use_mate_sort, res.nreads, np.uint8),
+                "status": _view(res.status, res.nreads, np.uint8), "n_wave": int(res.n_wave), "n_patch_jobs": int(res.n_patch_jobs), "n_patched": int(res.n_patched),
                 "kernel_ms": float(res.kernel_ms)}
 
     def finish_batch_device(self, d_regs_ptr, d_reg_off_ptr, nreads, total_regs, contigs, l_pac, opt, d_regs_out_ptr, d_reg_off_out_ptr, d_use_mate_sort_ptr, d_status_ptr, d_counters_ptr):
         """meme_finish_batch_device: the same on device arrays the caller owns, asynchronous on the ctx's stream (sync() before reading the results)."""
-        arr = (Contig * len(contigs))(*[Contig(int(o), int(l), int(a)) for o, l, a in contigs])
+        arr = _contig_array(contigs)
         out = FinishDeviceOut(d_regs_out_ptr, d_reg_off_out_ptr, d_use_mate_sort_ptr, d_status_ptr, d_counters_ptr)
         _check(lib().meme_finish_batch_device(C.c_void_p(self.h), C.c_void_p(d_regs_ptr), C.c_void_p(d_reg_off_ptr), C.c_int64(nreads), C.c_int64(total_regs), arr, C.c_int32(len(contigs)),
                                               C.c_int64(int(l_pac)), C.byref(opt or default_finish_opt()), C.byref(out)))
 
     def chain_batch_host(self, smems, smem_off, hits, hit_off, read_len, contigs, opt):
         """meme_chain_batch_host: chains of seeds the caller brings (numpy arrays laid out as seed_batch_host returns them)."""
-        arr = (Contig * len(contigs))(*[Contig(int(o), int(l), int(a)) for o, l, a in contigs])
+        arr = _contig_array(contigs)
         smems = np.ascontiguousarray(smems, dtype=MEM_TL)
         smem_off = np.ascontiguousarray(smem_off, dtype=np.int64)
         hits = np.ascontiguousarray(hits, dtype=np.uint64)
@@ -666,16 +627,10 @@ class Context:
     @staticmethod
     def _chain_result(res):
         n = res.nreads
-
-        def view(ptr, count, dtype):
-            if count == 0:
-                return np.zeros(0, dtype=dtype)
-            buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
-            return np.frombuffer(buf, dtype=dtype, count=count).copy()
-        return {"chain_off": view(res.chain_off, n + 1, np.int64), "chains": view(res.chains, res.total_chains, CHAIN),
-                "seed_off": view(res.seed_off, n + 1, np.int64), "seeds": view(res.seeds, res.total_seeds, CHAIN_SEED),
-                "tree_size": view(res.tree_size, n, np.int32), "frac_rep": view(res.frac_rep, n, np.float32),
-                "fallback": view(res.fallback, n, np.uint8), "n_fallback": int(res.n_fallback), "n_tier2": int(res.n_tier2)}
+        return {"chain_off": _view(res.chain_off, n + 1, np.int64), "chains": _view(res.chains, res.total_chains, CHAIN),
+                "seed_off": _view(res.seed_off, n + 1, np.int64), "seeds": _view(res.seeds, res.total_seeds, CHAIN_SEED),
+                "tree_size": _view(res.tree_size, n, np.int32), "frac_rep": _view(res.frac_rep, n, np.float32),
+                "fallback": _view(res.fallback, n, np.uint8), "n_fallback": int(res.n_fallback), "n_tier2": int(res.n_tier2)}
 
     def seed_batch_device(self, d_reads_ptr, d_read_off_ptr, nreads, total_bases, opt=None) -> SeedResult:
         opt = opt or default_seed_opt()

@@ -62,6 +62,12 @@ def model(W, B, **opt):
     return FG.model(B["regs"], B["reg_off"], B["reads"], B["read_off"], W["text"], W["l_pac"], alt_of(W), FG.default_opt(**opt) if opt else None)
 
 
+def alt_flipped(W, B):
+    """W with is_alt flipped on the contig of the first record the model keeps of the batch B: a contig table the records of B notice"""
+    rid = int(model(W, B)[0]["rid"][0])
+    return dict(W, contigs=[(o, l, a ^ 1 if k == rid else a) for k, (o, l, a) in enumerate(W["contigs"])])
+
+
 def finish_opt(**kw):
     return hipapi.default_finish_opt(**{k: (float(np.float32(v)) if k == "mask_level_redun" else v) for k, v in kw.items()})
 

@@ -145,22 +145,28 @@ def _one_hit_chains(weights, spacing, dup):
     return sm, hits
 
 
+def _tied_batch():
+    """two pairs of reads of one-hit chains with monotone weights full of ties (test_tied_monotone_weights_...): -> (reads, smems, smem_off, hits, hit_off, read_len, pairs)"""
+    pairs = [([(40 - i) // 2 for i in range(40)], 1000, 150), ([i // 2 for i in range(100)], 600, 250)]
+    reads = [_one_hit_chains(w, spacing, dup) for w, spacing, _ in pairs for dup in (False, True)]
+    read_len = np.array([rl for _, _, rl in pairs for _ in (0, 1)], np.int32)
+    smem_off = np.zeros(5, np.int64); hit_off = np.zeros(5, np.int64)
+    smem_off[1:] = np.cumsum([sm.shape[0] for sm, _ in reads]); hit_off[1:] = np.cumsum([h.shape[0] for _, h in reads])
+    smems = np.concatenate([sm for sm, _ in reads]); hits = np.concatenate([h for _, h in reads])
+    return reads, smems, smem_off, hits, hit_off, read_len, pairs
+
+
 def test_tied_monotone_weights_take_the_sort_fallback_in_both_wavefront_tiers():
     """The comb-sort branch of the shared sort (bwa-meme_amd/csrc/meme_ksort.h) on the device: monotone chain weights full of ties spend klib's depth
     budget, and where its comb sort leaves equal weights differs from a stable sort.  Read A of each pair has more chains than the lane tier
     holds and is sorted by the LDS tier (wave_introsort_lds); read B also puts two chains on one position and is sorted by the B-tree tier
     (k_chain_wave).  The lane tier never has more than 16 chains: the sort is one partition pass there, which the goldens cover."""
     import test_introsort_model as M
-    pairs = [([(40 - i) // 2 for i in range(40)], 1000, 150), ([i // 2 for i in range(100)], 600, 250)]
+    reads, smems, smem_off, hits, hit_off, read_len, pairs = _tied_batch()
     for weights, _, _ in pairs:                                  # what the model makes of these weights (ids in tree order)
         arr = [(19 + w, i) for i, w in enumerate(weights)]
         M.COMB_CALLS[0] = 0
         assert M.klib(arr) != M.stable(arr) and M.COMB_CALLS[0] > 0, len(weights)
-    reads = [_one_hit_chains(w, spacing, dup) for w, spacing, _ in pairs for dup in (False, True)]
-    read_len = np.array([rl for _, _, rl in pairs for _ in (0, 1)], np.int32)
-    smem_off = np.zeros(5, np.int64); hit_off = np.zeros(5, np.int64)
-    smem_off[1:] = np.cumsum([sm.shape[0] for sm, _ in reads]); hit_off[1:] = np.cumsum([h.shape[0] for _, h in reads])
-    smems = np.concatenate([sm for sm, _ in reads]); hits = np.concatenate([h for _, h in reads])
     assert int(smems["end"].max()) <= 250 and int(smems["end"][:smem_off[2]].max()) <= 150
     contig_off, contig_alt, oo = np.array([0, 70_000, 150_000], np.int64), np.array([0, 0, 1], np.uint8), O.default_chain_opt(200_000)
     trees = [O.chain_read(sm, h, rl, contig_off, contig_alt, oo)[3] for (sm, h), rl in zip(reads, read_len)]
@@ -175,6 +181,24 @@ def test_tied_monotone_weights_take_the_sort_fallback_in_both_wavefront_tiers():
     assert R["n_fallback"] == 0 and list(R["tree_size"]) == trees
     assert tier3 == 2 and R["n_tier2"] == 4                      # both B reads reached the B-tree tier, through the LDS tier that sorts the A reads
     assert O.chain_compare_batch(smems, smem_off, hits, hit_off, read_len, contig_off, contig_alt, oo, R) == (0, -1)
+
+
+def test_the_contig_table_follows_the_call():
+    """one ctx, the tables A, B, A in turn (B: the first boundary moved into the reads' hits): the ctx keeps one contig table and restages it when a call brings another"""
+    reads, smems, smem_off, hits, hit_off, read_len, _ = _tied_batch()
+    tables = {"A": _contigs3(), "B": [(0, 30_000, 0), (30_000, 120_000, 0), (150_000, 50_000, 1)]}
+    oo = O.default_chain_opt(200_000)
+    cols = {k: (np.array([c[0] for c in t], np.int64), np.array([c[2] for c in t], np.uint8)) for k, t in tables.items()}
+    rids = {k: [int(ch["rid"]) for ch in O.chain_read(reads[0][0], reads[0][1], int(read_len[0]), off, alt, oo)[1]] for k, (off, alt) in cols.items()}
+    assert rids["A"] != rids["B"] and len(rids["A"]) == len(rids["B"]) == 40      # the two tables give different chains: the test cannot pass on a stale table
+    ctx = hipapi.Context(0)
+    try:
+        for name in ("A", "B", "A"):
+            R = ctx.chain_batch_host(smems, smem_off, hits, hit_off, read_len, tables[name], hipapi.default_chain_opt(200_000))
+            assert R["n_fallback"] == 0
+            assert O.chain_compare_batch(smems, smem_off, hits, hit_off, read_len, cols[name][0], cols[name][1], oo, R) == (0, -1), name
+    finally:
+        ctx.close()
 
 
 def _adversarial(n, seed):

@@ -232,6 +232,17 @@ def test_a_patch_that_bridges_the_strands_sets_status(ctx, W, gold):
     assert FC.same(others, want) is None
 
 
+def test_the_contig_table_follows_the_call(ctx, W):
+    """one ctx, the tables A, B, A in turn: the ctx keeps one contig table and restages it when a call brings another"""
+    B = FC.subset(W, np.arange(10))
+    WB = FC.alt_flipped(W, B)
+    want = {"A": FC.model(W, B), "B": FC.model(WB, B)}
+    assert FG.same_records(*want["A"][:3], *want["B"][:3]) is not None        # the two tables give different records: the test cannot pass on a stale table
+    for name, w in (("A", W), ("B", WB), ("A", W)):
+        got = run(ctx, w, B)
+        assert FC.same(got, want[name]) is None and not got["status"].any(), name
+
+
 def test_arguments_the_stage_refuses(ctx, W):
     B = FC.subset(W, np.arange(10))
     fresh = hipapi.Context(0)

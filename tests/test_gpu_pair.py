@@ -105,6 +105,7 @@ def test_finish_primary_and_pair_stages_chained_without_a_host_copy(W, modelled)
     """meme_finish_batch_device -> meme_primary_batch_device -> meme_pair_batch_device on finish_golden.npz's reads, each taking the arrays the stage before it left in HBM:
     the model's result on primary_golden.npz's records (the first batch of the workload, which begins with them)"""
     import torch
+    import finish_cases as FC
     import finish_gen as FG
     import primary_gen as PG
     dev = torch.device("cuda:0")
@@ -140,6 +141,21 @@ def test_finish_primary_and_pair_stages_chained_without_a_host_copy(W, modelled)
         assert QG.same(got, want, ALL) is None
         assert int(got["n_cand"].sum()) == int(want["n_cand"].sum()) > 50          # (the fixture's reads are paired as they come, not mates: few pairs have candidates)
         assert got["n_heavy"] == int((keys_of(B) > LIGHT_MAX).sum()) > 50
+        # record finishing twice more, with the table it has used and at once, no host synchronisation in between, with another: the ctx's one contig table has to wait
+        # for the kernels that read it before it is overwritten
+        FWB = FC.alt_flipped(FW, FC.subset(FW, np.arange(10)))
+        want_a, want_b = FC.model(FW, FW), FC.model(FWB, FW)
+        assert FG.same_records(*want_a[:3], *want_b[:3]) is not None
+        F2 = {k: torch.zeros_like(v) for k, v in F.items()}
+        torch.cuda.synchronize()
+        for w, T in ((FW, F), (FWB, F2)):
+            c.finish_batch_device(d_regs.data_ptr(), d_off.data_ptr(), n, total, w["contigs"], w["l_pac"], None, T["out"].data_ptr(), T["off"].data_ptr(), T["ums"].data_ptr(),
+                                  T["status"].data_ptr(), T["ctr"].data_ptr())
+        c.sync()
+        for T, want in ((F, want_a), (F2, want_b)):
+            off = T["off"].cpu().numpy()
+            left = {"regs": FG.take(T["out"].cpu().numpy().view(hipapi.ALNREG), np.arange(off[-1])), "reg_off": off, "use_mate_sort": T["ums"].cpu().numpy()}
+            assert FC.same(left, want) is None and not T["status"].cpu().numpy().any()
         del keep
     finally:
         c.close()
@@ -303,3 +319,16 @@ def test_arguments_the_stage_refuses(ctx, W):
         run(ctx, dict(B, reg_off=down))
     with pytest.raises(hipapi.MemeError):                # contigs that are no reference sequences of the genome
         run(ctx, dict(B, contigs=[(0, 100000, 0), (50000, 100000, 0), (200000, 100000, 0)]))
+
+
+def test_a_refused_contig_table_is_not_remembered(ctx, W):
+    """the ctx keeps one contig table: a table it refuses leaves nothing behind, and a table that differs in is_alt alone (which pair scoring does not read) is staged
+    like any other"""
+    B = QG.piece(W[1], 0, 4)
+    want = QG.model(B)
+    with pytest.raises(hipapi.MemeError):
+        run(ctx, dict(B, contigs=[(0, 100000, 0), (50000, 100000, 0), (200000, 100000, 0)]))
+    assert QG.same(run(ctx, B), want, ALL) is None
+    alt = [(o, l, a ^ 1) for o, l, a in QG.CONTIGS]
+    assert alt != list(QG.CONTIGS) and [c[:2] for c in alt] == [c[:2] for c in QG.CONTIGS]
+    assert QG.same(run(ctx, dict(B, contigs=alt)), want, ALL) is None
