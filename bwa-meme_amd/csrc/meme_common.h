@@ -279,9 +279,15 @@ struct meme_ctx {
     i64 chain_light_hits = 32;         // reads with more hits to walk skip the lane-per-read tier: LDS tier at once, beside it
     i64 chain_lane_hits = 256;         // hits per read the lane-per-read chaining tier walks; reads with more go to the wavefront tiers at once
     i64 chain_wave_tiers = 1;          // 0: the chaining stage skips the LDS tier (everything beyond the lane tier through the B-tree tier; tests)
+    i64 sa_chunk = (i64)1 << 28;       // meme_sa_build_device sorts the four-base buckets in groups of at most this many suffixes (a bucket alone may exceed it) ...
+    i64 sa_piece = (i64)1 << 28;       // ... and looks for the padding entries in pieces of this many slots.  Both have tuning keys: bounds of the workspace, and how the tests reach the
+                                       // multi-group and multi-piece paths with small texts; same array
     i64 bsw_blocks = 0;
     i64 bsw_lane_min_pairs = 32768;   // batches at least this big use the lane-per-pair kernel (throughput); smaller ones the
                                        // lanes-per-pair kernel (latency: a lone pair takes ~6 ms on one lane, ~0.3 ms on 64)
+    // what the last suffix-array build on this ctx did (meme_debug_sa_stats); valid after a build that returned MEME_OK
+    bool sa_stats_valid = false;
+    long long sa_stats[MEME_SA_STATS] = {0};
     // timings
     i64 sam_text_reads = 0;            // reads of the batch whose names / qualities meme_sam_stage_text staged (0: none)
     bool sam_has_quals = false;

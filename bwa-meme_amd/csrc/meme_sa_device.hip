@@ -11,7 +11,9 @@
 // Order convention = the reference's (src/Learnedindex.cpp:157-229, 242, 456-548; host/meme_sa.cpp): the text is followed by
 // k = max(longest A run, longest T run) + 1 bases T and then the end sentinel; the suffix array of that padded text is built
 // and the k entries that point into the padding are dropped.  The result equals the reference's `.pos_packed` order
-// (checked against the host builder by tests/test_gpu_sa.py).
+// (checked against the host builder by tests/test_gpu_sa.py).  The group bound of step 2 and the piece length of the final drop are the
+// tuning keys sa_chunk / sa_piece; meme_debug_sa_stats says what a build did, which is how the tests know that a small text took the
+// multi-group and multi-piece paths of a genome-sized one.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
@@ -207,6 +209,7 @@ extern "C" int meme_sa_build_device(meme_ctx* ctx, const uint8_t* d_text0123, in
     if (!ctx || !d_text0123 || !d_sa || n < 64) { meme_set_error("meme_sa_build_device: bad argument"); return MEME_E_ARG; }
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
+    ctx->sa_stats_valid = false;
     Scratch S;
     int rc;
     unsigned long long* d_cnt = nullptr;
@@ -232,7 +235,8 @@ extern "C" int meme_sa_build_device(meme_ctx* ctx, const uint8_t* d_text0123, in
     HIP_TRY(hipMemcpyAsync(h_hist, d_cnt, sizeof(h_hist), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     // ---- groups of consecutive buckets, each at most `chunk` suffixes (a single bucket may exceed it) ----------------------
-    i64 chunk = (i64)1 << 28, biggest = 0;
+    const i64 chunk = ctx->sa_chunk;                     // (tuning key; 2^28 unless a test asks for small groups)
+    i64 biggest = 0;
     std::vector<std::pair<unsigned, unsigned>> groups;
     {
         unsigned b = 0;
@@ -309,8 +313,8 @@ extern "C" int meme_sa_build_device(meme_ctx* ctx, const uint8_t* d_text0123, in
         HIP_TRY(hipStreamSynchronize(st));
         for (auto& t : tied_parts) S.drop(t.first);
     }
-    i64 m = n_tied;
-    for (i64 h = 32; m > 0; h *= 2) {
+    i64 m = n_tied, rounds = 0;
+    for (i64 h = 32; m > 0; h *= 2, ++rounds) {
         if (h > 4 * N) { meme_set_error("meme_sa_build_device: refinement did not converge"); return MEME_E_STATE; }
         Scratch R;
         u64 *prim = nullptr, *sec = nullptr, *val = nullptr, *k2 = nullptr, *prim_s = nullptr, *sec_s = nullptr, *val_s = nullptr, *upos2 = nullptr;
@@ -359,13 +363,13 @@ extern "C" int meme_sa_build_device(meme_ctx* ctx, const uint8_t* d_text0123, in
         unsigned char* stmp = nullptr;
         // the padding entries sit where suffixes start with a long T run: flag + select over the whole array, in pieces
         if ((rc = S.get(&pad_slots, (size_t)k_pad + 8))) return rc;
-        const i64 piece = (i64)1 << 28;
+        const i64 piece = ctx->sa_piece < N ? ctx->sa_piece : N;   // (tuning key; 2^28 slots, or the whole array where it is shorter)
         if ((rc = S.get(&flag, (size_t)piece)) || (rc = S.get(&iota, (size_t)piece))) return rc;
         size_t sb = 0;
         HIP_TRY(rocprim::select(nullptr, sb, iota, flag, pad_slots, d_cnt, piece, st));
         if ((rc = S.get(&stmp, sb))) return rc;
-        i64 found = 0;
-        for (i64 o = 0; o < N; o += piece) {
+        i64 found = 0, n_pieces = 0, pad_pieces = 0;
+        for (i64 o = 0; o < N; o += piece, ++n_pieces) {
             const i64 mlen = N - o < piece ? N - o : piece;
             hipLaunchKernelGGL(k_sa_flag_padding, dim3(grid_blocks(mlen, 256, 256 * 32)), dim3(256), 0, st, (const u64*)(sa + o), mlen, (i64)n, flag);
             hipLaunchKernelGGL(k_iota_off, dim3(grid_blocks(mlen, 256, 256 * 32)), dim3(256), 0, st, iota, mlen, o);
@@ -374,12 +378,25 @@ extern "C" int meme_sa_build_device(meme_ctx* ctx, const uint8_t* d_text0123, in
             HIP_TRY(hipMemcpyAsync(&h_sel, d_cnt, sizeof(h_sel), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             found += (i64)h_sel;
+            if (h_sel) ++pad_pieces;
             if (found > k_pad) { meme_set_error("meme_sa_build_device: internal padding count mismatch"); return MEME_E_STATE; }
         }
         if (found != k_pad) { meme_set_error("meme_sa_build_device: internal padding count mismatch (%lld of %lld)", (long long)found, (long long)k_pad); return MEME_E_STATE; }
         hipLaunchKernelGGL(k_sa_drop_padding, dim3(grid_blocks(N, 256, 256 * 32)), dim3(256), 0, st, (const u64*)sa, N, (i64)n, (const u64*)pad_slots, (int)k_pad, (u64*)d_sa);
+        const long long stats[MEME_SA_STATS] = {(long long)k_pad, (long long)groups.size(), (long long)biggest, (long long)n_tied, (long long)rounds,
+                                                (long long)n_pieces, (long long)pad_pieces};
+        for (int k = 0; k < MEME_SA_STATS; ++k) ctx->sa_stats[k] = stats[k];
     }
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipGetLastError());
+    ctx->sa_stats_valid = true;
+    return MEME_OK;
+}
+
+extern "C" int meme_debug_sa_stats(meme_ctx* ctx, int64_t* out, int32_t capacity) {
+    if (!ctx || !out) return MEME_E_ARG;
+    if (!ctx->sa_stats_valid) { meme_set_error("meme_debug_sa_stats: no suffix array was built on this ctx, or the last build failed"); return MEME_E_STATE; }
+    if (capacity < MEME_SA_STATS) { meme_set_error("meme_debug_sa_stats: %d values needed", MEME_SA_STATS); return MEME_E_CAPACITY; }
+    for (int k = 0; k < MEME_SA_STATS; ++k) out[k] = ctx->sa_stats[k];
     return MEME_OK;
 }

@@ -67,6 +67,16 @@ int meme_scan_exclusive(meme_ctx* ctx, const i64* d_in, i64* d_out, i64 n) {
     return MEME_OK;
 }
 
+// the scan on caller-owned arrays, finished when the call returns (tests/test_gpu_index_staging.py)
+extern "C" int meme_debug_scan_exclusive(meme_ctx* ctx, const int64_t* d_in, int64_t* d_out, int64_t n) {
+    if (!ctx || !d_in || !d_out || n < 0) { meme_set_error("meme_debug_scan_exclusive: bad argument"); return MEME_E_ARG; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int rc = meme_scan_exclusive(ctx, (const i64*)d_in, (i64*)d_out, (i64)n);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return MEME_OK;
+}
+
 int meme_scan_total(meme_ctx* ctx, const i64* d_in, i64* d_out, i64 n, i64* h_total) {
     const int rc = meme_scan_exclusive(ctx, d_in, d_out, n);
     if (!rc) HIP_TRY(hipMemcpyAsync(h_total, d_out + n, 8, hipMemcpyDeviceToHost, ctx->stream));

@@ -235,10 +235,11 @@ EXPORTS = ["meme_device_count", "meme_ctx_create", "meme_ctx_destroy", "meme_las
            "meme_host_free", "meme_stage_pack_text", "meme_stage_pos5_from_sa", "meme_stage_build_entries", "meme_stage_build_plcp",
            "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_primary_batch_host", "meme_primary_batch_device", "meme_finish_batch_host", "meme_finish_batch_device", "meme_pair_batch_host", "meme_pair_batch_device", "meme_seed_batch_device",
            "meme_bsw_batch", "meme_bsw_batch_device", "meme_get_timings", "meme_set_tuning", "meme_debug_packed_reads",
-           "meme_debug_reseed_counts"]
+           "meme_debug_reseed_counts", "meme_debug_sa_stats", "meme_debug_scan_exclusive"]
 
 RESEED_MAX_ROUNDS = 8                    # meme_hip.h: MEME_RESEED_COUNTS = RESEED_MAX_ROUNDS + 6 values from meme_debug_reseed_counts
 RESEED_COUNTS = RESEED_MAX_ROUNDS + 6
+SA_STATS = ("k_pad", "groups", "largest_group", "tied", "rounds", "pieces", "pad_pieces")    # meme_hip.h: the MEME_SA_STATS values of meme_debug_sa_stats, in order
 
 _lib = None
 
@@ -444,6 +445,18 @@ class Context:
         st = RESEED_MAX_ROUNDS                         # layout: one list length per round, then stage 0 / 1 / 2, no interval, walked, neighbour probes
         return {"rounds": [int(v) for v in out[:rounds.value]], "stage": [int(v) for v in out[st:st + 3]], "no_interval": int(out[st + 3]),
                 "walked": int(out[st + 4]), "neighbour_probes": int(out[st + 5])}
+
+    def debug_sa_stats(self):
+        """meme_debug_sa_stats: what the last meme_sa_build_device on this ctx did.  Returns a dict: `k_pad` (bases T behind the text), `groups` (bucket
+        groups sorted) and `largest_group` (its suffixes), `tied` (suffixes tied after the sort by 32 bases), `rounds` (refinement rounds), `pieces` (of the
+        search for the padding's entries) and `pad_pieces` (pieces that held one)."""
+        out = np.zeros(len(SA_STATS), dtype=np.int64)
+        _check(lib().meme_debug_sa_stats(C.c_void_p(self.h), _p(out), C.c_int32(out.size)))
+        return {k: int(v) for k, v in zip(SA_STATS, out)}
+
+    def debug_scan_exclusive(self, d_in_ptr, d_out_ptr, n):
+        """meme_debug_scan_exclusive: out[i] = in[0] + ... + in[i - 1] for i in [0, n] over int64 arrays in HBM (out holds n + 1 values; finished on return)"""
+        _check(lib().meme_debug_scan_exclusive(C.c_void_p(self.h), C.c_void_p(d_in_ptr), C.c_void_p(d_out_ptr), C.c_int64(n)))
 
     def seed_reserve(self, nreads, total_bases):
         _check(lib().meme_seed_reserve(C.c_void_p(self.h), C.c_int64(nreads), C.c_int64(total_bases)))

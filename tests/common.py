@@ -43,6 +43,52 @@ def build_index(fasta, bits=12, threads=4):
     return dst
 
 
+def pos5_image(sa):
+    """the 5-byte position image: the upper 32 bits little-endian, then the low byte"""
+    sa = np.ascontiguousarray(sa, dtype=np.uint64)
+    out = np.empty((sa.shape[0], 5), np.uint8)
+    out[:, :4] = (sa >> np.uint64(8)).astype("<u4").view(np.uint8).reshape(-1, 4)
+    out[:, 4] = (sa & np.uint64(0xff)).astype(np.uint8)
+    return out.reshape(-1)
+
+
+def entry_keys(text, sa):
+    """the 32-base key of every suffix-array slot (2 bits per base, first base on top; a suffix that ends is padded with T)"""
+    pad = np.concatenate([text, np.full(32, 3, np.uint8)]).astype(np.uint64)
+    pos = sa.astype(np.int64)
+    k = np.zeros(text.shape[0], np.uint64)
+    for j in range(32):
+        k = (k << np.uint64(2)) | pad[pos + j]
+    return k
+
+
+def prmi_bounds_cover(text, sa, l1, l2, slots):
+    """Every key of `slots` must be found inside [pred - lo_err, pred + hi_err] of its record (reference lookup arithmetic,
+    src/LearnedIndex_seeding.cpp:186-210, 2145-2146).  l1 / l2: the third- and second-layer tables as 24-byte records (intercept, slope, error word)."""
+    rec_t = np.dtype([("a", "<f8"), ("b", "<f8"), ("e", "<u8")])
+    l1, l2 = np.ascontiguousarray(l1).view(rec_t), np.ascontiguousarray(l2).view(rec_t)
+    n = sa.shape[0]
+    bits = int(np.log2(l2.shape[0]))
+    text = np.concatenate([text, np.full(40, 3, np.uint8)])
+    for slot in slots:
+        slot = int(slot)
+        p = int(sa[slot])
+        key = 0
+        for r in range(32):
+            key = (key << 2) | int(text[p + r])
+        rec = l2[key >> (64 - bits)]
+        pred = rec["a"] + rec["b"] * float(key)
+        err = int(rec["e"])
+        if err >> 63:
+            ps, pn = (err >> 32) & 0x7fffffff, err & 0xffffffff
+            rec = l1[ps + int(min(max(pred, 0), pn - 1))]
+            pred = rec["a"] + rec["b"] * float(key)
+            err = int(rec["e"])
+        pos = int(min(max(pred, 0), n - 1))
+        lo, hi = (err >> 32) & 0x3fffffff, err & 0x7fffffff
+        assert pos - lo <= slot <= pos + hi, (slot, key, pos, lo, hi)
+
+
 def chain_golden_workload():
     """The genome and reads tests/golden/chain_golden.npz was generated from (same seeds as tests/golden/make_chain_golden.py):
     returns (genome, list of reads as uint8 code arrays of their own lengths)."""

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import oracle_py as O
-from common import GOLDEN, build_index, read_fastq_codes
+from common import GOLDEN, build_index, entry_keys, pos5_image, read_fastq_codes
 from pymeme import hipapi, hostapi, synth
 from pymeme.hostapi import RMI_DTYPE
 
@@ -27,25 +27,6 @@ SHIFTS = (11, 12, 13, 16, 17, 64, 65, 1000)
 
 
 # ---- host restatements ---------------------------------------------------------------------------------------------------------------------
-def pos5_image(sa):
-    """the 5-byte position image: the upper 32 bits little-endian, then the low byte"""
-    sa = np.ascontiguousarray(sa, dtype=np.uint64)
-    out = np.empty((sa.shape[0], 5), np.uint8)
-    out[:, :4] = (sa >> U(8)).astype("<u4").view(np.uint8).reshape(-1, 4)
-    out[:, 4] = (sa & U(0xff)).astype(np.uint8)
-    return out.reshape(-1)
-
-
-def entry_keys(text, sa):
-    """the 32-base key of every suffix-array slot (2 bits per base, first base on top; a suffix that ends is padded with T)"""
-    pad = np.concatenate([text, np.full(32, 3, np.uint8)]).astype(np.uint64)
-    pos = sa.astype(np.int64)
-    k = np.zeros(text.shape[0], np.uint64)
-    for j in range(32):
-        k = (k << U(2)) | pad[pos + j]
-    return k
-
-
 def read_keys(reads, off):
     """The key a search from any base of any read would look up, on both strands: the bases up to the next N or the read's end, at most 32 of
     them, T-padded.  Returns (keys, read index, valid bases capped at 32)."""

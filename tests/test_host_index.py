@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import oracle_py as O
-from common import GOLDEN, build_index
+from common import GOLDEN, build_index, prmi_bounds_cover
 from pymeme import synth
 
 
@@ -54,25 +54,6 @@ def test_prmi_bounds_cover_every_key():
     src/LearnedIndex_seeding.cpp:186-210, 2145-2146)."""
     prefix = build_index(os.path.join(GOLDEN, "g1.fa"))
     idx = O.load_index_files(prefix)
-    n = idx.sa.shape[0]
     l2 = np.fromfile(prefix + ".suffixarray_uint64_L2_PARAMETERS", dtype=[("a", "<f8"), ("b", "<f8"), ("e", "<u8")])
     l1 = np.fromfile(prefix + ".suffixarray_uint64_L1_PARAMETERS", dtype=[("a", "<f8"), ("b", "<f8"), ("e", "<u8")])
-    bits = int(np.log2(l2.shape[0]))
-    text = np.concatenate([idx.text, np.full(40, 3, np.uint8)])
-    rng = np.random.default_rng(0)
-    for slot in rng.integers(0, n, size=3000):
-        p = int(idx.sa[slot])
-        key = 0
-        for r in range(32):
-            key = (key << 2) | int(text[p + r])
-        rec = l2[key >> (64 - bits)]
-        pred = rec["a"] + rec["b"] * float(key)
-        err = int(rec["e"])
-        if err >> 63:
-            ps, pn = (err >> 32) & 0x7fffffff, err & 0xffffffff
-            rec = l1[ps + int(min(max(pred, 0), pn - 1))]
-            pred = rec["a"] + rec["b"] * float(key)
-            err = int(rec["e"])
-        pos = int(min(max(pred, 0), n - 1))
-        lo, hi = (err >> 32) & 0x3fffffff, err & 0x7fffffff
-        assert pos - lo <= slot <= pos + hi
+    prmi_bounds_cover(idx.text, idx.sa, l1, l2, np.random.default_rng(0).integers(0, idx.sa.shape[0], size=3000))
