@@ -151,14 +151,18 @@ struct ResidentBatch {
 // a seeding counter set (u64): slot cursor of the tier, searches, reads left for the next tier (the length of its overflow list), window loads, eight diagnostic sums
 // (SEED_PROF, or RESEED_PROF's census), searches of the re-seeding kernels' lanes, length of the pending list, the two blocked-region cursors; then what
 // meme_debug_reseed_counts reports: the length of the blocked list each batch search met (one per round), the blocked regions' lane searches by the region's
-// stage, how many of them ended without an interval / walked a run for one, and their probes of a neighbour slot outside the cached window
+// stage, how many of them ended without an interval / walked a run for one, and their probes of a neighbour slot outside the cached window; last, the read cursor
+// of tier 0's round-3 launch and the third-round searches it ran twice (key-only compares could not decide them)
 enum { SEED_CTR_SLOT = 0, SEED_CTR_SEARCHES = 1, SEED_CTR_OVERFLOW = 2, SEED_CTR_WINDOWS = 3, SEED_CTR_PROF = 4, SEED_CTR_LANE = 12, SEED_CTR_PEND = 13, SEED_CTR_BLK = 14, SEED_CTR_BLK_OUT = 15,
-       SEED_CTR_RS_ROUND = 16, SEED_CTR_RS_STAGE = 24, SEED_CTR_RS_NOINTV = 27, SEED_CTR_RS_WALKED = 28, SEED_CTR_RS_NBPROBE = 29, SEED_CTRS = 32 };
+       SEED_CTR_RS_ROUND = 16, SEED_CTR_RS_STAGE = 24, SEED_CTR_RS_NOINTV = 27, SEED_CTR_RS_WALKED = 28, SEED_CTR_RS_NBPROBE = 29, SEED_CTR_SLOT3 = 30, SEED_CTR_R3_REPEAT = 31, SEED_CTRS = 32 };
 constexpr int RESEED_MAX_ROUNDS = SEED_CTR_RS_STAGE - SEED_CTR_RS_ROUND;
 enum { SEED_EV_PACK0, SEED_EV_PACK1, SEED_EV_SEARCH0, SEED_EV_SEARCH1, SEED_EV_RESEED0, SEED_EV_GATHER0, SEED_EV_GATHER1, SEED_EVS };   // SeedWs::ev: begin / end of packing, of a tier's search, begin of re-seeding, begin / end of offsets + gather
 struct SeedWs {
     DevBuf slots[3], ovf[2];           // SMEM slots of a tier; reads that overflow it (tier & 1)
     DevBuf slot_cnt, slot_hits, slot_loc, counters, pend, blk;
+    DevBuf carry;                      // per read, from tier 0's rounds-1/2 launch to its round-3 launch: searches | windows << 32, or "sent to the overflow list"
+    long long r3_counts[MEME_R3_COUNTS] = {0};   // the last seeding call: did tier 0 run in two launches, third-round searches run twice (meme_debug_seed_r3_counts)
+    bool r3_valid = false;
     long long reseed_counts[SEED_CTRS - SEED_CTR_RS_ROUND] = {0};   // the re-seeding counters of the last seeding call (meme_debug_reseed_counts); valid while reseed_rounds > 0
     int reseed_rounds = 0;
     HostBuf h_smems, h_hits, h_smem_off, h_hit_off;   // results of meme_seed_batch_host
@@ -276,6 +280,8 @@ struct meme_ctx {
     i64 gcig_zcap = -1;                // >= 0: bytes of LDS per CIGAR job for its backtrack matrix / window (default: 8192 where a typical matrix of the batch fits, else 2048)
     i64 ext_census = 0;                // 1: the extension stage counts its exact-prefix jobs (a measurement, profiles/r05_bsw.md)
     i64 seed_defer = 1;                // 1: re-seeding regions of unique SMEMs are verified on the plcp table (k_reseed) instead of searched
+    i64 seed_r3_split = 1;             // tier 0 with three rounds: 1 = the third round in a k_seed launch of its own behind rounds 1-2, its searches on the keys alone first;
+                                       // 0 = one launch for all three rounds
     i64 chain_light_hits = 32;         // reads with more hits to walk skip the lane-per-read tier: LDS tier at once, beside it
     i64 chain_lane_hits = 256;         // hits per read the lane-per-read chaining tier walks; reads with more go to the wavefront tiers at once
     i64 chain_wave_tiers = 1;          // 0: the chaining stage skips the LDS tier (everything beyond the lane tier through the B-tree tier; tests)

@@ -146,10 +146,11 @@ extern "C" int meme_get_timings(meme_ctx* ctx, meme_timings* out) {
 extern "C" int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value) {
     if (!ctx || !key) return MEME_E_ARG;
     if (!strcmp(key, "gcig_groups") && value != 0 && value != 1) { meme_set_error("gcig_groups must be 0 or 1"); return MEME_E_ARG; }
+    if (!strcmp(key, "seed_r3_split") && value != 0 && value != 1) { meme_set_error("seed_r3_split must be 0 or 1"); return MEME_E_ARG; }
     if (!strcmp(key, "group_lanes") && value != 1 && value != 2 && value != 4 && value != 8 && value != 16 && value != 32) { meme_set_error("group_lanes must be 1, 2, 4, 8, 16 or 32"); return MEME_E_ARG; }
     const i64 any = INT64_MIN;   // no lower clamp
     static const struct { const char* key; i64 meme_ctx::*member; i64 at_least; } keys[] = {
-        {"seed_blocks", &meme_ctx::seed_blocks, any}, {"helper_blocks", &meme_ctx::helper_blocks, 0}, {"smem_cap", &meme_ctx::smem_cap, 8}, {"seed_defer", &meme_ctx::seed_defer, any}, {"max_batch", &meme_ctx::max_batch, any},
+        {"seed_blocks", &meme_ctx::seed_blocks, any}, {"helper_blocks", &meme_ctx::helper_blocks, 0}, {"smem_cap", &meme_ctx::smem_cap, 8}, {"seed_defer", &meme_ctx::seed_defer, any}, {"seed_r3_split", &meme_ctx::seed_r3_split, 0}, {"max_batch", &meme_ctx::max_batch, any},
         {"sam_max_batch", &meme_ctx::sam_max_batch, any}, {"bsw_circ", &meme_ctx::bsw_circ, any}, {"ext_split", &meme_ctx::ext_split, any}, {"ext_slab_jobs", &meme_ctx::ext_slab_jobs, 1},
         {"ext_census", &meme_ctx::ext_census, any}, {"gcig_zcap", &meme_ctx::gcig_zcap, any}, {"gcig_groups", &meme_ctx::gcig_groups, any}, {"ext_live_only", &meme_ctx::ext_live_only, any},
         {"ext_rounds", &meme_ctx::ext_rounds, 0}, {"bsw_blocks", &meme_ctx::bsw_blocks, any}, {"bsw_lane_min_pairs", &meme_ctx::bsw_lane_min_pairs, any},

@@ -179,13 +179,21 @@ __global__ void __launch_bounds__(BLOCK) k_gather(const SaEnt* __restrict__ sa, 
     }
 }
 
-template <int G>
-int launch_k_seed(hipStream_t stream, const SeedArgs& A, size_t lds, i64 blocks) {
+template <int G, int RND>
+int launch_k_seed_rounds(hipStream_t stream, const SeedArgs& A, size_t lds, i64 blocks) {
     if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_seed<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_seed<G>, dim3((unsigned)blocks), dim3(BLOCK), lds, stream, A);
+        HIP_TRY(hipFuncSetAttribute((const void*)k_seed<G, RND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_seed<G, RND>), dim3((unsigned)blocks), dim3(BLOCK), lds, stream, A);
     HIP_TRY(hipGetLastError());
     return MEME_OK;
+}
+template <int G>
+int launch_k_seed(hipStream_t stream, const SeedArgs& A, size_t lds, i64 blocks, int rnd) {
+    switch (rnd) {
+    case SEED_R12: return launch_k_seed_rounds<G, SEED_R12>(stream, A, lds, blocks);
+    case SEED_R3: return launch_k_seed_rounds<G, SEED_R3>(stream, A, lds, blocks);
+    default: return launch_k_seed_rounds<G, SEED_ALL>(stream, A, lds, blocks);
+    }
 }
 
 // ---- one seeding call, in phases ----------------------------------------------------------------------------
@@ -197,6 +205,7 @@ struct SeedRun {
     PackGeom geo;
     TierTable tiers = {};              // where every tier that ran keeps its slots (k_gather)
     bool defer = false;                // tier 0 leaves the re-seeding regions of unique SMEMs to k_reseed
+    bool split = false;                // tier 0 runs its third round in a k_seed launch of its own (tuning seed_r3_split)
     i64 n_early = -1;                  // reads of the tier-1 launch that ran beside the re-seeding kernels (-1: none did)
     i64 n_todo = 0;                    // reads the last tier left to the next one
     float ms_total = 0.f, ms_reseed = 0.f;
@@ -251,7 +260,9 @@ int seed_pack(SeedRun& R, const uint8_t* d_reads, i64 max_len, i64 total_bytes) 
 
 // One k_seed launch of a tier: `n_todo` reads (tier 0: the batch; overflow tiers: the reads named in `pending`), SMEM slots in
 // ctx->seed.slots[tier], the reads that overflow THIS tier appended to ctx->seed.ovf[tier & 1], counters in set `cset`.
-int launch_tier(SeedRun& R, int tier, i64 n_todo, const i64* pending, int cset, hipStream_t stream, bool defer) {
+// `rnd` (SeedRounds): SEED_ALL, or tier 0 in two launches -- SEED_R12, then SEED_R3 over the same reads on the same stream: it appends to the slot rows, the
+// overflow list and the counter set of the first (its own read cursor: SEED_CTR_SLOT3), so buffers and counters are set up by the first alone.
+int launch_tier(SeedRun& R, int tier, i64 n_todo, const i64* pending, int cset, hipStream_t stream, bool defer, int rnd = SEED_ALL) {
     meme_ctx* ctx = R.ctx;
     // overflow tiers hold a 512-entry SMEM ring per read in LDS: run them 32 lanes per read (8 reads per block)
     int G = tier == 0 ? (int)ctx->group_lanes : 32;
@@ -272,10 +283,12 @@ int launch_tier(SeedRun& R, int tier, i64 n_todo, const i64* pending, int cset, 
         }
     }
     int rc;
-    if ((rc = meme_buf_reserve(ctx, sb, need))) return rc;
-    if ((rc = meme_buf_reserve(ctx, ob, (size_t)n_todo * sizeof(i64)))) return rc;
     unsigned long long* counters = ctx->seed.counter_set(cset);
-    HIP_TRY(hipMemsetAsync(counters, 0, SEED_CTRS * sizeof(unsigned long long), stream));
+    if (rnd != SEED_R3) {
+        if ((rc = meme_buf_reserve(ctx, sb, need))) return rc;
+        if ((rc = meme_buf_reserve(ctx, ob, (size_t)n_todo * sizeof(i64)))) return rc;
+        HIP_TRY(hipMemsetAsync(counters, 0, SEED_CTRS * sizeof(unsigned long long), stream));
+    }
     SeedArgs A;
     A.I = ctx->idx;
     A.packed = (const u64*)ctx->batch.packed.p;
@@ -294,23 +307,26 @@ int launch_tier(SeedRun& R, int tier, i64 n_todo, const i64* pending, int cset, 
     A.tier = tier;
     A.counters = counters;
     A.defer = defer ? 1 : 0;
+    A.carry = rnd == SEED_ALL ? nullptr : (u64*)ctx->seed.carry.p;
+    A.r3cap = (rnd == SEED_R3 && SEED_R3_CAP && R.opt->min_seed_len + 1 <= 32) ? 1 : 0;   // (msl of the third round; above 32 the keys decide no level)
     R.tiers.base[tier] = (const SlotRec*)sb.p;
     R.tiers.cap[tier] = cap;
-    while (G < 32 && seed_lds_bytes(G, R.geo, lcap) > (size_t)160 * 1024) G *= 2;   // long reads: fewer reads per workgroup
+    const bool r3 = rnd == SEED_R3;                                                      // (stages the forward words and mask only, keeps no ring)
+    while (G < 32 && seed_lds_bytes(G, R.geo, lcap, r3) > (size_t)160 * 1024) G *= 2;   // long reads: fewer reads per workgroup
     const int groups = BLOCK / G;
-    size_t lds = seed_lds_bytes(G, R.geo, lcap);
+    size_t lds = seed_lds_bytes(G, R.geo, lcap, r3);
     i64 want = (n_todo + groups - 1) / groups;
     i64 blocks = ctx->seed_blocks > 0 ? ctx->seed_blocks : (i64)ctx->n_cus * ctx->seed_blocks_per_cu;
     if (blocks > want) blocks = want;
     if (blocks < 1) blocks = 1;
-    if (tier == 0) HIP_TRY(hipEventRecord(ctx->seed.ev[SEED_EV_SEARCH0], stream));
+    if (tier == 0 && rnd != SEED_R3) HIP_TRY(hipEventRecord(ctx->seed.ev[SEED_EV_SEARCH0], stream));   // (the stage's events span both launches)
     switch (G) {
-    case 1: return launch_k_seed<1>(stream, A, lds, blocks);
-    case 2: return launch_k_seed<2>(stream, A, lds, blocks);
-    case 4: return launch_k_seed<4>(stream, A, lds, blocks);
-    case 8: return launch_k_seed<8>(stream, A, lds, blocks);
-    case 16: return launch_k_seed<16>(stream, A, lds, blocks);
-    case 32: return launch_k_seed<32>(stream, A, lds, blocks);
+    case 1: return launch_k_seed<1>(stream, A, lds, blocks, rnd);
+    case 2: return launch_k_seed<2>(stream, A, lds, blocks, rnd);
+    case 4: return launch_k_seed<4>(stream, A, lds, blocks, rnd);
+    case 8: return launch_k_seed<8>(stream, A, lds, blocks, rnd);
+    case 16: return launch_k_seed<16>(stream, A, lds, blocks, rnd);
+    case 32: return launch_k_seed<32>(stream, A, lds, blocks, rnd);
     default: meme_set_error("group_lanes must be 1, 2, 4, 8, 16 or 32"); return MEME_E_ARG;
     }
 }
@@ -428,7 +444,14 @@ int seed_tier0(SeedRun& R) {
     S.reseed_rounds = 0;
     if (R.defer && (rc = meme_buf_reserve(ctx, S.pend, (size_t)R.nreads * sizeof(i64)))) return rc;
     if (R.defer && (rc = meme_buf_reserve(ctx, S.blk, (size_t)R.nreads * BLK_PER_READ * 2 * sizeof(BlkRec)))) return rc;
-    if ((rc = launch_tier(R, 0, R.nreads, nullptr, 0, ctx->stream, R.defer))) return rc;
+    // Three rounds: rounds 1-2, then the third round in a launch of its own over the same reads, then the re-seeding kernels -- a read's slots stay in today's
+    // order (first round, third round, re-seeding).  The second launch leaves alone what the first sent to the overflow list and sends there what overflows now.
+    R.split = ctx->seed_r3_split != 0 && R.opt->rounds >= 3 && R.opt->max_mem_intv > 0;
+    if (R.split) {
+        if ((rc = meme_buf_reserve(ctx, S.carry, (size_t)R.nreads * sizeof(u64)))) return rc;
+        if ((rc = launch_tier(R, 0, R.nreads, nullptr, 0, ctx->stream, R.defer, SEED_R12))) return rc;
+        if ((rc = launch_tier(R, 0, R.nreads, nullptr, 0, ctx->stream, R.defer, SEED_R3))) return rc;
+    } else if ((rc = launch_tier(R, 0, R.nreads, nullptr, 0, ctx->stream, R.defer))) return rc;
     if (R.defer) {
         if ((rc = meme_side_stream(ctx, 0)) || (rc = launch_reseed(R)) || (rc = launch_early_overflow(R))) return rc;
         HIP_TRY(hipStreamWaitEvent(ctx->stream, S.emit_ev[1], 0));
@@ -462,6 +485,8 @@ int seed_tier0(SeedRun& R) {
         if (getenv("MEME_SEED_TRACE")) fprintf(stderr, "[meme] seed tier 0: search kernel + re-seeding kernels %.2f ms, of which behind k_seed %.2f ms (%lld lane searches; %lld reads of the "
                                                "overflow tier beside them)\n", ms, a, (long long)h[SEED_CTR_LANE], (long long)(R.n_early < 0 ? 0 : R.n_early));
     }
+    S.r3_counts[0] = R.split ? 1 : 0;
+    S.r3_counts[1] = (long long)h[SEED_CTR_R3_REPEAT];
     tally(R, h);
     return MEME_OK;
 }
@@ -562,6 +587,7 @@ int launch_seed(meme_ctx* ctx, const uint8_t* d_reads, const i64* d_read_off, i6
     ctx->tm.seed_windows = R.windows;
     ctx->tm.seed_reseed_ms = R.ms_reseed;
     ctx->tm.seed_lane_searches = R.lane_searches;
+    S.r3_valid = true;
     return seed_gather(R, out);
 }
 
@@ -683,6 +709,15 @@ extern "C" int meme_debug_reseed_counts(meme_ctx* ctx, int64_t* out, int32_t cap
     return MEME_OK;
 }
 
+extern "C" int meme_debug_seed_r3_counts(meme_ctx* ctx, int64_t* out, int32_t capacity) {
+    if (!ctx || !out) return MEME_E_ARG;
+    const SeedWs& S = ctx->seed;
+    if (!S.r3_valid) { meme_set_error("meme_debug_seed_r3_counts: no seeding call on this ctx yet"); return MEME_E_STATE; }
+    if (capacity < MEME_R3_COUNTS) { meme_set_error("meme_debug_seed_r3_counts: %d values needed", MEME_R3_COUNTS); return MEME_E_CAPACITY; }
+    for (int k = 0; k < MEME_R3_COUNTS; ++k) out[k] = S.r3_counts[k];
+    return MEME_OK;
+}
+
 // Host-pointer variant whose results land in pinned buffers owned by the ctx (valid until the next seeding call on it):
 // no capacity negotiation, and the device-to-host copies are plain DMA transfers.  `reads` / `read_off` may be pageable or
 // pinned (meme_host_alloc).  This is the call a chunk-level binding issues once per -K chunk.
@@ -701,7 +736,7 @@ extern "C" int meme_seed_reserve(meme_ctx* ctx, int64_t nreads, int64_t total_ba
     ChainWs& C = ctx->chain; ExtWs& E = ctx->ext;
     struct { DevBuf* b; size_t bytes; } dev[] = {
         {&B.reads, (size_t)total_bases + 16}, {&B.read_off, (n + 1) * 8}, {&S.slot_cnt, n * 4}, {&S.slot_hits, n * 8},
-        {&S.slot_loc, n * 8}, {&S.counters, 2 * SEED_CTRS * 8}, {&S.pend, n * 8}, {&S.blk, n * BLK_PER_READ * 2 * sizeof(BlkRec)}, {&B.packed, n * stride * 8}, {&S.slots[0], n * (size_t)ctx->smem_cap * sizeof(SlotRec)},
+        {&S.slot_loc, n * 8}, {&S.carry, n * 8}, {&S.counters, 2 * SEED_CTRS * 8}, {&S.pend, n * 8}, {&S.blk, n * BLK_PER_READ * 2 * sizeof(BlkRec)}, {&B.packed, n * stride * 8}, {&S.slots[0], n * (size_t)ctx->smem_cap * sizeof(SlotRec)},
         {&B.smem_off, (n + 1) * 8}, {&B.hit_off, (n + 1) * 8}, {&B.smems, n * 12 * sizeof(meme_mem_tl)}, {&B.hits, n * 24 * 8},
         {&C.chains, n * 3 * sizeof(meme_chain)}, {&C.seeds, n * 6 * sizeof(meme_chain_seed)}};
     for (auto& d : dev) if ((rc = meme_buf_reserve(ctx, *d.b, d.bytes))) return rc;

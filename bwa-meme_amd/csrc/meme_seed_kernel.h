@@ -83,7 +83,19 @@ struct SeedArgs {
     int cap, lcap, tier;
     unsigned long long* counters;   // one counter set (SEED_CTR_*, meme_common.h)
     int defer;                      // 1: re-seeding regions of unique SMEMs are left to k_reseed (tier 0 only)
+    u64* carry;                     // [all reads] what the rounds-1/2 launch hands the round-3 launch (SEED_R12 / SEED_R3): CARRY_OVF, or searches | windows << 32
+    int r3cap;                      // SEED_R3: 1 = a search first compares keys alone (cap 32), and runs again in full where that cannot decide it
 };
+// Rounds a k_seed instantiation runs.  SEED_ALL: the whole read (overflow tiers, rounds < 3, tuning seed_r3_split = 0).  SEED_R12 and SEED_R3: tier 0 in
+// two launches over the same reads -- the first leaves a read's SMEM count, hit count and search tallies per read, the second takes them up, appends to
+// the same slot row and publishes.  A read the first launch sent to the overflow list carries CARRY_OVF: the second leaves it alone (that tier redoes
+// all three rounds), which "no SMEMs" (slot_cnt = 0) could not tell it.
+enum SeedRounds : int { SEED_ALL = 0, SEED_R12 = 1, SEED_R3 = 2 };
+// 0: a measurement build whose round-3 launch compares every search in full (the second launch without the key-only first try)
+#ifndef SEED_R3_CAP
+#define SEED_R3_CAP 1
+#endif
+constexpr u64 CARRY_OVF = ~0ull;
 
 // ---- read packing -------------------------------------------------------------------------------------
 // Layout per read: fw[W] rc[W] nfw[MW] nrc[MW] len|hasN<<31.  A WAVEFRONT packs a run of `rw` consecutive reads (a chunk) and never meets
@@ -314,14 +326,15 @@ __host__ __device__ constexpr int win_entries(int G) { return (WIN_E * G > 64) ?
 // the cold state words and two windows of 16-bit LCPs (the partition window stays cached while edges are followed)
 constexpr int TICKET_CHUNK = 32;     // reads a wavefront draws from the global ticket counter at a time
 
-__host__ __device__ inline size_t seed_lds_group_bytes(int G, int stride, int lcap) {
+// (`qwords`: staged words of a read -- its whole record, stride; SEED_R3: the forward words and the forward N mask, W + MW, and no ring: lcap = 0)
+__host__ __device__ inline size_t seed_lds_group_bytes(int G, int qwords, int lcap) {
     const int groups = BLOCK / G;
     const int W = win_entries(G) * G;
-    return (((size_t)groups * (SEED_QUERY_LDS ? stride * 8 : 0) + (size_t)groups * (2 * lcap + ST_WORDS + (W + 1) / 2) * sizeof(int)) + 7) & ~(size_t)7;
+    return (((size_t)groups * (SEED_QUERY_LDS ? qwords * 8 : 0) + (size_t)groups * (2 * lcap + ST_WORDS + (W + 1) / 2) * sizeof(int)) + 7) & ~(size_t)7;
 }
 // + per wavefront: the ticket chunk it is handing out (count, base)
-inline size_t seed_lds_bytes(int G, const PackGeom& geo, int lcap) {
-    return seed_lds_group_bytes(G, geo.stride, lcap) + (size_t)(BLOCK / 64) * 16;
+inline size_t seed_lds_bytes(int G, const PackGeom& geo, int lcap, bool r3 = false) {
+    return seed_lds_group_bytes(G, r3 ? geo.W + geo.MW : geo.stride, r3 ? 0 : lcap) + (size_t)(BLOCK / 64) * 16;
 }
 
 // ---- compare: compare_read_and_ref_binary* (:226-601) ---------------------------------------------------
@@ -471,7 +484,23 @@ __device__ __forceinline__ int first_n(q_u64 mask, bool has_n, int from, int l_s
 //   PH_EDGE_UP  pred = LCP(suffix, query) >= L (above the run)   flip = one past its last slot
 // [lo, hi] brackets the flip (lo: highest slot known true, hi: lowest known false); a window that does not
 // contain it moves the bracket and the next window gallops (step doubling) or bisects.
-template <int G>
+//
+// RND (SeedRounds) fixes at compile time which rounds the body holds: the states, kinds and modes of the others are gone from the instantiation
+// (`if constexpr`, or a condition that folds), not skipped at run time -- the loop body is issued whole every iteration, whatever a read needs.
+// SEED_R3 is mode 2 alone on the forward strand: no rc words, no SMEM ring, no zig-zag or re-seeding control, no deferral.
+//
+// Key-only compares (SEED_R3, A.r3cap, msl <= 32).  A third-round query of more than 32 bases is first searched as if it ended after 32: every
+// compare is settled by the entries' 64-bit keys, no text word is fetched.  With LCPs capped at 32 all true levels >= 32 merge into one level "32"
+// whose run is the run of the lowest true level >= 32.  The walk stops at the first level whose run holds >= min_intv suffixes, or above the first
+// next level < msl <= 32; the runs of the true levels >= 32 all lie inside the run at "32".  So if that run holds fewer than min_intv suffixes none of
+// them stops the uncapped walk, which arrives at the lowest true level >= 32 with the same run, the same neighbours (their LCPs are < 32: the cap
+// does not touch them) and goes on below exactly as the capped walk does: same `nxt < msl` stop, same LF_HAVE_LAST interval from there down (the one
+// it may hold ON arrival is read only when that run reaches min_intv), same r_L, r_start, r_count; and r_T is read only for a run of one suffix,
+// which is the slot both walks sit on.  If the run at "32" reaches min_intv suffixes the levels above 32 matter (r_L = L + 1 for some L >= 32 and
+// the interval before it): the search is run again from its first window with the full cap.  Both tries are one search; the second's windows count.
+// A read that had to run a search again lies in repeated sequence, where its next pivots usually meet the same families: the rest of its searches
+// compare in full at once (`r3full`), so a read pays for at most one wasted try.
+template <int G, int RND = SEED_ALL>
 #ifndef SEED_MIN_WAVES
 #define SEED_MIN_WAVES 5
 #endif
@@ -487,25 +516,26 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
     const int t = threadIdx.x & (G - 1);
     const int gbase = lane & ~(G - 1);
     const int stride = A.geo.stride, PW = A.geo.W, MW = A.geo.MW;
-    const int cap = A.cap, lcap = A.lcap;
+    const int cap = A.cap, lcap = RND == SEED_R3 ? 0 : A.lcap;
+    const int qwords = RND == SEED_R3 ? PW + MW : stride;      // words of a read staged in LDS (SEED_R3: fw[PW] nfw[MW])
 #if SEED_QUERY_LDS
-    u64* rd = reinterpret_cast<u64*>(smem_raw) + (size_t)gib * stride;
+    u64* rd = reinterpret_cast<u64*>(smem_raw) + (size_t)gib * qwords;
     const q_u64 fw = (lds_u64)rd;
 #else
     q_u64 fw = (q_u64)A.packed;                          // the current read's record: fw[PW] rc[PW] nfw[MW] nrc[MW] len
 #endif
 #define rcs (fw + PW)
-#define nfw (fw + 2 * PW)
+#define nfw (fw + ((RND == SEED_R3 && SEED_QUERY_LDS) ? PW : 2 * PW))
 #define nrc (fw + 2 * PW + MW)
     // per group after the packed reads: SMEM ring (2 ints per entry), cold state, two windows of 16-bit LCPs
-    const lds_int ring = (lds_int)(reinterpret_cast<int*>(smem_raw + (SEED_QUERY_LDS ? (size_t)GROUPS * stride * 8 : 0)) +
+    const lds_int ring = (lds_int)(reinterpret_cast<int*>(smem_raw + (SEED_QUERY_LDS ? (size_t)GROUPS * qwords * 8 : 0)) +
                                    (size_t)gib * (2 * lcap + ST_WORDS + (W + 1) / 2));
     const lds_int sm_se = ring;               // start | end << 16
     const lds_int sm_cnt = ring + lcap;
     const lds_int st = ring + 2 * lcap;
     const lds_u16 wl = (lds_u16)(st + ST_WORDS);
     // the wavefront's ticket chunk: [0] tickets handed out, [2..3] first ticket
-    const lds_int wv = (lds_int)(reinterpret_cast<int*>(smem_raw + seed_lds_group_bytes(G, stride, lcap)) + (threadIdx.x >> 6) * 4);
+    const lds_int wv = (lds_int)(reinterpret_cast<int*>(smem_raw + seed_lds_group_bytes(G, qwords, lcap)) + (threadIdx.x >> 6) * 4);
     const glb_ent sa = (glb_ent)A.I.sa;
     const glb_u64 pac = (glb_u64)A.I.pac;
     const glb_rmi l2 = (glb_rmi)A.I.l2, l1 = (glb_rmi)A.I.l1;
@@ -524,8 +554,10 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
     int pivot = 0, l_seq = 0, msl = A.opt.min_seed_len, min_intv = 1;
     bool has_n = false;
     // the request in flight
-    int q_kind = 0, q_mode = 0, off = 0, vlen = 0, capc = 0;
+    int q_kind = RND == SEED_R3 ? K_R3 : 0, q_mode = RND == SEED_R3 ? 2 : 0, off = 0, vlen = 0, capc = 0;
     bool q_rc = false, q_exact = false;
+    bool capped = false, redo = false, r3full = false;      // SEED_R3: the search in flight compares keys alone / is to run again in full / this read no longer tries keys first
+    unsigned acc_repeats = 0;
     i64 base = 0, lo = -1, hi = n;
     int stepk = 0;
     u64 wq = 0;
@@ -552,6 +584,7 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
             bool have = false;
 #define AT(pc_) (!have && pc == (pc_))
             do {
+              if constexpr (RND != SEED_R3) {
                 if (AT(PC_ZZ_TOP)) {       // zig-zag loop head (:1724-1737, :1969)
                     if (st[ST_ZZ_SP] >= st[ST_ZZ_NEXT] || ++st[ST_ZZ_GUARD] > 4 * l_seq + 16) pc = PC_ZZ_END;
                     else if (FLAG(F_ZZ_CHECK) && has_n && is_n(nfw, st[ST_ZZ_SP])) {
@@ -602,7 +635,7 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                     }
                 }
                 if (AT(PC_ALLPOS_TOP)) {   // Learned_getSMEMsAllPosOneThread loop head (:916) + step1 entry (:1691-1723)
-                    if (pivot >= l_seq || ++st[ST_AP_GUARD] > 4 * l_seq + 16) pc = PC_R3_INIT;
+                    if (pivot >= l_seq || ++st[ST_AP_GUARD] > 4 * l_seq + 16) pc = RND == SEED_R12 ? PC_DONE : PC_R3_INIT;
                     else {
                         st[ST_BEFORE] = st[ST_N_SMEMS]; st[ST_SM_BASE] = st[ST_BEFORE]; SETFLAG(F_REC, true);
                         if (has_n && is_n(nfw, pivot)) {
@@ -615,8 +648,10 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                         } else { q_kind = K_S1_RIGHT; have = true; }
                     }
                 }
-                if (AT(PC_R3_INIT)) {      // src/bwamem.cpp:1385-1394
-                    if (A.opt.rounds >= 3 && A.opt.max_mem_intv > 0 && !FLAG(F_LDS_OVF)) {
+              }
+              if constexpr (RND != SEED_R12) {
+                if (AT(PC_R3_INIT)) {      // src/bwamem.cpp:1385-1394 (SEED_R3: the host launches it under this condition)
+                    if (RND == SEED_R3 || (A.opt.rounds >= 3 && A.opt.max_mem_intv > 0 && !FLAG(F_LDS_OVF))) {
                         min_intv = A.opt.max_mem_intv;
                         msl = A.opt.min_seed_len + 1;
                         pivot = 0;
@@ -633,17 +668,21 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                         break;
                     }
                 }
+              }
                 if (AT(PC_DONE)) {         // publish the read's SMEM count / hit count; its slots are already written
                     const unsigned long long ticket = ((unsigned long long)(unsigned)st[ST_TICKET_HI] << 32) | (unsigned)st[ST_TICKET_LO];
-                    const bool ovf = st[ST_N_SMEMS] > cap || FLAG(F_LDS_OVF);
+                    const bool ovf = st[ST_N_SMEMS] > cap || (RND != SEED_R3 && FLAG(F_LDS_OVF));
                     if (t == 0) {
                         const i64 rid = A.pending ? A.pending[ticket] : (i64)ticket;
                         A.slot_cnt[rid] = ovf ? 0 : st[ST_N_SMEMS];
                         A.slot_hits[rid] = ovf ? 0 : LD64(ST_HITS_LO);
-                        A.slot_loc[rid] = ((i64)A.tier << 40) | (i64)ticket;
+                        if constexpr (RND != SEED_R3) A.slot_loc[rid] = ((i64)A.tier << 40) | (i64)ticket;
+                        // the read's tallies travel with it: they count once, in the launch (or tier) that is done with the read
+                        if constexpr (RND == SEED_R12) A.carry[rid] = ovf ? CARRY_OVF : ((u64)(unsigned)st[ST_SEARCHES] | ((u64)(unsigned)st[ST_WINDOWS] << 32));
                         if (ovf) A.ovf_list[atomicAdd(&A.counters[SEED_CTR_OVERFLOW], 1ull)] = rid;
                     }
-                    if (!ovf) { acc_searches += (unsigned)st[ST_SEARCHES]; acc_windows += (unsigned)st[ST_WINDOWS]; }
+                    if constexpr (RND != SEED_R12)
+                        if (!ovf) { acc_searches += (unsigned)st[ST_SEARCHES]; acc_windows += (unsigned)st[ST_WINDOWS]; }
                     pc = PC_FETCH;
                 }
                 if (AT(PC_FETCH)) {        // pull the next read (reads differ 3x in cost: dynamic hand-out, no static deal)
@@ -663,7 +702,7 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                         const int kreq = __popcll(mo), alloc = kreq > TICKET_CHUNK ? kreq : TICKET_CHUNK;
                         unsigned long long nb = 0;
                         if (lane == first) {
-                            nb = atomicAdd(&A.counters[SEED_CTR_SLOT], (unsigned long long)alloc);
+                            nb = atomicAdd(&A.counters[RND == SEED_R3 ? SEED_CTR_SLOT3 : SEED_CTR_SLOT], (unsigned long long)alloc);
                             const unsigned long long wb = nb + (unsigned)(alloc - TICKET_CHUNK);
                             wv[0] = kreq - (alloc - TICKET_CHUNK); wv[2] = (int)(unsigned)(wb & 0xffffffffull); wv[3] = (int)(wb >> 32);
                         }
@@ -675,17 +714,32 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                     else {
                         const i64 rid = A.pending ? A.pending[ticket] : (i64)ticket;
                         const u64* src = A.packed + rid * stride;
+                        u64 carry = 0;
+                        int c0 = 0;
+                        i64 h0 = 0;
+                        if constexpr (RND == SEED_R3) { carry = A.carry[rid]; c0 = A.slot_cnt[rid]; h0 = A.slot_hits[rid]; }   // what the first launch left
 #if SEED_QUERY_LDS
                         // stage the packed read in LDS (coalesced 8-byte loads; the length word travels in the same
                         // batch of loads) and clear the cold state
-                        const int lw = (stride - 1) % G;               // the lane that loads the length word
                         u64 lenw = 0;
-                        for (int k = t; k < stride; k += G) {
-                            u64 v = src[k];
-                            rd[k] = v;
-                            if (k == stride - 1) lenw = v;
+                        if constexpr (RND == SEED_R3) {
+                            // only what the third round reads: staged word j = fw[j], then nfw[j - PW]; one word more = the length word (not kept)
+                            const int lw = qwords % G;
+                            for (int j = t; j <= qwords; j += G) {
+                                const int k = j < PW ? j : (j < qwords ? j + PW : stride - 1);
+                                u64 v = src[k];
+                                if (j < qwords) rd[j] = v; else lenw = v;
+                            }
+                            lenw = (u64)(unsigned)__shfl((int)lenw, gbase + lw);
+                        } else {
+                            const int lw = (stride - 1) % G;               // the lane that loads the length word
+                            for (int k = t; k < stride; k += G) {
+                                u64 v = src[k];
+                                rd[k] = v;
+                                if (k == stride - 1) lenw = v;
+                            }
+                            lenw = (u64)(unsigned)__shfl((int)lenw, gbase + lw);
                         }
-                        lenw = (u64)(unsigned)__shfl((int)lenw, gbase + lw);
 #else
                         // the searches read the record in place; only its last word (length, "has an N" flag) is needed now
                         fw = (q_u64)src;
@@ -698,16 +752,28 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                         if (l_seq <= 0 || l_seq > MAX_READ_LEN) {
                             // the reference exits on reads longer than LEARNED_MAX_READ_LEN (src/bwamem.cpp:1259-1262);
                             // here such a read yields no seeds and is flagged through slot_cnt = -1
-                            if (t == 0) { A.slot_cnt[rid] = l_seq > MAX_READ_LEN ? -1 : 0; A.slot_hits[rid] = 0; A.slot_loc[rid] = 0; }
+                            // (SEED_R3: the first launch wrote them)
+                            if constexpr (RND != SEED_R3)
+                                if (t == 0) { A.slot_cnt[rid] = l_seq > MAX_READ_LEN ? -1 : 0; A.slot_hits[rid] = 0; A.slot_loc[rid] = 0; }
                             // stays in PC_FETCH
+                        } else if (RND == SEED_R3 && carry == CARRY_OVF) {
+                            // the first launch sent the read to the overflow list: stays in PC_FETCH
                         } else {
                             st[ST_TICKET_LO] = (int)(unsigned)(ticket & 0xffffffffull);
                             st[ST_TICKET_HI] = (int)(ticket >> 32);
-                            pivot = 0; msl = A.opt.min_seed_len; min_intv = 1;
-                            pc = PC_ALLPOS_TOP;
-                            if (!(has_n && is_n(nfw, 0))) {                       // first step of PC_ALLPOS_TOP at pivot 0, inlined
-                                st[ST_AP_GUARD] = 1; SETFLAG(F_REC, true);
-                                q_kind = K_S1_RIGHT; have = true;
+                            if constexpr (RND == SEED_R3) {
+                                // go on where the first launch stopped: its SMEMs, hits and tallies
+                                st[ST_N_SMEMS] = c0; ST64(ST_HITS_LO, h0);
+                                st[ST_SEARCHES] = (int)(unsigned)(carry & 0xffffffffull); st[ST_WINDOWS] = (int)(unsigned)(carry >> 32);
+                                r3full = false;
+                                pc = PC_R3_INIT;
+                            } else {
+                                pivot = 0; msl = A.opt.min_seed_len; min_intv = 1;
+                                pc = PC_ALLPOS_TOP;
+                                if (!(has_n && is_n(nfw, 0))) {                       // first step of PC_ALLPOS_TOP at pivot 0, inlined
+                                    st[ST_AP_GUARD] = 1; SETFLAG(F_REC, true);
+                                    q_kind = K_S1_RIGHT; have = true;
+                                }
                             }
                         }
                     }
@@ -716,7 +782,8 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
 #undef AT
             if (pc == PC_EXIT) {
                 if (t == 0) {
-                    atomicAdd(&A.counters[SEED_CTR_SEARCHES], (unsigned long long)acc_searches); atomicAdd(&A.counters[SEED_CTR_WINDOWS], (unsigned long long)acc_windows);
+                    if constexpr (RND != SEED_R12) { atomicAdd(&A.counters[SEED_CTR_SEARCHES], (unsigned long long)acc_searches); atomicAdd(&A.counters[SEED_CTR_WINDOWS], (unsigned long long)acc_windows); }
+                    if constexpr (RND == SEED_R3) if (acc_repeats) atomicAdd(&A.counters[SEED_CTR_R3_REPEAT], (unsigned long long)acc_repeats);
 #ifdef SEED_PROF
                     for (int k = 0; k < 8; ++k) atomicAdd(&A.counters[SEED_CTR_PROF + k], (unsigned long long)prof[k]);
 #endif
@@ -726,15 +793,24 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
             newreq = true;
         }
         PROF_MARK(0);
-        if (newreq) {
+        if (newreq || (RND == SEED_R3 && redo)) {
             // ---- the request: query = bases [off, off+vlen) of one strand; first window at the model's prediction
-            q_rc = q_kind == K_ZZ_LEFT;
-            off = q_rc ? l_seq - 1 - pivot : pivot;
-            vlen = first_n(q_rc ? nrc : nfw, has_n, off, l_seq) - off;
-            q_exact = q_kind == K_S1_RIGHT || q_kind == K_ZZ_RIGHT || q_kind == K_OP_SMEM;
-            q_mode = q_kind == K_R3 ? 2 : ((q_exact || min_intv != 1) ? 1 : 0);
-            st[ST_SEARCHES] = st[ST_SEARCHES] + 1;
-            wq = ext_l(q_rc ? rcs : fw, off);                 // first 32 bases of the query: every window compares against it
+            if constexpr (RND == SEED_R3) {                       // mode 2 on the forward strand, nothing else
+                off = pivot;
+                vlen = first_n(nfw, has_n, off, l_seq) - off;
+                // both tries are one search.  The repeat goes through the whole request again -- N scan, query word, model lookup, first window -- although only the
+                // bracket and the cap change: it pays the model record's line a second time, for one request block in the kernel instead of two
+                if (redo) ++acc_repeats; else st[ST_SEARCHES] = st[ST_SEARCHES] + 1;
+                wq = ext_l(fw, off);
+            } else {
+                q_rc = q_kind == K_ZZ_LEFT;
+                off = q_rc ? l_seq - 1 - pivot : pivot;
+                vlen = first_n(q_rc ? nrc : nfw, has_n, off, l_seq) - off;
+                q_exact = q_kind == K_S1_RIGHT || q_kind == K_ZZ_RIGHT || q_kind == K_OP_SMEM;
+                q_mode = (RND == SEED_ALL && q_kind == K_R3) ? 2 : ((q_exact || min_intv != 1) ? 1 : 0);
+                st[ST_SEARCHES] = st[ST_SEARCHES] + 1;
+                wq = ext_l(q_rc ? rcs : fw, off);             // first 32 bases of the query: every window compares against it
+            }
             u64 key = wq;
             if (vlen < 32) key |= (~0ull) >> (2 * vlen);          // T-pad short queries like Tokenization (:813-817)
             u64 err;
@@ -757,12 +833,22 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
             if (base < 0) base = 0;
             if (base > n - W) base = n - W;
             lo = -1; hi = n; stepk = 0; capc = vlen;
+            if constexpr (RND == SEED_R3) {                       // first try on the keys alone (see the kernel's head)
+                if (redo) r3full = true;
+                capped = A.r3cap != 0 && !r3full && vlen > 32;
+                if (capped) capc = 32;
+                redo = false;
+            }
             phase = PH_PART;
         }
+        // what the request in flight is, as far as the instantiation leaves it open
+        const bool exact = RND != SEED_R3 && q_exact;
+        const bool kind_r3 = RND == SEED_R3 || (RND == SEED_ALL && q_kind == K_R3);
+        const bool mode2 = RND == SEED_R3 || (RND == SEED_ALL && q_mode == 2);
         PROF_MARK(1);
 
         // ================= window: E coalesced loads of G entries each, issued together, then the compares ===========
-        const q_u64 s = q_rc ? rcs : fw;
+        const q_u64 s = (RND != SEED_R3 && q_rc) ? rcs : fw;
         int lcp[E];
         bool less[E];
         u64 ep[E];
@@ -808,13 +894,13 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                 const int c = (lm >= lp) ? P - 1 : P;
                 L = lm >= lp ? lm : lp;
                 r_L = L; r_start = base + c; r_count = 1;
-                if (q_exact || q_kind == K_R3) {              // the kinds that emit: an interval of ONE suffix is this slot, and its position is here
+                if (exact || kind_r3) {                       // the kinds that emit: an interval of ONE suffix is this slot, and its position is here
                     u64 tc = 0;
 #pragma unroll
                     for (int e = 0; e < E; ++e) tc = (e * G + t == c) ? ep[e] : tc;
                     r_T = (i64)(((u64)(unsigned)group_or<G>((int)(tc >> 32)) << 32) | (u64)(unsigned)group_or<G>((int)(unsigned)tc));
                 }
-                if (q_mode == 0 || (q_mode == 2 && L < msl)) finished = true;       // (:1204-1208)
+                if ((RND != SEED_R3 && q_mode == 0) || (mode2 && L < msl)) finished = true;       // (:1204-1208)
                 else {
                     s_edge = e_edge = base + c;
                     lf = LF_NEED_LO | LF_NEED_HI;
@@ -830,7 +916,7 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
         } else {
             if (P == W) lo = base + W - 1; else hi = base;
             bool stop = false;
-            if (phase != PH_PART && !q_exact) {
+            if (phase != PH_PART && !exact) {
                 // the interval is not emitted at the level where the walk stops (left extensions, third round): it is
                 // enough to know that it reached min_intv suffixes
                 s_edge = LD64(ST_SE_LO); e_edge = LD64(ST_EE_LO);
@@ -895,10 +981,12 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                 }
                 const i64 cnt = e_edge - s_edge + 1;
                 const int nxt = nb_lo > nb_hi ? nb_lo : nb_hi;
-                if (q_mode == 1) {                                  // (:2568-2573, :2936-2940)
+                if (!mode2) {                                       // mode 1 (:2568-2573, :2936-2940)
                     if (cnt >= (i64)min_intv) { r_L = L; r_start = s_edge; r_count = cnt; finished = true; break; }
                 } else {
                     if (cnt >= (i64)min_intv) {                     // :1243-1251
+                        if constexpr (RND == SEED_R3)
+                            if (capped && L >= 32) { redo = true; break; }   // the levels above 32 decide: again, in full
                         if (lf & LF_HAVE_LAST) { r_count = LD64(ST_LAST_CNT_LO); r_start = LD64(ST_LAST_S_LO); }
                         else { r_count = cnt; r_start = s_edge; }
                         r_L = L + 1;
@@ -914,11 +1002,11 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                 lf = (lf & LF_HAVE_LAST) | ((nb_lo >= L && s_edge > 0) ? LF_NEED_LO : 0) | ((nb_hi >= L && e_edge < n - 1) ? LF_NEED_HI : 0);
             }
             if (finished) {
-                if (q_mode == 2) {
+                if (mode2) {
                     r_emit = r_count < (i64)min_intv;              // :1265
                     if (r_L < msl) r_L = msl;
                 }
-            } else {
+            } else if (!(RND == SEED_R3 && redo)) {
                 capc = L;
                 st[ST_L] = L; st[ST_NB_LO] = nb_lo; st[ST_NB_HI] = nb_hi; st[ST_LF] = lf;
                 ST64(ST_SE_LO, s_edge); ST64(ST_EE_LO, e_edge); ST64(ST_CB_LO, cb);
@@ -934,7 +1022,8 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
             bool emit = false;
             const int e_start = pivot;
             int e_end = pivot;
-            switch (q_kind) {
+            if constexpr (RND == SEED_R3) { emit = r_emit; e_end = pivot + r_L; }
+            else switch (q_kind) {
             case K_S1_RIGHT:          // (:1852-1893)
             case K_ZZ_RIGHT:          // (:1846-1848)
             case K_OP_SMEM:           // (:2093-2125)
@@ -949,7 +1038,7 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                 pc = PC_ZZ_TOP;
                 break;
             default:                  // K_R3 (:1204-1208, :1265-1281)
-                emit = r_emit; e_end = pivot + r_L;
+                if constexpr (RND == SEED_ALL) { emit = r_emit; e_end = pivot + r_L; }
                 break;
             }
             if (emit) {               // kv_push of mem_tl + hits (:2639-2657, :1266-1277)
@@ -961,7 +1050,7 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                 const bool have_pos = r_count == 1 && r_T >= 0 && !cache_in_lds;
                 // (Not where the locus lies in repeated sequence -- its suffix shares min_seed_len bases or more with a neighbour in the suffix
                 // array: there the table would send nearly every search of the region back, and the searches are better done here.)
-                const bool defer = have_pos && A.defer != 0 && FLAG(F_REC) && ns < DEFER_MAX_K && ns < cap && A.opt.rounds >= 2 &&
+                const bool defer = RND != SEED_R3 && have_pos && A.defer != 0 && FLAG(F_REC) && ns < DEFER_MAX_K && ns < cap && A.opt.rounds >= 2 &&
                                    e_end - e_start >= A.opt.split_len && A.opt.split_width >= 1 && nb_lo < msl && nb_hi < msl;
                 if (ns < cap && t == 0) {
                     const unsigned long long ticket = ((unsigned long long)(unsigned)st[ST_TICKET_HI] << 32) | (unsigned)st[ST_TICKET_LO];
@@ -970,7 +1059,7 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                     sr.sa_start = have_pos ? (SLOT_POS | (defer ? SLOT_DEFER : 0ll) | r_T) : r_start;
                     A.slots[(i64)ticket * cap + ns] = sr;
                 }
-                if (FLAG(F_REC)) {
+                if constexpr (RND != SEED_R3) if (FLAG(F_REC)) {
                     const int k = ns - st[ST_SM_BASE];
                     if (k < lcap) {
                         // group-uniform redundant LDS stores (every lane writes the same value): no hand-off needed
@@ -984,11 +1073,12 @@ __global__ void __launch_bounds__(BLOCK, (G >= 4 ? SEED_MIN_WAVES : G)) k_seed(S
                 h += LD64(ST_HITS_LO);
                 ST64(ST_HITS_LO, h);
             }
-            switch (q_kind) {
+            if constexpr (RND == SEED_R3) { pivot = pivot + (r_L < msl ? msl : r_L); pc = PC_R3_TOP; }
+            else switch (q_kind) {
             case K_S1_RIGHT: pivot = pivot + r_L; pc = PC_AFTER_STEP1; break;
             case K_ZZ_RIGHT: pivot = pivot + r_L; st[ST_ZZ_SP] = pivot; pc = PC_ZZ_TOP; break;
             case K_OP_SMEM: pivot = pivot + r_L; pc = PC_R2_AFTER; break;
-            case K_R3: pivot = pivot + (r_L < msl ? msl : r_L); pc = PC_R3_TOP; break;
+            case K_R3: if constexpr (RND == SEED_ALL) { pivot = pivot + (r_L < msl ? msl : r_L); pc = PC_R3_TOP; } break;
             default: break;
             }
             phase = PH_CTRL;

@@ -235,7 +235,7 @@ EXPORTS = ["meme_device_count", "meme_ctx_create", "meme_ctx_destroy", "meme_las
            "meme_host_free", "meme_stage_pack_text", "meme_stage_pos5_from_sa", "meme_stage_build_entries", "meme_stage_build_plcp",
            "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_primary_batch_host", "meme_primary_batch_device", "meme_finish_batch_host", "meme_finish_batch_device", "meme_pair_batch_host", "meme_pair_batch_device", "meme_seed_batch_device",
            "meme_bsw_batch", "meme_bsw_batch_device", "meme_get_timings", "meme_set_tuning", "meme_debug_packed_reads",
-           "meme_debug_reseed_counts", "meme_debug_sa_stats", "meme_debug_scan_exclusive"]
+           "meme_debug_reseed_counts", "meme_debug_seed_r3_counts", "meme_debug_sa_stats", "meme_debug_scan_exclusive"]
 
 RESEED_MAX_ROUNDS = 8                    # meme_hip.h: MEME_RESEED_COUNTS = RESEED_MAX_ROUNDS + 6 values from meme_debug_reseed_counts
 RESEED_COUNTS = RESEED_MAX_ROUNDS + 6
@@ -445,6 +445,13 @@ class Context:
         st = RESEED_MAX_ROUNDS                         # layout: one list length per round, then stage 0 / 1 / 2, no interval, walked, neighbour probes
         return {"rounds": [int(v) for v in out[:rounds.value]], "stage": [int(v) for v in out[st:st + 3]], "no_interval": int(out[st + 3]),
                 "walked": int(out[st + 4]), "neighbour_probes": int(out[st + 5])}
+
+    def debug_seed_r3_counts(self):
+        """meme_debug_seed_r3_counts: tier 0 of the last seeding call.  Returns a dict: `split` (the third round ran in a launch of its own), `repeats`
+        (third-round searches run twice: keys alone, then in full)."""
+        out = np.zeros(2, dtype=np.int64)
+        _check(lib().meme_debug_seed_r3_counts(C.c_void_p(self.h), _p(out), C.c_int32(out.size)))
+        return {"split": bool(out[0]), "repeats": int(out[1])}
 
     def debug_sa_stats(self):
         """meme_debug_sa_stats: what the last meme_sa_build_device on this ctx did.  Returns a dict: `k_pad` (bases T behind the text), `groups` (bucket

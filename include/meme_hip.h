@@ -526,7 +526,7 @@ typedef struct {
     int64_t gcig_class_jobs[6];   /* the last CIGAR call's jobs by kernel: 16-lane groups, 32-lane groups, a wavefront each in 64-column chunks, the gap-free shortcut, 64-lane "groups"; the last entry is always 0 (the two-columns-per-lane kernel it counted was removed) */
 } meme_timings;
 int meme_get_timings(meme_ctx* ctx, meme_timings* out);
-int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value);   /* "group_lanes", "seed_blocks_per_cu", "seed_blocks", "smem_cap", "bsw_blocks", "bsw_lane_min_pairs", "chain_wave_tiers", "chain_lane_hits", "chain_light_hits", "seed_defer", "ext_live_only" (1: meme_extend_last_batch_host hands over only the records mem_kernel2_core keeps, src/bwamem.cpp:1680-1693 -- qe > qb, in order -- instead of one per chained seed with the purged ones marked; the stage then also runs in rounds -- "ext_rounds" (default 1; 0: off): a read's seeds are taken in extension order, tested against the read's surviving alignments first and extended only if they survive, one seed per read and round, after that many rounds everything still ahead at once: the same surviving records, without the banded SW of seeds the purge drops), "gcig_groups" (1, default: CIGAR jobs whose band has at most 16 / 32 / 64 columns run 4 / 2 / 1 to a wavefront with one chunk per row; 0: one wavefront per job in 64-column chunks; any other value: MEME_E_ARG), "gcig_zcap" (>= 0: bytes of LDS a CIGAR job keeps for its backtrack matrix or the window it is walked back through; default: chosen per call, 8192 where a typical matrix of the batch fits, else 2048; results do not depend on it), "ext_census" (1: meme_extend_last_batch_host also counts the extension jobs whose query is a prefix of its target), "max_batch" (> 0: meme_extend_last_batch_host / meme_global_batch_host refuse larger batches with MEME_E_CAPACITY), "ext_slab_jobs" (default 8 Mi, at least 1: the extension stage poses and aligns its jobs in slabs of whole reads with at most this many jobs per side, and at least one read, each -- a bound, and how the tests reach the multi-slab path; same records), "ext_split" (default 1: the extension stage's kernels that walk a read's chains run eight lanes per read for reads with at most 8 chained seeds and a wavefront per read for the others; 0: a wavefront per read throughout; same records), "bsw_circ" (default 1: the lane-per-pair banded-SW kernel keeps the columns of queries longer than its band in a ring of 2w + 2 columns -- same results, more wavefronts per CU; 0: one LDS word per query column as before), "sam_max_batch" (> 0: meme_sam_format_batch_host refuses more record slots than this with MEME_E_CAPACITY; the caller formats in pieces), "helper_blocks" (> 0: at most this many workgroups in the read packer, the offsets scan and the hit gather of a seeding call, as "seed_blocks" does for the search kernel -- how the tests drive their loops round with small batches; 0, default: no cap; same results), "primary_split" (default 8, its maximum: meme_primary_batch_host / _device run reads with at most this many records eight lanes to a read with the records in registers, reads with more a wavefront each with the records in HBM; 0 sends every non-empty read to the wavefront tier; larger values count as 8; same results), "primary_blocks" (> 0: at most this many workgroups in each kernel of that stage, so that a small batch goes round their grid-stride loops; 0, default: no cap; same results), "finish_blocks" (> 0: the same cap for the kernels of meme_finish_batch_host / _device; 0, default: no cap; same results), "finish_lds_recs" (> 0: reads handed over with more records than this are walked by the wavefront tier of that stage in a workspace in HBM instead of in LDS; 0, default, and anything above it: 128; same results), "pair_split" (default 8, its maximum: meme_pair_batch_host / _device run pairs with at most this many keys -- records of both ends that take part -- eight lanes to a pair with the keys in registers, pairs with more a wavefront each; 0 sends every non-empty pair to the wavefront tier; larger values count as 8; same results), "pair_blocks" (> 0: at most this many workgroups in each kernel of that stage; 0, default: no cap; same results), "pair_lds_keys" (> 0: the wavefront tier keeps this many of a pair's sorted keys in LDS and the rest in a workspace in HBM; 0, default, and anything above it: 512; same results), "sa_chunk" (default 2^28, at least 1: meme_sa_build_device sorts the 256 four-base buckets in groups of consecutive buckets with at most this many suffixes each -- a bucket alone may exceed it; a bound of the workspace, and how the tests reach the multi-group path with small texts; same array), "sa_piece" (default 2^28, at least 1: that call looks for the suffix-array entries of the padding in pieces of this many slots; same array) */
+int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value);   /* "group_lanes", "seed_blocks_per_cu", "seed_blocks", "smem_cap", "bsw_blocks", "bsw_lane_min_pairs", "chain_wave_tiers", "chain_lane_hits", "chain_light_hits", "seed_defer", "seed_r3_split" (1, default: with three rounds the third runs in a search-kernel launch of its own behind rounds 1-2, its searches on the 64-bit keys alone first; 0: one launch; same seeds and counts either way), "ext_live_only" (1: meme_extend_last_batch_host hands over only the records mem_kernel2_core keeps, src/bwamem.cpp:1680-1693 -- qe > qb, in order -- instead of one per chained seed with the purged ones marked; the stage then also runs in rounds -- "ext_rounds" (default 1; 0: off): a read's seeds are taken in extension order, tested against the read's surviving alignments first and extended only if they survive, one seed per read and round, after that many rounds everything still ahead at once: the same surviving records, without the banded SW of seeds the purge drops), "gcig_groups" (1, default: CIGAR jobs whose band has at most 16 / 32 / 64 columns run 4 / 2 / 1 to a wavefront with one chunk per row; 0: one wavefront per job in 64-column chunks; any other value: MEME_E_ARG), "gcig_zcap" (>= 0: bytes of LDS a CIGAR job keeps for its backtrack matrix or the window it is walked back through; default: chosen per call, 8192 where a typical matrix of the batch fits, else 2048; results do not depend on it), "ext_census" (1: meme_extend_last_batch_host also counts the extension jobs whose query is a prefix of its target), "max_batch" (> 0: meme_extend_last_batch_host / meme_global_batch_host refuse larger batches with MEME_E_CAPACITY), "ext_slab_jobs" (default 8 Mi, at least 1: the extension stage poses and aligns its jobs in slabs of whole reads with at most this many jobs per side, and at least one read, each -- a bound, and how the tests reach the multi-slab path; same records), "ext_split" (default 1: the extension stage's kernels that walk a read's chains run eight lanes per read for reads with at most 8 chained seeds and a wavefront per read for the others; 0: a wavefront per read throughout; same records), "bsw_circ" (default 1: the lane-per-pair banded-SW kernel keeps the columns of queries longer than its band in a ring of 2w + 2 columns -- same results, more wavefronts per CU; 0: one LDS word per query column as before), "sam_max_batch" (> 0: meme_sam_format_batch_host refuses more record slots than this with MEME_E_CAPACITY; the caller formats in pieces), "helper_blocks" (> 0: at most this many workgroups in the read packer, the offsets scan and the hit gather of a seeding call, as "seed_blocks" does for the search kernel -- how the tests drive their loops round with small batches; 0, default: no cap; same results), "primary_split" (default 8, its maximum: meme_primary_batch_host / _device run reads with at most this many records eight lanes to a read with the records in registers, reads with more a wavefront each with the records in HBM; 0 sends every non-empty read to the wavefront tier; larger values count as 8; same results), "primary_blocks" (> 0: at most this many workgroups in each kernel of that stage, so that a small batch goes round their grid-stride loops; 0, default: no cap; same results), "finish_blocks" (> 0: the same cap for the kernels of meme_finish_batch_host / _device; 0, default: no cap; same results), "finish_lds_recs" (> 0: reads handed over with more records than this are walked by the wavefront tier of that stage in a workspace in HBM instead of in LDS; 0, default, and anything above it: 128; same results), "pair_split" (default 8, its maximum: meme_pair_batch_host / _device run pairs with at most this many keys -- records of both ends that take part -- eight lanes to a pair with the keys in registers, pairs with more a wavefront each; 0 sends every non-empty pair to the wavefront tier; larger values count as 8; same results), "pair_blocks" (> 0: at most this many workgroups in each kernel of that stage; 0, default: no cap; same results), "pair_lds_keys" (> 0: the wavefront tier keeps this many of a pair's sorted keys in LDS and the rest in a workspace in HBM; 0, default, and anything above it: 512; same results), "sa_chunk" (default 2^28, at least 1: meme_sa_build_device sorts the 256 four-base buckets in groups of consecutive buckets with at most this many suffixes each -- a bucket alone may exceed it; a bound of the workspace, and how the tests reach the multi-group path with small texts; same array), "sa_piece" (default 2^28, at least 1: that call looks for the suffix-array entries of the padding in pieces of this many slots; same array) */
 
 /* Debug: the packed image of the last seeded batch (what the search kernels read), copied to the host.  Per read `stride` 64-bit
  * words: fw[W] rc[W] nfw[MW] nrc[MW] len | hasN << 31 (2 bits per base, first base in the top bits, N packed as A; mask bit j of word m =
@@ -542,6 +542,12 @@ int meme_debug_packed_reads(meme_ctx* ctx, uint64_t* out, int64_t capacity_words
  * kernels (seed_defer 0, no plcp table, one round, or no call yet). */
 #define MEME_RESEED_COUNTS 14
 int meme_debug_reseed_counts(meme_ctx* ctx, int64_t* out, int32_t capacity, int32_t* rounds);
+
+/* Debug: tier 0 of the last seeding call on this ctx.  out[0]: 1 when its third round ran in a k_seed launch of its own (tuning "seed_r3_split" 1, three
+ * rounds, max_mem_intv > 0), else 0; out[1]: third-round searches that launch ran twice -- first on the 64-bit keys alone, then in full because 32 bases could not
+ * decide them (at most one per read: the read's later searches compare in full at once; 0 with min_seed_len + 1 > 32).  capacity < MEME_R3_COUNTS is MEME_E_CAPACITY; MEME_E_STATE before the first seeding call. */
+#define MEME_R3_COUNTS 2
+int meme_debug_seed_r3_counts(meme_ctx* ctx, int64_t* out, int32_t capacity);
 
 /* Debug: what the last meme_sa_build_device on this ctx did.  out[0]: k, the bases T behind the text (longest run of A or of T, + 1); out[1]: groups of
  * four-base buckets sorted (tuning "sa_chunk"; groups without a suffix are not counted); out[2]: suffixes of the largest group; out[3]: suffixes of the
