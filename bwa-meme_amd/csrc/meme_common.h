@@ -211,6 +211,11 @@ struct PairWs {        // regs / reg_off / n_pri / res / status / counter: the h
     bool tab_in_flight = false;
 };
 
+struct DecideWs {      // regs / reg_off / n_pri / in / in_status / res / status / counter: the host form's staging (in: the pair stage's score, sub, n_sub and z, five ints a pair; res: path,
+                       // q_pe, flag, sel, q_se and alt, nine ints a pair); list: the heavy pairs
+    DevBuf regs, reg_off, n_pri, in, in_status, res, status, counter, list; HostBuf h_regs, h_res, h_status; Events<2> ev;
+};
+
 struct FinishWs {      // regs / reg_off / out / reg_off_out / ums / status / counters: the host form's staging; stage: the records a read keeps, at the read's input offsets, before the
                        // pack; cnt: records kept per read; live / first: live records of a read and the first of them; list: the wavefront tier's reads; cols_l / cols_c: the
                        // columns of reads too large for LDS
@@ -247,7 +252,7 @@ struct meme_ctx {
     ContigCache contigs;
     HostBuf h_ctr;                     // where a call's counters land on the host, read behind the call's own synchronise (never a stack variable: an error return
                                        // between the copy and the synchronise would leave the copy writing into a dead frame)
-    ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam; PrimaryWs primary; PairWs pair; FinishWs finish; SeedWs seed;
+    ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam; PrimaryWs primary; PairWs pair; DecideWs decide; FinishWs finish; SeedWs seed;
     // Streams.  Order of destruction: meme_ctx_destroy synchronises every stream of the ctx; then the members go in reverse order of declaration, so the streams
     // and their fork / join events -- these two and, last member of the last workspace, the seeding stage's -- are destroyed BEFORE any DevBuf / HostBuf above is
     // freed.  A new stream holder goes below the buffers too: here, or last in SeedWs.  (A stage's timing events go with the stage; they are idle by then.)
@@ -272,6 +277,9 @@ struct meme_ctx {
     i64 pair_split = 8;                // pair scoring: pairs with more keys (records of both ends that take part) than this go to the wavefront-per-pair tier (0: every non-empty pair; at most 8)
     i64 pair_blocks = 0;               // > 0: cap on the workgroups of the pair-scoring kernels (0 = none)
     i64 pair_lds_keys = 0;             // > 0: the wavefront tier keeps this many sorted keys of a pair in LDS, the rest in HBM (0, and anything above it: 512)
+    i64 decide_split = 64;             // pairing decision: pairs whose two ends hold more records than this go to the wavefront-per-pair tier (0: every pair with a record; at most 1 << 20;
+                                       // 64: the fastest of 0, 8, 16, 32, 64 on the production-shaped batch, profiles/decide_stage.md)
+    i64 decide_blocks = 0;             // > 0: cap on the workgroups of the pairing-decision kernels (0 = none)
     i64 finish_blocks = 0;             // > 0: cap on the workgroups of the record-finishing kernels (0 = none)
     i64 finish_lds_recs = 0;           // > 0: reads handed over with more records than this are walked in HBM by the wavefront tier (0, and anything above it: 128)
     i64 ext_live_only = 0;             // 1: meme_extend_last_batch_host hands over the surviving records only (qe > qb: what src/bwamem.cpp:1680-1693 keeps)
@@ -311,6 +319,8 @@ inline unsigned grid_blocks(i64 items, int per, i64 cap = 256 * 64) { i64 b = (i
 // ctx->stream synchronised, the contigs checked (ascending, inside the forward strand of an l_pac-base genome; the error message starts with `prefix`), staged,
 // synchronised again, remembered.  After a refusal nothing is remembered: the next call checks again.
 int meme_contigs(meme_ctx* ctx, const char* prefix, const meme_contig* contigs, int32_t n_contigs, i64 l_pac, ContigTab* out);
+// the ctx's table of logarithms, log((double)k) for k < 65536 by the host's libm (PrimaryWs::logtab): staged on first use, which synchronises ctx->stream once (meme_primary.hip)
+int meme_logtab(meme_ctx* ctx, const double** d_tab);
 // exclusive prefix sum of n 64-bit counts into out[0..n] (out[n] = total), asynchronous on ctx->stream (meme_scan.hip)
 int meme_scan_exclusive(meme_ctx* ctx, const i64* d_in, i64* d_out, i64 n);
 // the same, and the total on its way to *h_total (an asynchronous 8-byte copy: the caller synchronises ctx->stream before reading it)

@@ -347,13 +347,10 @@ static int primary_check_opt(const char* who, const meme_primary_opt* o) {
     return MEME_OK;
 }
 
-// the stage's kernels on device arrays, asynchronous on ctx->stream; ev: recorded around them
-static int primary_launch(meme_ctx* ctx, const meme_alnreg* d_regs, const i64* d_reg_off, i64 nreads, i64 total_regs, i64 id_base, const meme_primary_opt* opt,
-                          const meme_primary_device_out* o) {
+// the table of logarithms of the ctx (the pairing decision looks its own up in it too)
+int meme_logtab(meme_ctx* ctx, const double** d_tab) {
     PrimaryWs& P = ctx->primary;
-    int rc;
-    if ((rc = meme_buf_reserve(ctx, P.sorted, (size_t)(total_regs + 1) * sizeof(meme_alnreg))) || (rc = meme_buf_reserve(ctx, P.rank, (size_t)(total_regs + 1) * 4)) ||
-        (rc = meme_buf_reserve(ctx, P.list, (size_t)(nreads + 1) * 8)) || (rc = meme_buf_reserve(ctx, P.logtab, (size_t)PRI_LOG * 8))) return rc;
+    if (int rc = meme_buf_reserve(ctx, P.logtab, (size_t)PRI_LOG * 8)) return rc;
     if (!P.log_ready) {
         std::vector<double> tab((size_t)PRI_LOG);
         for (int k = 0; k < PRI_LOG; ++k) tab[(size_t)k] = log((double)k);
@@ -361,13 +358,25 @@ static int primary_launch(meme_ctx* ctx, const meme_alnreg* d_regs, const i64* d
         HIP_TRY(hipStreamSynchronize(ctx->stream));          // (tab goes out of scope)
         P.log_ready = true;
     }
+    *d_tab = (const double*)P.logtab.p;
+    return MEME_OK;
+}
+
+// the stage's kernels on device arrays, asynchronous on ctx->stream; ev: recorded around them
+static int primary_launch(meme_ctx* ctx, const meme_alnreg* d_regs, const i64* d_reg_off, i64 nreads, i64 total_regs, i64 id_base, const meme_primary_opt* opt,
+                          const meme_primary_device_out* o) {
+    PrimaryWs& P = ctx->primary;
+    int rc;
+    const double* logtab;
+    if ((rc = meme_buf_reserve(ctx, P.sorted, (size_t)(total_regs + 1) * sizeof(meme_alnreg))) || (rc = meme_buf_reserve(ctx, P.rank, (size_t)(total_regs + 1) * 4)) ||
+        (rc = meme_buf_reserve(ctx, P.list, (size_t)(nreads + 1) * 8)) || (rc = meme_logtab(ctx, &logtab))) return rc;
     HIP_TRY(P.ev.ensure());
     PriArgs A;
     A.in = d_regs; A.reg_off = d_reg_off; A.nreads = nreads; A.total_regs = total_regs; A.id_base = (u64)id_base; A.o = *opt;
     A.tmp = pri_score_distance(*opt);
     A.split = tune_split(ctx->primary_split, PRI_G);
     A.out = o->d_regs_out; A.sorted = (meme_alnreg*)P.sorted.p; A.rank = (int*)P.rank.p; A.n_pri = o->d_n_pri; A.mapq = o->d_mapq; A.status = o->d_status;
-    A.list = (i64*)P.list.p; A.n_heavy = (unsigned long long*)o->d_n_heavy; A.logtab = (const double*)P.logtab.p;
+    A.list = (i64*)P.list.p; A.n_heavy = (unsigned long long*)o->d_n_heavy; A.logtab = logtab;
     const i64 cap = tune_grid_cap(ctx->primary_blocks);
     HIP_TRY(hipEventRecord(P.ev[0], ctx->stream));
     HIP_TRY(hipMemsetAsync(o->d_n_heavy, 0, 8, ctx->stream));

@@ -173,6 +173,32 @@ def pair_pes(pes):
     return (PairPes * 4)(*[PairPes(int(lo), int(hi), int(failed), 0, float(avg), float(std)) for lo, hi, failed, avg, std in pes])
 
 
+class DecideOpt(C.Structure):       # meme_decide_opt
+    _fields_ = [(n, C.c_int32) for n in ("a", "b", "pen_unpaired", "T", "min_seed_len")] + [("mapQ_coef_len", C.c_float), ("mapQ_coef_fac", C.c_int32), ("no_pairing", C.c_int32)]
+
+
+class DecidePairIn(C.Structure):    # meme_decide_pair_in
+    _fields_ = [(n, C.c_void_p) for n in ("score", "sub", "n_sub", "z", "status")]
+
+
+class DecideHost(C.Structure):      # meme_decide_host_result
+    _fields_ = [("npairs", C.c_int64), ("total_regs", C.c_int64)] + [(n, C.c_void_p) for n in ("regs", "path", "q_pe", "flag", "sel", "q_se", "alt", "status")] + \
+               [("n_heavy", C.c_int64), ("kernel_ms", C.c_float)]
+
+
+class DecideDeviceOut(C.Structure):     # meme_decide_device_out
+    _fields_ = [(n, C.c_void_p) for n in ("d_path", "d_sel", "d_q_se", "d_q_pe", "d_flag", "d_alt", "d_status", "d_n_heavy")]
+
+
+def default_decide_opt(**kw):
+    # mem_opt_init (reference src/bwamem.cpp:126-162): a 1, b 4, pen_unpaired 17, T 30, min_seed_len 19, mapQ_coef_len 50, mapQ_coef_fac = log(50) = 3
+    o = DecideOpt(1, 4, 17, 30, 19, 50.0, 3, 0)
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
+
+
 class FinishOpt(C.Structure):       # meme_finish_opt
     _fields_ = [(n, C.c_int32) for n in ("a", "b", "o_del", "e_del", "o_ins", "e_ins", "w", "max_chain_gap")] + [("mask_level_redun", C.c_float), ("pad", C.c_int32)]
 
@@ -233,7 +259,7 @@ EXPORTS = ["meme_device_count", "meme_ctx_create", "meme_ctx_destroy", "meme_las
            "meme_index_pos5_bytes",
            "meme_index_attach", "meme_index_describe", "meme_index_share", "meme_index_replicate", "meme_host_alloc",
            "meme_host_free", "meme_stage_pack_text", "meme_stage_pos5_from_sa", "meme_stage_build_entries", "meme_stage_build_plcp",
-           "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_primary_batch_host", "meme_primary_batch_device", "meme_finish_batch_host", "meme_finish_batch_device", "meme_pair_batch_host", "meme_pair_batch_device", "meme_seed_batch_device",
+           "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_primary_batch_host", "meme_primary_batch_device", "meme_finish_batch_host", "meme_finish_batch_device", "meme_pair_batch_host", "meme_pair_batch_device", "meme_pair_decide_batch_host", "meme_pair_decide_batch_device", "meme_seed_batch_device",
            "meme_bsw_batch", "meme_bsw_batch_device", "meme_get_timings", "meme_set_tuning", "meme_debug_packed_reads",
            "meme_debug_reseed_counts", "meme_debug_seed_r3_counts", "meme_debug_sa_stats", "meme_debug_scan_exclusive"]
 
@@ -608,6 +634,37 @@ class Context:
         out = PairDeviceOut(d_score_ptr, d_sub_ptr, d_n_sub_ptr, d_n_cand_ptr, d_z_ptr, d_status_ptr, d_n_heavy_ptr)
         _check(lib().meme_pair_batch_device(C.c_void_p(self.h), C.c_void_p(d_regs_ptr), C.c_void_p(d_reg_off_ptr), C.c_void_p(d_n_pri_ptr), C.c_int64(nreads), C.c_int64(total_regs), arr,
                                             C.c_int32(len(contigs)), C.c_int64(int(l_pac)), pair_pes(pes), C.c_int64(int(id_base)), C.byref(opt or default_pair_opt()), C.byref(out)))
+
+    def pair_decide_batch_host(self, regs, reg_off, n_pri, pair, l_pac, pes, opt=None):
+        """meme_pair_decide_batch_host: the pairing decision behind mem_pair for the records regs (ALNREG) per read as primary_batch_host leaves them -- reads 2p and 2p + 1
+        are pair p; pair: what pair_batch_host returned (score, sub, n_sub, z, status); pes: four (low, high, failed, avg, std).  Returns dict(regs: the changed copy, path,
+        sel (pairs x 2), q_se (pairs x 2), q_pe, flag, alt (pairs x 2), status, n_heavy, kernel_ms)."""
+        opt = opt or default_decide_opt()
+        assert regs.dtype == ALNREG and regs.flags.c_contiguous
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
+        n_pri = np.ascontiguousarray(n_pri, dtype=np.int32)
+        n = reg_off.shape[0] - 1
+        assert n_pri.shape[0] == n
+        cols = [np.ascontiguousarray(pair[f], dtype=np.int32) for f in ("score", "sub", "n_sub")] + [np.ascontiguousarray(pair["z"], dtype=np.int32).reshape(-1),
+                                                                                                    np.ascontiguousarray(pair["status"], dtype=np.uint8)]
+        assert all(c.shape[0] == n // 2 for c in cols[:3]) and cols[3].shape[0] == n // 2 * 2 and cols[4].shape[0] == n // 2
+        pin = DecidePairIn(*[_p(c) for c in cols])
+        res = DecideHost()
+        _check(lib().meme_pair_decide_batch_host(C.c_void_p(self.h), _p(regs), _p(reg_off), _p(n_pri), C.c_int64(n), C.byref(pin), C.c_int64(int(l_pac)), pair_pes(pes), C.byref(opt),
+                                                 C.byref(res)))
+        m = int(res.npairs)
+        return {"regs": _view(res.regs, res.total_regs, ALNREG), "path": _view(res.path, m, np.int32), "sel": _view(res.sel, 2 * m, np.int32).reshape(m, 2),
+                "q_se": _view(res.q_se, 2 * m, np.int32).reshape(m, 2), "q_pe": _view(res.q_pe, m, np.int32), "flag": _view(res.flag, m, np.int32),
+                "alt": _view(res.alt, 2 * m, np.int32).reshape(m, 2), "status": _view(res.status, m, np.uint8), "n_heavy": int(res.n_heavy), "kernel_ms": float(res.kernel_ms)}
+
+    def pair_decide_batch_device(self, d_regs_ptr, d_reg_off_ptr, d_n_pri_ptr, nreads, total_regs, d_score_ptr, d_sub_ptr, d_n_sub_ptr, d_z_ptr, d_pair_status_ptr, l_pac, pes, opt,
+                                 d_path_ptr, d_sel_ptr, d_q_se_ptr, d_q_pe_ptr, d_flag_ptr, d_alt_ptr, d_status_ptr, d_n_heavy_ptr):
+        """meme_pair_decide_batch_device: the same on device arrays the caller owns (d_regs_out, d_reg_off and d_n_pri of primary_batch_device, the outputs of
+        pair_batch_device as they are); d_regs changes in place.  Asynchronous on the ctx's stream (sync() before reading the results)."""
+        pin = DecidePairIn(d_score_ptr, d_sub_ptr, d_n_sub_ptr, d_z_ptr, d_pair_status_ptr)
+        out = DecideDeviceOut(d_path_ptr, d_sel_ptr, d_q_se_ptr, d_q_pe_ptr, d_flag_ptr, d_alt_ptr, d_status_ptr, d_n_heavy_ptr)
+        _check(lib().meme_pair_decide_batch_device(C.c_void_p(self.h), C.c_void_p(d_regs_ptr), C.c_void_p(d_reg_off_ptr), C.c_void_p(d_n_pri_ptr), C.c_int64(nreads), C.c_int64(total_regs),
+                                                   C.byref(pin), C.c_int64(int(l_pac)), pair_pes(pes), C.byref(opt or default_decide_opt()), C.byref(out)))
 
     def finish_batch_host(self, regs, reg_off, contigs, l_pac, opt=None):
         """meme_finish_batch_host: record finishing (compaction to the live records, mem_sort_dedup_patch_mate_sort, is_alt) of the records regs (ALNREG) per read;

@@ -20,6 +20,7 @@
  *   meme_matesw_batch_host          <- mem_sam_pe_batch_pre() + mem_sam_pe_batch()   src/bwamem_pair.cpp:660-716, 1060-1223, 719-818
  *   meme_primary_batch_host         <- mem_mark_primary_se() + mem_reorder_primary5() + mem_approx_mapq_se()   src/bwamem.cpp:1974-2100
  *   meme_pair_batch_host            <- mem_pair()                                    src/bwamem_pair.cpp:372-433
+ *   meme_pair_decide_batch_host     <- mem_sam_pe() behind mem_pair(): the pairing decision   src/bwamem_pair.cpp:536-590, 632-648
  *   meme_bsw_batch                  <- BandedPairWiseSW::getScores8 / getScores16 /
  *                                      scalarBandedSWAWrapper                 src/bandedSWA.h:118-135,257-297
  *
@@ -443,8 +444,8 @@ int meme_primary_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs, const in
  * by its libm for every distance low .. high of every orientation that has not failed, per call, and staged on the ctx's stream as a table: no erfc or log
  * runs on the device.  high - low + 1 > 1 << 20 for such an orientation is MEME_E_ARG.  std == 0 is no special case (its infinite / NaN entries score 0, as
  * in the reference).
- * What it does NOT do: the pairing decision behind mem_pair (is_multi, q_pe, q_se, the secondary_all swap, src/bwamem_pair.cpp:938-992) and mate rescue in
- * front of it stay with the caller.
+ * What it does NOT do: the pairing decision behind mem_pair (is_multi, q_pe, q_se, the secondary_all swap, src/bwamem_pair.cpp:938-992) is the stage
+ * below, meme_pair_decide_batch_*; mate rescue in front of it stays with the caller.
  * Conventions: a pair one of whose ends has n_pri == 0 gets zeros and z = -1, -1 (the reference does not call mem_pair there).  status[p] = 1: a record that
  * takes part has rid outside [0, n_contigs) or a negative score; the pair is skipped, zeros and z = -1, -1.  status[p] = 2 (device form only): reg_off of one
  * of its reads is no span inside [0, total_regs], or n_pri is negative or exceeds the span; skipped likewise.  nreads odd, a null argument, opt->a < 1:
@@ -469,6 +470,60 @@ typedef struct { int32_t *d_score, *d_sub, *d_n_sub, *d_n_cand, *d_z; uint8_t* d
 int meme_pair_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs, const int64_t* d_reg_off, const int32_t* d_n_pri, int64_t nreads, int64_t total_regs,
                            const meme_contig* contigs, int32_t n_contigs, int64_t l_pac, const meme_pair_pes* pes /* 4 */, int64_t id_base, const meme_pair_opt* opt,
                            const meme_pair_device_out* out);
+
+/* ---- the pairing decision: what mem_sam_pe does behind mem_pair ---------------------------------------------------------------------------------
+ * What mem_sam_pe (reference src/bwamem_pair.cpp:536-590; the same text at :936-992 in the batch form) decides for every pair of a batch once mem_pair has
+ * returned, and what its no_pairing block (:632-648; :1032-1048) picks where the pairing is not entered or left: reads 2p and 2p + 1 of the call are pair
+ * p.  Inputs are exactly what the stages in front leave: the records, reg_off and n_pri as meme_primary_batch_* returns them; score, sub, n_sub, z and
+ * status of meme_pair_batch_* (meme_decide_pair_in); l_pac and pes[4].  No contig table: the records carry rid.  Per pair:
+ *   path    0: pairing not entered (an end with n_pri == 0, score <= 0, or opt->no_pairing; :533, :536).  1: left through is_multi (:541-546).
+ *           2: the paired branch, the unpaired alignment preferred (:576-580).  3: the paired alignment preferred (:559-575).
+ *   sel[2]  the record either end reports first: z behind the decision on paths 2 / 3 (0, 0 on path 2), `which` of no_pairing (:634-639) on paths 0 / 1,
+ *           -1 for none
+ *   q_se[2], q_pe   the mapping qualities of :548-580 on paths 2 / 3 (q_pe: the final value, :556); 0 on paths 0 / 1, where the reference has none
+ *           (q_se is the reference's int: negative where the cap of :573-574 is, csub > score; mem_aln_t then keeps its low eight bits)
+ *   flag    extra_flag: 1, or 3 where the pair is a proper one (:570 on path 3; :643-647 on paths 0 / 1; never with opt->no_pairing)
+ *   alt[2]  on paths 2 / 3 the index of the ALT record reported behind the end's own (n_pri, if it exists with score >= T, secondary < 0 and is_alt;
+ *           :603-605), else -1
+ * and the records' sub, secondary (of the two records z names on path 3 that have a parent: the parent's score, -2; :563-564) and secondary_all (the swap
+ * of :581-590 over ALL records of an end on paths 2 / 3) as the reference leaves them for mem_reg2aln and the SAM text.  Nothing else of a record changes.
+ * Logarithms (:552 and mem_approx_mapq_se's) are looked up in the ctx's table of the host libm's log((double)k), k < 65536; the sum of the two frac_rep of
+ * :556 is a float sum, as x86-64 evaluates it.  Only the mapQ_coef_len > 0 branch of mem_approx_mapq_se exists, as in the primary stage.
+ * What it does NOT do: mate rescue in front of mem_pair (its record updates stay with the caller, and with them the binding's call of the reference);
+ * mem_reg2sam's record list for paths 0 / 1; mem_gen_alt / XA; the SAM text.
+ * status[p] = 0: fine.  1: the pair stage's status was non-zero, or a logarithm beyond the table was asked for (n_sub + 1 or an alignment span of 65536 and
+ * more): the outputs are the defaults (path 0, sel -1, -1, zeros, flag 1, alt -1, -1) and the pair's records are untouched.  2 (device form only; the host form
+ * refuses the call): reg_off of one of its reads is no span inside [0, total_regs], n_pri is negative or exceeds the span, or on a pair with score > 0 z is
+ * outside [0, n_pri) or the record it names has a parent index beyond the read; defaults, records untouched.
+ * MEME_E_ARG: nreads odd, a null argument, opt->a < 1, opt->a + opt->b <= 0, opt->mapQ_coef_len <= 0, a record array that is not 16-byte aligned.
+ * Host form: the changed copy of the records and the results in pinned memory of the ctx until its next call of this function. */
+typedef struct {
+    int32_t a, b, pen_unpaired, T, min_seed_len;   /* mem_opt_t fields of the same names */
+    float mapQ_coef_len;
+    int32_t mapQ_coef_fac;
+    int32_t no_pairing;           /* opt->flag & MEM_F_NOPAIRING */
+} meme_decide_opt;
+/* the pair stage's outputs (host pointers for the host form, device pointers for the device form): score, sub, n_sub, status npairs each, z twice as many */
+typedef struct { const int32_t *score, *sub, *n_sub, *z; const uint8_t* status; } meme_decide_pair_in;
+typedef struct {
+    int64_t npairs, total_regs;
+    const meme_alnreg* regs;      /* the records behind the decision, offsets = the call's reg_off */
+    const int32_t *path, *q_pe, *flag;     /* npairs each */
+    const int32_t *sel, *q_se, *alt;       /* 2 * npairs each */
+    const uint8_t* status;        /* npairs */
+    int64_t n_heavy;              /* pairs the wavefront-per-pair tier took (tuning "decide_split") */
+    float kernel_ms;              /* HIP events around the stage's kernels */
+} meme_decide_host_result;
+int meme_pair_decide_batch_host(meme_ctx* ctx, const meme_alnreg* regs, const int64_t* reg_off /* nreads + 1, from 0 */, const int32_t* n_pri /* nreads */, int64_t nreads,
+                                const meme_decide_pair_in* pair, int64_t l_pac, const meme_pair_pes* pes /* 4 */, const meme_decide_opt* opt, meme_decide_host_result* out);
+/* The same on device arrays the caller owns -- d_regs: d_regs_out of meme_primary_batch_device, changed IN PLACE (sub, secondary, secondary_all; nothing else);
+ * d_reg_off, d_n_pri as that stage leaves them; d_pair: the outputs of meme_pair_batch_device; the outputs: nreads / 2 entries each, d_sel, d_q_se and d_alt
+ * twice as many, d_n_heavy one counter -- asynchronous on the ctx's stream: nothing is copied and the host does not wait (but for the table of logarithms on the
+ * ctx's first use of it). */
+typedef struct { int32_t *d_path, *d_sel, *d_q_se, *d_q_pe, *d_flag, *d_alt; uint8_t* d_status; uint64_t* d_n_heavy; } meme_decide_device_out;
+int meme_pair_decide_batch_device(meme_ctx* ctx, meme_alnreg* d_regs, const int64_t* d_reg_off, const int32_t* d_n_pri, int64_t nreads, int64_t total_regs,
+                                  const meme_decide_pair_in* d_pair, int64_t l_pac, const meme_pair_pes* pes /* 4 */, const meme_decide_opt* opt,
+                                  const meme_decide_device_out* out);
 
 /* ---- record finishing: the tail of mem_kernel2_core ----------------------------------------------------------------------------------------
  * What mem_kernel2_core does behind the extension (reference src/bwamem.cpp:1681-1719) with the alignment records of every read of a batch: the
