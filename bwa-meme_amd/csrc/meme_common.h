@@ -194,6 +194,7 @@ struct KswvWs {        // mate rescue poses into jobs, ref and qer; k_kswv reads
 };
 struct MateWs {        // counts: MateCounts; batch_off: gar and job offsets of the worker batches
     DevBuf regs, reg_off, counts, gar, aux, batch_off; HostBuf h_gar, h_batch_off, h_jobs;
+    i64 last_nb = -1, last_njobs = 0;  // the last meme_matesw_batch_host call that returned MEME_OK: its worker batches (-1: none, or a kswv call has taken KswvWs::res since) and jobs
 };
 struct SamWs {         // cols: SamCols; contigs: contig name offsets + names + read group
     DevBuf names, name_off, quals, recs, blob, cols, scratch, text, contigs; HostBuf h_text_off, h_text; Events<2> ev;
@@ -214,6 +215,13 @@ struct PairWs {        // regs / reg_off / n_pri / res / status / counter: the h
 struct DecideWs {      // regs / reg_off / n_pri / in / in_status / res / status / counter: the host form's staging (in: the pair stage's score, sub, n_sub and z, five ints a pair; res: path,
                        // q_pe, flag, sel, q_se and alt, nine ints a pair); list: the heavy pairs
     DevBuf regs, reg_off, n_pri, in, in_status, res, status, counter, list; HostBuf h_regs, h_res, h_status; Events<2> ev;
+};
+
+struct RescueWs {      // regs / reg_off / ums / rlen / gar / gar_off / job_off / res / out / reg_off_out / status / counters: the host form's staging; cnt_a / off_a: records of a read
+                       // that are looked at, and the scan; cap / off_c: records a list can come to hold, and the scan (where its records stand in `stage` before the pack);
+                       // cnt: records a list is left with; list: the wavefront tier's lists; cols_l / cols_c: the columns of lists too large for LDS, at off_c
+    DevBuf regs, reg_off, ums, rlen, gar, gar_off, job_off, res, out, reg_off_out, status, counters, stage, cnt_a, off_a, cap, off_c, cnt, list, cols_l, cols_c;
+    HostBuf h_regs, h_reg_off, h_status; Events<2> ev;
 };
 
 struct FinishWs {      // regs / reg_off / out / reg_off_out / ums / status / counters: the host form's staging; stage: the records a read keeps, at the read's input offsets, before the
@@ -252,7 +260,7 @@ struct meme_ctx {
     ContigCache contigs;
     HostBuf h_ctr;                     // where a call's counters land on the host, read behind the call's own synchronise (never a stack variable: an error return
                                        // between the copy and the synchronise would leave the copy writing into a dead frame)
-    ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam; PrimaryWs primary; PairWs pair; DecideWs decide; FinishWs finish; SeedWs seed;
+    ChainWs chain; ExtWs ext; BswWs bsw; GcigWs gcig; KswvWs kswv; MateWs mate; SamWs sam; PrimaryWs primary; PairWs pair; DecideWs decide; FinishWs finish; RescueWs rescue; SeedWs seed;
     // Streams.  Order of destruction: meme_ctx_destroy synchronises every stream of the ctx; then the members go in reverse order of declaration, so the streams
     // and their fork / join events -- these two and, last member of the last workspace, the seeding stage's -- are destroyed BEFORE any DevBuf / HostBuf above is
     // freed.  A new stream holder goes below the buffers too: here, or last in SeedWs.  (A stage's timing events go with the stage; they are idle by then.)
@@ -282,6 +290,8 @@ struct meme_ctx {
     i64 decide_blocks = 0;             // > 0: cap on the workgroups of the pairing-decision kernels (0 = none)
     i64 finish_blocks = 0;             // > 0: cap on the workgroups of the record-finishing kernels (0 = none)
     i64 finish_lds_recs = 0;           // > 0: reads handed over with more records than this are walked in HBM by the wavefront tier (0, and anything above it: 128)
+    i64 rescue_blocks = 0;             // > 0: cap on the workgroups of the mate-rescue record kernels (0 = none)
+    i64 rescue_lds_recs = 0;           // > 0: lists that can come to hold more records than this are walked in HBM by the wavefront tier (0, and anything above it: 128)
     i64 ext_live_only = 0;             // 1: meme_extend_last_batch_host hands over the surviving records only (qe > qb: what src/bwamem.cpp:1680-1693 keeps)
     i64 ext_rounds = 1;                // with ext_live_only: rounds of one seed per read before everything still ahead is extended at once (0: the reference's batch, then compaction)
     i64 gcig_groups = 1;               // 1: CIGAR jobs with bands of at most 16 / 32 / 64 columns run 4 / 2 / 1 to a wavefront as one chunk per row (k_gcig_grp); 0: a wavefront each, 64-column chunks

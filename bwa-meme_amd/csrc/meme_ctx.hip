@@ -156,7 +156,7 @@ extern "C" int meme_set_tuning(meme_ctx* ctx, const char* key, int64_t value) {
         {"ext_rounds", &meme_ctx::ext_rounds, 0}, {"bsw_blocks", &meme_ctx::bsw_blocks, any}, {"bsw_lane_min_pairs", &meme_ctx::bsw_lane_min_pairs, any},
         {"chain_wave_tiers", &meme_ctx::chain_wave_tiers, any}, {"chain_lane_hits", &meme_ctx::chain_lane_hits, any}, {"chain_light_hits", &meme_ctx::chain_light_hits, any},
         {"group_lanes", &meme_ctx::group_lanes, any}, {"primary_split", &meme_ctx::primary_split, 0}, {"primary_blocks", &meme_ctx::primary_blocks, 0}, {"finish_blocks", &meme_ctx::finish_blocks, 0}, {"pair_split", &meme_ctx::pair_split, 0}, {"pair_blocks", &meme_ctx::pair_blocks, 0}, {"pair_lds_keys", &meme_ctx::pair_lds_keys, 0},
-        {"decide_split", &meme_ctx::decide_split, 0}, {"decide_blocks", &meme_ctx::decide_blocks, 0},
+        {"decide_split", &meme_ctx::decide_split, 0}, {"decide_blocks", &meme_ctx::decide_blocks, 0}, {"rescue_blocks", &meme_ctx::rescue_blocks, 0}, {"rescue_lds_recs", &meme_ctx::rescue_lds_recs, 0},
         {"finish_lds_recs", &meme_ctx::finish_lds_recs, 0}, {"seed_blocks_per_cu", &meme_ctx::seed_blocks_per_cu, 1},
         {"sa_chunk", &meme_ctx::sa_chunk, 1}, {"sa_piece", &meme_ctx::sa_piece, 1}};
     for (const auto& k : keys) if (!strcmp(key, k.key)) { ctx->*k.member = value < k.at_least ? k.at_least : value; return MEME_OK; }

@@ -149,6 +149,50 @@ KS_HD int fin_word(int word_in, int n_comp, int rid, const unsigned char* alt, i
 // what the driver reports besides the records
 struct FinRead { int use_mate_sort, status, n_jobs, n_merged; };
 
+// The redundancy walk over n records in the order by end (:321-355; the same text in mem_sort_dedup_patch :394-428 and mem_dedup_patch :266-300): a record whose
+// overlaps with an earlier one exceed mask_level_redun loses against the higher score (qe = qb); for the others patch(p, q, a, b) stands where the reference calls
+// mem_patch_reg and merges.  With bns == 0 that function returns 0 (:200): mate rescue's callers hand a patch that does nothing (meme_rescue_rules.h).
+template <class S, class P>
+KS_HD void fin_walk(const S& s, const FinOrd<S>& ord, int n, int64_t gap, float mask_level_redun, P&& patch) {
+    for (int i = 1; i < n; ++i) {
+        const int p = ord.get(i), prev = ord.get(i - 1);
+        const int p_rid = s.geti(FIN_RID, p);
+        if (p_rid != s.geti(FIN_RID, prev) || s.getl(FIN_RB, p) >= s.getl(FIN_RE, prev) + gap) continue;
+        for (int j = i - 1; j >= 0; --j) {
+            const int q = ord.get(j);
+            if (!(p_rid == s.geti(FIN_RID, q) && s.getl(FIN_RB, p) < s.getl(FIN_RE, q) + gap)) break;
+            FinSpan a = {s.getl(FIN_RB, q), s.getl(FIN_RE, q), s.geti(FIN_QB, q), s.geti(FIN_QE, q), s.geti(FIN_SCORE, q), s.geti(FIN_W, q)};
+            FinSpan b = {s.getl(FIN_RB, p), s.getl(FIN_RE, p), s.geti(FIN_QB, p), s.geti(FIN_QE, p), s.geti(FIN_SCORE, p), s.geti(FIN_W, p)};
+            if (a.qe == a.qb) continue;                                            // a[j] has been excluded
+            const int64_t or_ = a.re - b.rb, oq = a.qb < b.qb ? a.qe - b.qb : b.qe - a.qb;
+            const int64_t mr = a.re - a.rb < b.re - b.rb ? a.re - a.rb : b.re - b.rb, mq = a.qe - a.qb < b.qe - b.qb ? a.qe - a.qb : b.qe - b.qb;
+            if (fin_redundant(or_, oq, mr, mq, mask_level_redun)) {
+                if (b.score < a.score) { s.seti(FIN_QE, p, b.qb); break; }
+                s.seti(FIN_QE, q, a.qb);
+            } else if (a.rb < b.rb) patch(p, q, a, b);
+        }
+    }
+}
+// the records of the order that are left (qe > qb), from position `from` on, closed up (:356-362, :376-380); -> their number
+template <class S>
+KS_HD int fin_compact(const S& s, const FinOrd<S>& ord, int n, int from) {
+    int m = n < from ? n : from;
+    for (int i = from; i < n; ++i) {
+        const int x = ord.get(i);
+        if (s.geti(FIN_QE, x) > s.geti(FIN_QB, x)) ord.set(m++, x);
+    }
+    return m;
+}
+// the identical-hit pass over n records in the order by score (:372-381): a record equal to its predecessor in score, rb and qb leaves; element 0 stays whatever it holds (:376)
+template <class S>
+KS_HD int fin_identical(const S& s, const FinOrd<S>& ord, int n) {
+    for (int i = 1; i < n; ++i) {
+        const int x = ord.get(i), y = ord.get(i - 1);
+        if (s.geti(FIN_SCORE, x) == s.geti(FIN_SCORE, y) && s.getl(FIN_RB, x) == s.getl(FIN_RB, y) && s.geti(FIN_QB, x) == s.geti(FIN_QB, y)) s.seti(FIN_QE, x, s.geti(FIN_QB, x));
+    }
+    return fin_compact(s, ord, n, 1);
+}
+
 // The whole function for one read.  s holds the read's n_in records as they are handed over (live and purged) in positions [0, n_in) with FIN_NCOMP = the
 // n_comp they carry; on return the first m entries of FIN_ORD name the records that are left, in their final order, and their fields are as the function
 // leaves them (m is returned).  score_fn(P, rb, qb) = the score of the posed alignment P whose target starts at rb and whose query starts at base qb of the read.
@@ -164,61 +208,29 @@ KS_HD int finish_read(const S& s, int n_in, int read_len, int64_t l_pac, const m
     st.n = 0;
     ks_introsort(ord, n, FinLtEnd<S>{s}, st);
     for (int i = 0; i < n; ++i) s.seti(FIN_NCOMP, ord.get(i), 1);
-    const int64_t gap = o.max_chain_gap;
-    for (int i = 1; i < n; ++i) {
-        const int p = ord.get(i), prev = ord.get(i - 1);
-        const int p_rid = s.geti(FIN_RID, p);
-        if (p_rid != s.geti(FIN_RID, prev) || s.getl(FIN_RB, p) >= s.getl(FIN_RE, prev) + gap) continue;
-        for (int j = i - 1; j >= 0; --j) {
-            const int q = ord.get(j);
-            if (!(p_rid == s.geti(FIN_RID, q) && s.getl(FIN_RB, p) < s.getl(FIN_RE, q) + gap)) break;
-            FinSpan a = {s.getl(FIN_RB, q), s.getl(FIN_RE, q), s.geti(FIN_QB, q), s.geti(FIN_QE, q), s.geti(FIN_SCORE, q), s.geti(FIN_W, q)};
-            FinSpan b = {s.getl(FIN_RB, p), s.getl(FIN_RE, p), s.geti(FIN_QB, p), s.geti(FIN_QE, p), s.geti(FIN_SCORE, p), s.geti(FIN_W, p)};
-            if (a.qe == a.qb) continue;                                            // a[j] has been excluded
-            const int64_t or_ = a.re - b.rb, oq = a.qb < b.qb ? a.qe - b.qb : b.qe - a.qb;
-            const int64_t mr = a.re - a.rb < b.re - b.rb ? a.re - a.rb : b.re - b.rb, mq = a.qe - a.qb < b.qe - b.qb ? a.qe - a.qb : b.qe - b.qb;
-            if (fin_redundant(or_, oq, mr, mq, o.mask_level_redun)) {
-                if (b.score < a.score) { s.seti(FIN_QE, p, b.qb); break; }
-                s.seti(FIN_QE, q, a.qb);
-            } else if (a.rb < b.rb) {
-                int w = 0;
-                if (!fin_patch_bars(a, b, l_pac, o.w, &w)) continue;
-                ++out->n_jobs;
-                const FinPose P = fin_pose(l_pac, a.qb, b.qe, read_len, a.rb, b.re, w, o);
-                if (!P.ok) { out->status = 1; continue; }                          // (the reference reads a score nobody wrote)
-                const int score = score_fn(P, a.rb, a.qb);
-                if (!fin_patch_ratio(a, b, score) || score <= 0) continue;
-                ++out->n_merged;                                                   // merge q into p (:345-352)
-                s.seti(FIN_NCOMP, p, s.geti(FIN_NCOMP, p) + s.geti(FIN_NCOMP, q) + 1);
-                const int cq = s.geti(FIN_SEEDCOV, q), sq = s.geti(FIN_SUB, q), csq = s.geti(FIN_CSUB, q);
-                if (cq > s.geti(FIN_SEEDCOV, p)) s.seti(FIN_SEEDCOV, p, cq);
-                if (sq > s.geti(FIN_SUB, p)) s.seti(FIN_SUB, p, sq);
-                if (csq > s.geti(FIN_CSUB, p)) s.seti(FIN_CSUB, p, csq);
-                s.seti(FIN_QB, p, a.qb); s.setl(FIN_RB, p, a.rb);
-                s.seti(FIN_SCORE, p, score); s.seti(FIN_TRUESC, p, score);
-                s.seti(FIN_W, p, w);
-                s.seti(FIN_QB, q, a.qe);
-            }
-        }
-    }
-    int m = 0;
-    for (int i = 0; i < n; ++i) {                                                  // :356-362
-        const int x = ord.get(i);
-        if (s.geti(FIN_QE, x) > s.geti(FIN_QB, x)) ord.set(m++, x);
-    }
-    n = m;
+    fin_walk(s, ord, n, (int64_t)o.max_chain_gap, o.mask_level_redun, [&](int p, int q, const FinSpan& a, const FinSpan& b) {
+        int w = 0;
+        if (!fin_patch_bars(a, b, l_pac, o.w, &w)) return;
+        ++out->n_jobs;
+        const FinPose P = fin_pose(l_pac, a.qb, b.qe, read_len, a.rb, b.re, w, o);
+        if (!P.ok) { out->status = 1; return; }                                    // (the reference reads a score nobody wrote)
+        const int score = score_fn(P, a.rb, a.qb);
+        if (!fin_patch_ratio(a, b, score) || score <= 0) return;
+        ++out->n_merged;                                                           // merge q into p (:345-352)
+        s.seti(FIN_NCOMP, p, s.geti(FIN_NCOMP, p) + s.geti(FIN_NCOMP, q) + 1);
+        const int cq = s.geti(FIN_SEEDCOV, q), sq = s.geti(FIN_SUB, q), csq = s.geti(FIN_CSUB, q);
+        if (cq > s.geti(FIN_SEEDCOV, p)) s.seti(FIN_SEEDCOV, p, cq);
+        if (sq > s.geti(FIN_SUB, p)) s.seti(FIN_SUB, p, sq);
+        if (csq > s.geti(FIN_CSUB, p)) s.seti(FIN_CSUB, p, csq);
+        s.seti(FIN_QB, p, a.qb); s.setl(FIN_RB, p, a.rb);
+        s.seti(FIN_SCORE, p, score); s.seti(FIN_TRUESC, p, score);
+        s.seti(FIN_W, p, w);
+        s.seti(FIN_QB, q, a.qe);
+    });
+    n = fin_compact(s, ord, n, 0);                                                 // :356-362
     for (int i = 0; i + 1 < n; ++i)                                                // :363-370
         if (s.getl(FIN_RE, ord.get(i)) == s.getl(FIN_RE, ord.get(i + 1))) { out->use_mate_sort = 0; break; }
     st.n = 0;
     ks_introsort(ord, n, FinLtScore<S>{s}, st);
-    for (int i = 1; i < n; ++i) {                                                  // mark identical hits (:372-375)
-        const int x = ord.get(i), y = ord.get(i - 1);
-        if (s.geti(FIN_SCORE, x) == s.geti(FIN_SCORE, y) && s.getl(FIN_RB, x) == s.getl(FIN_RB, y) && s.geti(FIN_QB, x) == s.geti(FIN_QB, y)) s.seti(FIN_QE, x, s.geti(FIN_QB, x));
-    }
-    m = n < 1 ? n : 1;                                                             // element 0 stays whatever it holds (:376)
-    for (int i = 1; i < n; ++i) {
-        const int x = ord.get(i);
-        if (s.geti(FIN_QE, x) > s.geti(FIN_QB, x)) ord.set(m++, x);
-    }
-    return m;
+    return fin_identical(s, ord, n);
 }

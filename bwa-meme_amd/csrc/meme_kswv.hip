@@ -217,6 +217,7 @@ int meme_kswv_run(meme_ctx* ctx, const meme_kswv_job* jobs, int64_t njobs, const
     if (!ctx || !opt || !out || njobs < 0 || (njobs > 0 && (!jobs || (!staged && (!ref || !qer))))) { meme_set_error("meme_kswv_batch_host: null argument"); return MEME_E_ARG; }
     HIP_TRY(hipSetDevice(ctx->device));
     memset(out, 0, sizeof(*out));
+    if (!staged) ctx->mate.last_nb = -1;                        // (KswvWs::res is about to hold another call's results: meme_matesw_last_device)
     if (njobs == 0) return MEME_OK;
     if (njobs > 0x7fffffff / 2) { meme_set_error("meme_kswv_batch_host: too many jobs in one call"); return MEME_E_ARG; }
     if (opt->a < 1 || opt->b < 0 || opt->e_del < 0 || opt->e_ins < 0 || opt->o_del < 0 || opt->o_ins < 0) { meme_set_error("meme_kswv_batch_host: bad scoring parameters"); return MEME_E_ARG; }

@@ -121,6 +121,7 @@ extern "C" int meme_matesw_batch_host(meme_ctx* ctx, meme_ctx* reads_of, const m
     if (!ctx || !reg_off || !pes || !contigs || n_contigs < 1 || !opt || !out || nreads < 0) { meme_set_error("%s: null argument", who); return MEME_E_ARG; }
     HIP_TRY(hipSetDevice(ctx->device));
     memset(out, 0, sizeof(*out));
+    ctx->mate.last_nb = -1;                                     // (meme_matesw_last_device: nothing to hand out until this call has returned MEME_OK)
     if (nreads == 0) return MEME_OK;
     // the batch whose reads are named: this ctx's, or -- reads_of -- that of another ctx of the same GPU (a binding that runs this stage beside another one
     // on the ctx that seeded the batch: the bases are only read, device pointers are valid across the ctxs of a device)
@@ -194,5 +195,15 @@ extern "C" int meme_matesw_batch_host(meme_ctx* ctx, meme_ctx* reads_of, const m
     out->nreads = n; out->nbatches = nb; out->njobs = nj; out->n_gar = 4 * nq;
     out->gar = (const int32_t*)M.h_gar.p; out->gar_off = (const int64_t*)M.h_batch_off.p; out->job_off = (const int64_t*)M.h_batch_off.p + (nb + 1);
     out->jobs = (const meme_kswv_job*)M.h_jobs.p; out->res = R.res; out->pose_ms = pose_ms; out->kernel_ms = R.kernel_ms;
+    M.last_nb = nb; M.last_njobs = nj;
+    return MEME_OK;
+}
+
+extern "C" int meme_matesw_last_device(meme_ctx* ctx, meme_rescue_jobs_in* view) {
+    if (!ctx || !view) { meme_set_error("meme_matesw_last_device: null argument"); return MEME_E_ARG; }
+    const MateWs& M = ctx->mate;
+    if (M.last_nb < 0) { meme_set_error("meme_matesw_last_device: no meme_matesw_batch_host call on this ctx whose results are still on the device"); return MEME_E_STATE; }
+    view->gar = (const int32_t*)M.gar.p; view->gar_off = (const int64_t*)M.batch_off.p; view->job_off = (const int64_t*)M.batch_off.p + (M.last_nb + 1);
+    view->nbatches = M.last_nb; view->res = (const meme_kswr*)ctx->kswv.res.p; view->njobs = M.last_njobs;
     return MEME_OK;
 }

@@ -221,6 +221,39 @@ def default_finish_opt(**kw):
     return o
 
 
+class RescueOpt(C.Structure):       # meme_rescue_opt
+    _fields_ = [(n, C.c_int32) for n in ("pen_unpaired", "max_matesw", "min_seed_len", "batch_reads", "max_chain_gap")] + [("mask_level_redun", C.c_float)]
+
+
+class RescueJobsIn(C.Structure):    # meme_rescue_jobs_in
+    _fields_ = [("gar", C.c_void_p), ("gar_off", C.c_void_p), ("job_off", C.c_void_p), ("nbatches", C.c_int64), ("res", C.c_void_p), ("njobs", C.c_int64)]
+
+
+class RescueHost(C.Structure):      # meme_rescue_host_result
+    _fields_ = [("nreads", C.c_int64), ("total_regs", C.c_int64), ("regs", C.c_void_p), ("reg_off", C.c_void_p), ("status", C.c_void_p),
+                ("n_wave", C.c_int64), ("n_tested", C.c_int64), ("n_pushed", C.c_int64), ("n_removed", C.c_int64), ("kernel_ms", C.c_float)]
+
+
+class RescueDeviceOut(C.Structure):     # meme_rescue_device_out
+    _fields_ = [(n, C.c_void_p) for n in ("d_regs_out", "d_reg_off_out", "d_status", "d_counters")]
+
+
+def default_rescue_opt(**kw):
+    # mem_opt_init (reference src/bwamem.cpp:126-162): pen_unpaired 17, max_matesw 50, min_seed_len 19, max_chain_gap 10000, mask_level_redun 0.95; batch_reads: BATCH_SIZE
+    o = RescueOpt(17, 50, 19, 512, 10000, 0.95)
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
+
+
+def mate_pes(pes):
+    """four (low, high, failed, ...) -> meme_pestat[4]"""
+    pes4 = np.zeros((4, 4), np.int32)
+    pes4[:, :3] = np.asarray([[int(x) for x in p[:3]] for p in pes], np.int32).reshape(4, 3)
+    return pes4
+
+
 class MateOpt(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("a", "b", "o_del", "e_del", "o_ins", "e_ins", "pen_unpaired", "max_matesw", "min_seed_len", "batch_reads")]
 
@@ -259,7 +292,7 @@ EXPORTS = ["meme_device_count", "meme_ctx_create", "meme_ctx_destroy", "meme_las
            "meme_index_pos5_bytes",
            "meme_index_attach", "meme_index_describe", "meme_index_share", "meme_index_replicate", "meme_host_alloc",
            "meme_host_free", "meme_stage_pack_text", "meme_stage_pos5_from_sa", "meme_stage_build_entries", "meme_stage_build_plcp",
-           "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_primary_batch_host", "meme_primary_batch_device", "meme_finish_batch_host", "meme_finish_batch_device", "meme_pair_batch_host", "meme_pair_batch_device", "meme_pair_decide_batch_host", "meme_pair_decide_batch_device", "meme_seed_batch_device",
+           "meme_stage_entries_from_sa", "meme_stage_rmi32", "meme_sa_build_device", "meme_prmi_train_device", "meme_seed_batch", "meme_seed_batch_host", "meme_seed_batch_resident", "meme_seed_batch_resident_ascii", "meme_seed_reserve", "meme_chain_last_batch_host", "meme_chain_batch_host", "meme_extend_last_batch_host", "meme_global_batch_host", "meme_gen_cigar_batch_host", "meme_sam_stage_text", "meme_sam_format_batch_host", "meme_kswv_batch_host", "meme_matesw_batch_host", "meme_primary_batch_host", "meme_primary_batch_device", "meme_finish_batch_host", "meme_finish_batch_device", "meme_pair_batch_host", "meme_pair_batch_device", "meme_pair_decide_batch_host", "meme_pair_decide_batch_device", "meme_rescue_batch_host", "meme_rescue_batch_device", "meme_matesw_last_device", "meme_seed_batch_device",
            "meme_bsw_batch", "meme_bsw_batch_device", "meme_get_timings", "meme_set_tuning", "meme_debug_packed_reads",
            "meme_debug_reseed_counts", "meme_debug_seed_r3_counts", "meme_debug_sa_stats", "meme_debug_scan_exclusive"]
 
@@ -665,6 +698,51 @@ class Context:
         out = DecideDeviceOut(d_path_ptr, d_sel_ptr, d_q_se_ptr, d_q_pe_ptr, d_flag_ptr, d_alt_ptr, d_status_ptr, d_n_heavy_ptr)
         _check(lib().meme_pair_decide_batch_device(C.c_void_p(self.h), C.c_void_p(d_regs_ptr), C.c_void_p(d_reg_off_ptr), C.c_void_p(d_n_pri_ptr), C.c_int64(nreads), C.c_int64(total_regs),
                                                    C.byref(pin), C.c_int64(int(l_pac)), pair_pes(pes), C.byref(opt or default_decide_opt()), C.byref(out)))
+
+    def rescue_batch_host(self, regs, reg_off, use_mate_sort, read_len, jobs, pes, contigs, l_pac, opt=None):
+        """meme_rescue_batch_host: mate rescue's record updates (mem_sam_pe_batch_post in front of the primary marking) for the records regs (ALNREG) per read as
+        finish_batch_host leaves them, with its use_mate_sort -- reads 2p and 2p + 1 are pair p; read_len: l_seq per read; jobs: what matesw_batch_host returned (gar,
+        gar_off, job_off, res); pes: four (low, high, failed, ...).  Returns dict(regs, reg_off, status, n_wave, n_tested, n_pushed, n_removed, kernel_ms)."""
+        opt = opt or default_rescue_opt()
+        assert regs.dtype == ALNREG and regs.flags.c_contiguous
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
+        n = reg_off.shape[0] - 1
+        ums = np.ascontiguousarray(use_mate_sort, dtype=np.uint8)
+        rlen = np.ascontiguousarray(read_len, dtype=np.int32)
+        assert ums.shape[0] == n and rlen.shape[0] == n
+        gar = np.ascontiguousarray(jobs["gar"], dtype=np.int32)
+        gar_off = np.ascontiguousarray(jobs["gar_off"], dtype=np.int64)
+        job_off = np.ascontiguousarray(jobs["job_off"], dtype=np.int64)
+        kres = np.ascontiguousarray(jobs["res"], dtype=KSWR)
+        assert gar_off.shape == job_off.shape
+        jin = RescueJobsIn(_p(gar), _p(gar_off), _p(job_off), gar_off.shape[0] - 1, _p(kres), kres.shape[0])
+        arr = _contig_array(contigs)
+        pes4 = mate_pes(pes)
+        res = RescueHost()
+        _check(lib().meme_rescue_batch_host(C.c_void_p(self.h), _p(regs), _p(reg_off), _p(ums), _p(rlen), C.c_int64(n), C.byref(jin), _p(pes4), arr, C.c_int32(len(contigs)),
+                                            C.c_int64(int(l_pac)), C.byref(opt), C.byref(res)))
+        return {"regs": _view(res.regs, res.total_regs, ALNREG), "reg_off": _view(res.reg_off, res.nreads + 1, np.int64), "status": _view(res.status, res.nreads, np.uint8),
+                "n_wave": int(res.n_wave), "n_tested": int(res.n_tested), "n_pushed": int(res.n_pushed), "n_removed": int(res.n_removed), "kernel_ms": float(res.kernel_ms)}
+
+    def rescue_batch_device(self, d_regs_ptr, d_reg_off_ptr, d_use_mate_sort_ptr, d_read_len_ptr, nreads, total_regs, d_jobs, pes, contigs, l_pac, opt, d_regs_out_ptr, d_reg_off_out_ptr,
+                            d_status_ptr, d_counters_ptr):
+        """meme_rescue_batch_device: the same on device arrays the caller owns (d_regs_out, d_reg_off_out and d_use_mate_sort of finish_batch_device as they are; d_jobs: the dict
+        matesw_last_device returns, or one of device pointers gar, gar_off, job_off, nbatches, res, njobs); d_regs_out: room for total_regs + njobs records.  Asynchronous on
+        the ctx's stream (sync() before reading the results)."""
+        jin = RescueJobsIn(d_jobs["gar"], d_jobs["gar_off"], d_jobs["job_off"], int(d_jobs["nbatches"]), d_jobs["res"], int(d_jobs["njobs"]))
+        arr = _contig_array(contigs)
+        out = RescueDeviceOut(d_regs_out_ptr, d_reg_off_out_ptr, d_status_ptr, d_counters_ptr)
+        pes4 = mate_pes(pes)
+        _check(lib().meme_rescue_batch_device(C.c_void_p(self.h), C.c_void_p(d_regs_ptr), C.c_void_p(d_reg_off_ptr), C.c_void_p(d_use_mate_sort_ptr), C.c_void_p(d_read_len_ptr),
+                                              C.c_int64(nreads), C.c_int64(total_regs), C.byref(jin), _p(pes4), arr, C.c_int32(len(contigs)), C.c_int64(int(l_pac)),
+                                              C.byref(opt or default_rescue_opt()), C.byref(out)))
+
+    def matesw_last_device(self):
+        """meme_matesw_last_device: the device pointers of the last matesw_batch_host call's gar, gar_off, job_off and res (valid until the ctx's next mate call), as the
+        dict rescue_batch_device takes."""
+        v = RescueJobsIn()
+        _check(lib().meme_matesw_last_device(C.c_void_p(self.h), C.byref(v)))
+        return {"gar": v.gar, "gar_off": v.gar_off, "job_off": v.job_off, "nbatches": int(v.nbatches), "res": v.res, "njobs": int(v.njobs)}
 
     def finish_batch_host(self, regs, reg_off, contigs, l_pac, opt=None):
         """meme_finish_batch_host: record finishing (compaction to the live records, mem_sort_dedup_patch_mate_sort, is_alt) of the records regs (ALNREG) per read;

@@ -21,6 +21,9 @@
  *   meme_primary_batch_host         <- mem_mark_primary_se() + mem_reorder_primary5() + mem_approx_mapq_se()   src/bwamem.cpp:1974-2100
  *   meme_pair_batch_host            <- mem_pair()                                    src/bwamem_pair.cpp:372-433
  *   meme_pair_decide_batch_host     <- mem_sam_pe() behind mem_pair(): the pairing decision   src/bwamem_pair.cpp:536-590, 632-648
+ *   meme_rescue_batch_host          <- mem_sam_pe_batch_post() in front of mem_mark_primary_se(): mate rescue's record updates,
+ *                                      mem_matesw_batch_post() / _post_mate_sort()      src/bwamem_pair.cpp:851-921, 1225-1334, 1337-1485
+ *   meme_matesw_last_device         <- the `aln` and `gar` arrays worker_sam hands from mem_sam_pe_batch() to mem_sam_pe_batch_post()   src/bwamem.cpp:1855-1877
  *   meme_bsw_batch                  <- BandedPairWiseSW::getScores8 / getScores16 /
  *                                      scalarBandedSWAWrapper                 src/bandedSWA.h:118-135,257-297
  *
@@ -489,7 +492,7 @@ int meme_pair_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs, const int64
  * of :581-590 over ALL records of an end on paths 2 / 3) as the reference leaves them for mem_reg2aln and the SAM text.  Nothing else of a record changes.
  * Logarithms (:552 and mem_approx_mapq_se's) are looked up in the ctx's table of the host libm's log((double)k), k < 65536; the sum of the two frac_rep of
  * :556 is a float sum, as x86-64 evaluates it.  Only the mapQ_coef_len > 0 branch of mem_approx_mapq_se exists, as in the primary stage.
- * What it does NOT do: mate rescue in front of mem_pair (its record updates stay with the caller, and with them the binding's call of the reference);
+ * What it does NOT do: mate rescue in front of mem_pair (its record updates are the stage meme_rescue_batch_* below; the binding still calls the reference);
  * mem_reg2sam's record list for paths 0 / 1; mem_gen_alt / XA; the SAM text.
  * status[p] = 0: fine.  1: the pair stage's status was non-zero, or a logarithm beyond the table was asked for (n_sub + 1 or an alignment span of 65536 and
  * more): the outputs are the defaults (path 0, sel -1, -1, zeros, flag 1, alt -1, -1) and the pair's records are untouched.  2 (device form only; the host form
@@ -562,6 +565,52 @@ int meme_finish_batch_host(meme_ctx* ctx, const meme_alnreg* regs, const int64_t
 typedef struct { meme_alnreg* d_regs_out; int64_t* d_reg_off_out; uint8_t* d_use_mate_sort; uint8_t* d_status; uint64_t* d_counters; } meme_finish_device_out;
 int meme_finish_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs, const int64_t* d_reg_off, int64_t nreads, int64_t total_regs,
                              const meme_contig* contigs, int32_t n_contigs, int64_t l_pac, const meme_finish_opt* opt, const meme_finish_device_out* out);
+
+/* ---- mate rescue's record updates: mem_sam_pe_batch_post in front of the primary marking ---------------------------------------------------------
+ * What mem_sam_pe_batch_post (reference src/bwamem_pair.cpp:851-921) does with the kswr_t results of mate rescue before it marks primaries, for every pair of a
+ * batch (reads 2p, 2p + 1): for each end i the records within pen_unpaired of its first, at most max_matesw of them (a snapshot taken before any update), and for each
+ * of those mem_matesw_batch_post (:1225-1334) -- or, where use_mate_sort of BOTH ends is set, mem_matesw_batch_post_mate_sort (:1337-1485) between sort_alnreg_re and
+ * mem_sort_dedup_patch / sort_alnreg_score (:875, :886-892) -- on the other end's list: the orientations that pes[] allows and no record the list holds NOW explains,
+ * the window clamped to the sequence of its midpoint, the result gar points to, the record it becomes (:1302-1313), its insertion (by score :1315-1322; by end, with
+ * the resort branch, :1431-1474) and mem_sort_dedup_patch (src/bwamem.cpp:385-446) / mem_dedup_patch (:258-308) with bns == 0 inside the orientation loop.  flg = 0
+ * on every record (:859-862).
+ * Inputs are exactly what the stages in front leave: regs, reg_off and use_mate_sort of meme_finish_batch_*; read_len[r] = l_seq of read r (the stage needs neither an
+ * index nor a resident batch); jobs = gar, gar_off, job_off, nbatches, res and njobs of meme_matesw_batch_host (host pointers for the host form; the device pointers
+ * of meme_matesw_last_device for the device form), posed with the same pen_unpaired, max_matesw, min_seed_len and batch_reads; pes[4]; the contigs.
+ * Outputs: the records per read in the reference's order behind the loop, compact offsets; a new record carries rid, is_alt, qb, qe, rb, re, score, csub, seedcov,
+ * secondary = -1, n_comp and zeros; an old one what went in but for flg, n_comp and its place.
+ * status[r] = 0: fine.  1: an orientation the walk of list r reaches has gar == -1 or an index outside the batch's jobs -- the reference would call ksw_align2
+ * there (:1290-1296); read r's records come back as they went in, flg included, so that the caller can give the pair to the reference.  Lists into which no result
+ * can be pushed (no gar entry >= 0 among the other end's records looked at) are walked only on the mate-sort path, where they hold two records or more, and report 0 otherwise.  2 (device form only): reg_off of
+ * the read or of its mate is no span inside [0, total_regs], the gar entries of its batch end before the pair's (or gar / res is null where the offsets say it holds entries), or the output does not hold the list; the read
+ * keeps its input where that is a span and the output holds it.
+ * MEME_E_ARG: nreads odd, a null argument, max_matesw < 0, batch_reads odd or < 2, nbatches not ceil(nreads / batch_reads), a record array that is not 16-byte
+ * aligned.  Host form: results in pinned memory of the ctx until its next call of this function. */
+typedef struct { int32_t pen_unpaired, max_matesw, min_seed_len, batch_reads, max_chain_gap; float mask_level_redun; } meme_rescue_opt;   /* mem_opt_t fields; batch_reads as meme_mate_opt */
+/* the mate stage's outputs: host pointers for the host form, device pointers for the device form */
+typedef struct { const int32_t* gar; const int64_t* gar_off; const int64_t* job_off; int64_t nbatches; const meme_kswr* res; int64_t njobs; } meme_rescue_jobs_in;
+typedef struct {
+    int64_t nreads, total_regs;            /* records behind the stage */
+    const meme_alnreg* regs;
+    const int64_t* reg_off;                /* nreads + 1, compact */
+    const uint8_t* status;                 /* nreads */
+    int64_t n_wave, n_tested, n_pushed, n_removed;   /* lists the wavefront tier walked; the sum of the post functions' return values; records pushed; records removed */
+    float kernel_ms;                       /* HIP events around the stage's kernels */
+} meme_rescue_host_result;
+int meme_rescue_batch_host(meme_ctx* ctx, const meme_alnreg* regs, const int64_t* reg_off /* nreads + 1, from 0 */, const uint8_t* use_mate_sort /* nreads */,
+                           const int32_t* read_len /* nreads */, int64_t nreads, const meme_rescue_jobs_in* jobs, const meme_pestat* pes /* 4 */,
+                           const meme_contig* contigs, int32_t n_contigs, int64_t l_pac, const meme_rescue_opt* opt, meme_rescue_host_result* out);
+/* The same on device arrays the caller owns, asynchronous on the ctx's stream: nothing is copied and the host does not wait.  d_regs_out: room for total_regs +
+ * jobs->njobs records (16-byte aligned, not d_regs); d_reg_off_out: nreads + 1; d_status: nreads; d_counters: 8 words, [0] n_wave, [1] n_tested, [2] n_pushed,
+ * [3] n_removed.  d_regs_out and d_reg_off_out go to meme_primary_batch_device as they are, with total_regs + njobs as the bound of the record array. */
+typedef struct { meme_alnreg* d_regs_out; int64_t* d_reg_off_out; uint8_t* d_status; uint64_t* d_counters; } meme_rescue_device_out;
+int meme_rescue_batch_device(meme_ctx* ctx, const meme_alnreg* d_regs, const int64_t* d_reg_off, const uint8_t* d_use_mate_sort, const int32_t* d_read_len, int64_t nreads,
+                             int64_t total_regs, const meme_rescue_jobs_in* d_jobs, const meme_pestat* pes /* 4 */, const meme_contig* contigs, int32_t n_contigs, int64_t l_pac,
+                             const meme_rescue_opt* opt, const meme_rescue_device_out* out);
+/* The device pointers of what the ctx's last meme_matesw_batch_host call computed -- gar, gar_off and job_off as the posing kernels left them, res in posing order as
+ * the Smith-Waterman launches wrote it -- valid until that ctx's next mate (or kswv) call.  MEME_E_STATE without such a call.  Changes nothing of what
+ * meme_matesw_batch_host returns. */
+int meme_matesw_last_device(meme_ctx* ctx, meme_rescue_jobs_in* view);
 
 /* ---- measurement ---------------------------------------------------------------------------------
  * HIP-event timings of the kernels of the last *_device call, measured on the ctx's stream.          */
